@@ -18,11 +18,15 @@ association (Hungarian: every rank its own frame pairs + one MAX all-reduce of t
 arcs of an all-ones mask are rebuilt on every rank, so the all-gather stays the only collective before the replicated solve), and
 every rank materialises its own block of IDed_dets_all (its frames x the identities alive in them).
 
-Prints ONE JSON line on rank 0 (contract: see the task description), with
+Prints ONE JSON line on rank 0 (contract: see the task description). A plain run sets up, warms up, times --steps passes
+and prints the headline (metric, value, unit, ms_per_step, dtype, config, ...); --dump-outputs DIR also writes what the
+last timed pass computed as DIR/<name>.npy. Everything else runs only with --full, after the timed region:
   roofline     -- dominant kernel: algorithmic FLOPs / HIP-event time measured inside the timed
                   region on the launch stream, against the f32 MFMA peak (157.3 TFLOP/s);
   cpu_baseline -- the CPU oracle (a port of the reference's algorithm, oracle/) timed on this
-                  box's host cores on a bounded sample of the same workload.
+                  box's host cores on a bounded sample of the same workload;
+  and the stage breakdown, the other arithmetic / association / input variants, the passes over a fresh timelapse, the
+  flow certificate and the self-check against the CPU oracle (`verified`).
 """
 import argparse
 import json
@@ -103,7 +107,15 @@ def main():
     ap.add_argument('--replicated-solve', action='store_true', help='N > 1, --assoc mcf: every rank solves the whole flow problem (round 2) instead of sharing it')
     ap.add_argument('--launch-check', action='store_true',
                     help='no GPU work: every rank joins a gloo group, one all-reduce, rank 0 prints what it saw (tests the launcher)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also measure and check everything beyond the headline: per-kernel table and roofline, '
+                         'stage breakdown, the other variants, fresh-timelapse passes, the self-check against the CPU oracle, the CPU '
+                         'baseline (--no-profile, --no-verify, --no-host-variant and --cpu-frames select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     resolve_workload(args)
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -155,7 +167,7 @@ def main():
     if args.workload == 'c5':                       # BASELINE config 5: occlusion mask, path costs on the masked grid
         mask = synth.corridor_mask(H, W, width=40, pitch=128)
         frames *= mask[None].astype(np.float32)
-    frames_host = frames if (rank == 0 and not args.no_verify) else None     # the checker's copy (rank 0's block)
+    frames_host = frames if (rank == 0 and args.full and not args.no_verify) else None     # the checker's copy (rank 0's block)
     sd = synth.synth_state_dict(42)
     P = params.load_parameters()
     P['DEVICE'] = str(dev)
@@ -209,7 +221,7 @@ def main():
     # pass, so it stays outside the timed region). Inside the timed region only the dominant kernel is bracketed:
     # its time there is what roofline.achieved is computed from.
     table, dom_idx = None, None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         model.set_profiling(True)
         model.read_profile()
         step()
@@ -224,13 +236,63 @@ def main():
     sync_all()
     dt = time.perf_counter() - t0
     prof = None
-    if not args.no_profile:
+    if table is not None:
         prof = model.read_profile()
         model.set_profiling(False)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ad, args.associates)
+
+    def headline():
+        value = total_frames * args.steps / dt
+        out = {
+            'metric': (f'frames/sec end-to-end detect+associate, {H}x{W}xT timelapse' if args.associates
+                       else 'frames/sec detection only (CNN forward + NMS), 512x512xT timelapse')
+                      + (' -- raw uint16 input in host memory, H2D copy and preprocessing inside every pass (PCIe-inclusive)' if args.input == 'host' else ''),
+            'value': round(value, 2), 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f32' if args.arith != 'bf16x3' else 'f32 via 3 x bf16 split operands (6 partial products, f32 accumulate) in conv blocks 2-8; f32 elsewhere',
+            'data': 'synthetic',
+            'config': {'workload': f'{args.workload}: synthetic {H}x{W}x{args.frames} grayscale timelapse per GPU, '
+                                   + (f'detection + path-cost matrix + {"Hungarian (frame-to-frame)" if args.assoc == "hungarian" else "global min-cost-flow"} association (IDed_dets_all)'
+                                      if args.associates else 'detection only')
+                                   + ('' if not args.big else
+                                      f'; BASELINE config {args.workload[1]} = {BIG_CONFIGS[args.workload][0]}x{BIG_CONFIGS[args.workload][0]}x{BIG_CONFIGS[args.workload][1]} on '
+                                      f'{BIG_CONFIGS[args.workload][2]} GPUs' + (', occlusion mask (40-px corridors on a 128-px lattice), path costs on the masked grid' if mask is not None else ', all-ones mask')
+                                      + f': this run is {world} of {BIG_CONFIGS[args.workload][2]} GPU shares ({per_rank} detection frames per GPU), the timelapse it solves has {total_frames} detection frames'),
+                       'association': args.assoc if args.associates else None,
+                       'detection_frames_per_gpu': per_rank, 'tiles_per_frame': n_tiles,
+                       'weights': 'random-init (synth seed 42)', 'parallelism': f'frame-sharded x{world}',
+                       'input': 'hbm_resident' if args.input == 'hbm' else 'host_u16',
+                       'input_detail': ('preprocessed f32 frames resident in HBM when the timed region starts' if args.input == 'hbm' else
+                                        f'raw uint16 frames in pinned host memory: every pass copies them on a second stream (16-frame pieces) beside '
+                                        f'axt_preprocess_u16 and the CNN of the frames already there (chunks of 16, 32, 48, 64, 80, then {args.chunk} frames; PCIe-inclusive)'),
+                       'steady_state': {'what': 'the timed passes run over ONE timelapse object: its kept-tile list (a property of the dataset, Timelapse.py:551-558) '
+                                                'is computed by the first pass and kept, and IDed_dets_all is sized from the identity count of the previous pass '
+                                                'over a timelapse of this shape instead of a device-to-host round trip; packed weights belong to the Detector'},
+                       'cnn_arith': args.arith,
+                       'conv_algorithm': ('Winograd F(2x2,3x3), f32, for the six stride-1 conv blocks (2,4,5,7,8,10); direct for the two stride-2 blocks'
+                                          if winograd else 'direct') + ('; the two stride-2 blocks fused into one kernel' if getattr(model, 'fused_front', False) else '')},
+            'detections': int(ad._host_dets()[0].sum()),
+        }
+        if world > 1:
+            out['rccl_world'] = dist.get_world_size() if args.backend == 'nccl' else 0
+            out['backend'] = args.backend
+        if args.associates:
+            out['n_ids'] = getattr(ad, 'n_ids', None)
+        return out
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- stage breakdown (one extra, untimed, synchronised step on rank 0's clock)
     stages = {}
@@ -365,54 +427,19 @@ def main():
         del ac
 
     if rank == 0:
-        value = total_frames * args.steps / dt
-        out = {
-            'metric': (f'frames/sec end-to-end detect+associate, {H}x{W}xT timelapse' if args.associates
-                       else 'frames/sec detection only (CNN forward + NMS), 512x512xT timelapse')
-                      + (' -- raw uint16 input in host memory, H2D copy and preprocessing inside every pass (PCIe-inclusive)' if args.input == 'host' else ''),
-            'value': round(value, 2), 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f32' if args.arith != 'bf16x3' else 'f32 via 3 x bf16 split operands (6 partial products, f32 accumulate) in conv blocks 2-8; f32 elsewhere',
-            'data': 'synthetic',
-            'config': {'workload': f'{args.workload}: synthetic {H}x{W}x{args.frames} grayscale timelapse per GPU, '
-                                   + (f'detection + path-cost matrix + {"Hungarian (frame-to-frame)" if args.assoc == "hungarian" else "global min-cost-flow"} association (IDed_dets_all)'
-                                      if args.associates else 'detection only')
-                                   + ('' if not args.big else
-                                      f'; BASELINE config {args.workload[1]} = {BIG_CONFIGS[args.workload][0]}x{BIG_CONFIGS[args.workload][0]}x{BIG_CONFIGS[args.workload][1]} on '
-                                      f'{BIG_CONFIGS[args.workload][2]} GPUs' + (', occlusion mask (40-px corridors on a 128-px lattice), path costs on the masked grid' if mask is not None else ', all-ones mask')
-                                      + f': this run is {world} of {BIG_CONFIGS[args.workload][2]} GPU shares ({per_rank} detection frames per GPU), the timelapse it solves has {total_frames} detection frames'),
-                       'association': args.assoc if args.associates else None,
-                       'detection_frames_per_gpu': per_rank, 'tiles_per_frame': n_tiles,
-                       'weights': 'random-init (synth seed 42)', 'parallelism': f'frame-sharded x{world}',
-                       'input': 'hbm_resident' if args.input == 'hbm' else 'host_u16',
-                       'input_detail': ('preprocessed f32 frames resident in HBM when the timed region starts' if args.input == 'hbm' else
-                                        f'raw uint16 frames in pinned host memory: every pass copies them on a second stream (16-frame pieces) beside '
-                                        f'axt_preprocess_u16 and the CNN of the frames already there (chunks of 16, 32, 48, 64, 80, then {args.chunk} frames; PCIe-inclusive)'),
-                       'steady_state': {'what': 'the timed passes run over ONE timelapse object: its kept-tile list (a property of the dataset, Timelapse.py:551-558) '
-                                                'is computed by the first pass and kept, and IDed_dets_all is sized from the identity count of the previous pass '
-                                                'over a timelapse of this shape instead of a device-to-host round trip; packed weights belong to the Detector',
-                                        'fresh_timelapse_pass_ms': fresh_ms,
-                                        'fresh_timelapse_next_passes_ms': fresh_next_ms,
-                                        'fresh_timelapse_pass': 'passes over NEW Timelapse objects of the same frames with the identity-count guess cleared (after the timed region): the first one, and the mean of the following ones (each again over a new object): the first also pays what a process pays once (allocator pools for the new buffers)'},
-                       'cnn_arith': args.arith,
-                       'conv_algorithm': ('Winograd F(2x2,3x3), f32, for the six stride-1 conv blocks (2,4,5,7,8,10); direct for the two stride-2 blocks'
-                                          if winograd else 'direct') + ('; the two stride-2 blocks fused into one kernel' if getattr(model, 'fused_front', False) else '')},
-            'stages': stages,
-            'detections': int(ad._host_dets()[0].sum()),
-        }
-        if world > 1:
-            out['rccl_world'] = dist.get_world_size() if args.backend == 'nccl' else 0
-            out['backend'] = args.backend
-            if args.associates:
-                out['collectives_ms'] = collectives
-                out['tracks_identical_on_all_ranks'] = same_on_all_ranks
+        out = headline()
+        out['config']['steady_state'].update({
+            'fresh_timelapse_pass_ms': fresh_ms,
+            'fresh_timelapse_next_passes_ms': fresh_next_ms,
+            'fresh_timelapse_pass': 'passes over NEW Timelapse objects of the same frames with the identity-count guess cleared (after the timed region): the first one, and the mean of the following ones (each again over a new object): the first also pays what a process pays once (allocator pools for the new buffers)'})
+        out['stages'] = stages
+        if world > 1 and args.associates:
+            out['collectives_ms'] = collectives
+            out['tracks_identical_on_all_ranks'] = same_on_all_ranks
         if not args.no_verify:
             out.update(verify(args, ad, frames_host, sd, per_rank, world, mask, cert))
-        if args.associates:
-            out['n_ids'] = getattr(ad, 'n_ids', None)
-            if other:
-                out['other_association_variant'] = other
+        if args.associates and other:
+            out['other_association_variant'] = other
         if direct:
             out['other_arithmetic_variant'] = direct
         if host_variant:
@@ -469,8 +496,8 @@ def assoc_only(args):
     per frame that are born, move <= 10 px per frame, are missed 8 % of the time and die; 8 % clutter) are resident in HBM;
     one step = AxonDetections.assign_ids(): observation costs, admissible arcs (GPU), the association (--assoc mcf: the
     reference's global min-cost-flow tracker, host solve; hungarian: the frame-to-frame variant, GPU) and IDed_dets_all.
-    Verified outside the timed region: the flow tracker against the successive-shortest-path solver (same trajectories
-    and cost), the frame-to-frame variant against the oracle's."""
+    With --full, verified outside the timed region: the flow tracker against the successive-shortest-path solver (same
+    trajectories and cost), the frame-to-frame variant against the oracle's."""
     import axtrack_amd
     from axtrack_amd import synth, params, hotpath as hp
     from axtrack_amd.detections import _cost_units_on_device
@@ -497,50 +524,9 @@ def assoc_only(args):
         ad = step()
     torch.cuda.synchronize(dev)
     dt = (time.perf_counter() - t0) / args.steps
-    # the arc builder alone (HBM-bound integer work), with events on its stream
-    dmax, units = _cost_units_on_device(P, 500, dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    hp.build_arcs(cx, cy, cc, size, size, dmax, units)
-    e0.record()
-    for _ in range(5):
-        arcs = hp.build_arcs(cx, cy, cc, size, size, dmax, units)
-    e1.record()
-    torch.cuda.synchronize(dev)
-    arcs_ms = e0.elapsed_time(e1) / 5
-    n_det, n_arcs = int(d['count'].sum()), int(arcs[1].numel())
-    arc_bytes = 12 * n_det * (1 + len(dmax)) + 15 * n_arcs        # anchors read per (frame, gap), 15 B per admitted arc
-    ok, what = None, 'not checked'
-    if not args.no_verify:
-        if args.assoc == 'mcf':
-            os.environ['AXT_MCF_FORCE_SSP'] = '1'
-            ref = step()
-            del os.environ['AXT_MCF_FORCE_SSP']
-            ok = bool(np.array_equal(ref._track_flat, ad._track_flat) and ref.mcf_total_cost == ad.mcf_total_cost)
-            what = 'trajectories and total cost equal to the successive-shortest-path solver on the same network'
-        else:
-            from oracle import oracle as orc
-            dets = [(d['conf'][t, :d['count'][t]], d['x'][t, :d['count'][t]].astype(np.int64), d['y'][t, :d['count'][t]].astype(np.int64)) for t in range(F)]
-            trajs = orc.hungarian_assoc(dets, size, size, dict(orc.DEFAULTS))
-            frame_of = np.repeat(np.arange(F), d['count'])
-            offs = np.concatenate([[0], np.cumsum(d['count'])])
-            got = {}
-            for k, tid in enumerate(ad._track_flat):
-                if tid >= 0:
-                    got.setdefault(int(tid), []).append((int(frame_of[k]), int(k - offs[frame_of[k]])))
-            ok = [sorted(got[i]) for i in sorted(got)] == trajs
-            what = 'trajectories equal to the oracle (hungarian)'
-    # how well the association recovers the scene's cones: detections of one cone that share one identity
-    truth = np.concatenate([d['truth'][t, :d['count'][t]] for t in range(F)])
-    tr = ad._track_flat
-    both = (truth >= 0) & (tr >= 0)
-    purity = None
-    if both.any():
-        pairs = np.stack([truth[both], tr[both]], 1)
-        _, inv, cnts = np.unique(pairs, axis=0, return_inverse=True, return_counts=True)
-        best = {}
-        for (c_, _t), n_ in zip(np.unique(pairs, axis=0), cnts):
-            best[c_] = max(best.get(c_, 0), n_)
-        purity = round(sum(best.values()) / max(int((truth >= 0).sum()), 1), 4)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ad, True)
+    n_det = int(d['count'].sum())
     out = {'metric': f'frames/sec association only ({"global min-cost flow" if args.assoc == "mcf" else "frame-to-frame Hungarian"}), '
                      f'{size}x{size}x{F + 4} scene of moving growth cones',
            'value': round(F / dt, 2), 'unit': 'frames/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
@@ -548,16 +534,98 @@ def assoc_only(args):
            'dtype': 'int64 (integer arc costs); f64 observation costs', 'data': 'synthetic',
            'config': {'workload': f'{args.workload}: association only -- {F} frames of {size}x{size}, ~{alive} moving cones per frame (born, '
                                   f'<= 10 px per frame, missed 8 %, dying; 8 % clutter), detections resident in HBM',
-                      'association': args.assoc, 'input': 'detections_hbm_resident', 'detections': n_det, 'arcs': n_arcs},
-           'n_ids': ad.n_ids, 'cones_in_scene': int(len(np.unique(truth[truth >= 0]))), 'detections_of_a_cone_under_its_main_identity': purity,
-           'verified': ok, 'verify': what,
-           'roofline': {'bound': 'hbm', 'kernel': 'axt_build_arcs (count + fill passes)', 'achieved': round(arc_bytes / (arcs_ms * 1e-3) / 1e9, 2),
-                        'peak': 8000.0, 'unit': 'GB/s', 'frac': round(arc_bytes / (arcs_ms * 1e-3) / 1e9 / 8000.0, 5), 'traffic': None,
-                        'avg_launch_ms': round(arcs_ms, 4), 'bytes_per_launch': arc_bytes,
-                        'note': 'algorithmic bytes (12 B per detection and (frame, gap) + 15 B per admitted arc) over HIP-event time; the pass is '
-                                'latency-bound at this size; the flow solve itself is host work and has no roofline'},
-           'solver_threads': min(len(os.sched_getaffinity(0)), 16)}
+                      'association': args.assoc, 'input': 'detections_hbm_resident', 'detections': n_det},
+           'n_ids': ad.n_ids, 'solver_threads': min(len(os.sched_getaffinity(0)), 16)}
+    if args.full:
+        # the arc builder alone (HBM-bound integer work), with events on its stream
+        dmax, units = _cost_units_on_device(P, 500, dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        hp.build_arcs(cx, cy, cc, size, size, dmax, units)
+        e0.record()
+        for _ in range(5):
+            arcs = hp.build_arcs(cx, cy, cc, size, size, dmax, units)
+        e1.record()
+        torch.cuda.synchronize(dev)
+        arcs_ms = e0.elapsed_time(e1) / 5
+        n_arcs = int(arcs[1].numel())
+        arc_bytes = 12 * n_det * (1 + len(dmax)) + 15 * n_arcs        # anchors read per (frame, gap), 15 B per admitted arc
+        ok, what = None, 'not checked'
+        if not args.no_verify:
+            if args.assoc == 'mcf':
+                os.environ['AXT_MCF_FORCE_SSP'] = '1'
+                ref = step()
+                del os.environ['AXT_MCF_FORCE_SSP']
+                ok = bool(np.array_equal(ref._track_flat, ad._track_flat) and ref.mcf_total_cost == ad.mcf_total_cost)
+                what = 'trajectories and total cost equal to the successive-shortest-path solver on the same network'
+            else:
+                from oracle import oracle as orc
+                dets = [(d['conf'][t, :d['count'][t]], d['x'][t, :d['count'][t]].astype(np.int64), d['y'][t, :d['count'][t]].astype(np.int64)) for t in range(F)]
+                trajs = orc.hungarian_assoc(dets, size, size, dict(orc.DEFAULTS))
+                frame_of = np.repeat(np.arange(F), d['count'])
+                offs = np.concatenate([[0], np.cumsum(d['count'])])
+                got = {}
+                for k, tid in enumerate(ad._track_flat):
+                    if tid >= 0:
+                        got.setdefault(int(tid), []).append((int(frame_of[k]), int(k - offs[frame_of[k]])))
+                ok = [sorted(got[i]) for i in sorted(got)] == trajs
+                what = 'trajectories equal to the oracle (hungarian)'
+        # how well the association recovers the scene's cones: detections of one cone that share one identity
+        truth = np.concatenate([d['truth'][t, :d['count'][t]] for t in range(F)])
+        tr = ad._track_flat
+        both = (truth >= 0) & (tr >= 0)
+        purity = None
+        if both.any():
+            pairs = np.stack([truth[both], tr[both]], 1)
+            _, inv, cnts = np.unique(pairs, axis=0, return_inverse=True, return_counts=True)
+            best = {}
+            for (c_, _t), n_ in zip(np.unique(pairs, axis=0), cnts):
+                best[c_] = max(best.get(c_, 0), n_)
+            purity = round(sum(best.values()) / max(int((truth >= 0).sum()), 1), 4)
+        out['config']['arcs'] = n_arcs
+        out.update({'cones_in_scene': int(len(np.unique(truth[truth >= 0]))), 'detections_of_a_cone_under_its_main_identity': purity,
+                    'verified': ok, 'verify': what,
+                    'roofline': {'bound': 'hbm', 'kernel': 'axt_build_arcs (count + fill passes)', 'achieved': round(arc_bytes / (arcs_ms * 1e-3) / 1e9, 2),
+                                 'peak': 8000.0, 'unit': 'GB/s', 'frac': round(arc_bytes / (arcs_ms * 1e-3) / 1e9 / 8000.0, 5), 'traffic': None,
+                                 'avg_launch_ms': round(arcs_ms, 4), 'bytes_per_launch': arc_bytes,
+                                 'note': 'algorithmic bytes (12 B per detection and (frame, gap) + 15 B per admitted arc) over HIP-event time; the pass is '
+                                         'latency-bound at this size; the flow solve itself is host work and has no roofline'}})
     print(json.dumps(out), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, ad, associates):
+    """--dump-outputs: what the last timed step hands its caller, as out_dir/<name>.npy in float32 / float64 (integers are
+    exact in float64): det_count [F] and the detection lists flat in frame-major order (det_conf, det_x, det_y); with an
+    association also track (trajectory id of every detection, -1 = none), ided_dets_all (the values of IDed_dets_all, 0
+    where an identity is absent) and ided_dets_all_present (1 where IDed_dets_all holds a value, 0 where it holds NaN), so
+    that every array is finite. If the arrays would exceed DUMP_LIMIT_BYTES, each is cut to the same fraction of its
+    rows, drawn with a fixed seed (arrays of one length share the rows), and <name>_rows.npy holds the row indices."""
+    cnt, conf, x, y = ad._host_dets()
+    valid = np.arange(conf.shape[1])[None, :] < cnt[:, None]
+    arrays = {'det_count': cnt.astype(np.float64), 'det_conf': conf[valid].astype(np.float32),
+              'det_x': x[valid].astype(np.float64), 'det_y': y[valid].astype(np.float64)}
+    if associates:
+        arrays['track'] = np.asarray(ad._track_flat).astype(np.float64)
+        if ad.IDed_dets_all is not None:
+            ided = ad.IDed_dets_all.to_numpy(dtype=np.float64)
+            present = ~np.isnan(ided)
+            arrays['ided_dets_all'] = np.where(present, ided, 0.0)
+            arrays['ided_dets_all_present'] = present.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES / total / 2                    # half the budget: room for the row indices
+        rows_of = {}
+        for name, a in list(arrays.items()):
+            if len(a) not in rows_of:
+                rng = np.random.default_rng(len(a))
+                rows_of[len(a)] = np.sort(rng.choice(len(a), int(len(a) * keep), replace=False))
+            arrays[name] = a[rows_of[len(a)]]
+            arrays[name + '_rows'] = rows_of[len(a)].astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
 
 
 def launch_ranks(n):

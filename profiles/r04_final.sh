@@ -16,14 +16,16 @@ if [ "$2" = full ]; then
   AXT_MCF_DEBUG=1 timeout -k 10 400 python profiles/full_config.py c5 > gpurun_out/${T}_c5_full.log 2>&1
   exit $?
 fi
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || exit 1
-timeout -k 10 300 python bench.py --assoc mcf --steps 10 --warmup 2 > gpurun_out/${T}_bench_mcf.json 2>> gpurun_out/${T}_bench.err || exit 1
-timeout -k 10 300 python bench.py --workload c4 --steps 5 --warmup 2 > gpurun_out/${T}_bench_c4.json 2>> gpurun_out/${T}_bench.err || exit 1
-timeout -k 10 400 python bench.py --workload c5 --steps 5 --warmup 2 > gpurun_out/${T}_bench_c5.json 2>> gpurun_out/${T}_bench.err || exit 1
-timeout -k 10 300 python bench.py --workload c2 --steps 20 --warmup 5 > gpurun_out/${T}_bench_c2.json 2>> gpurun_out/${T}_bench.err || exit 1
-timeout -k 10 300 python bench.py --input host --steps 20 --warmup 5 --cpu-frames 0 > gpurun_out/${T}_bench_host.json 2>> gpurun_out/${T}_bench.err || exit 1
+OUT=${OUT:-bench_out}                # where the bench lines go
+mkdir -p $OUT
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --assoc mcf --steps 10 --warmup 2 > $OUT/${T}_bench_mcf.json 2>> $OUT/${T}_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --workload c4 --steps 5 --warmup 2 > $OUT/${T}_bench_c4.json 2>> $OUT/${T}_bench.err || exit 1
+timeout -k 10 400 python bench.py --full --workload c5 --steps 5 --warmup 2 > $OUT/${T}_bench_c5.json 2>> $OUT/${T}_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --workload c2 --steps 20 --warmup 5 > $OUT/${T}_bench_c2.json 2>> $OUT/${T}_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --input host --steps 20 --warmup 5 --cpu-frames 0 > $OUT/${T}_bench_host.json 2>> $OUT/${T}_bench.err || exit 1
 for w in assoc-c3 assoc-c4; do for a in mcf hungarian; do
-  timeout -k 10 300 python bench.py --workload $w --assoc $a --steps 5 --warmup 2 > gpurun_out/${T}_bench_${w}_${a}.json 2>> gpurun_out/${T}_bench.err || exit 1
+  timeout -k 10 300 python bench.py --full --workload $w --assoc $a --steps 5 --warmup 2 > $OUT/${T}_bench_${w}_${a}.json 2>> $OUT/${T}_bench.err || exit 1
 done; done
-timeout -k 10 300 python bench.py --gpus 2 --backend gloo --single-device --assoc mcf --frames 132 --steps 3 --warmup 1 --no-verify > gpurun_out/${T}_bench_2ranks_mcf.json 2>> gpurun_out/${T}_bench.err || exit 1
-timeout -k 10 400 python bench.py --gpus 2 --backend gloo --single-device --workload c4 --steps 2 --warmup 1 --cpu-frames 0 > gpurun_out/${T}_bench_2ranks_c4.json 2>> gpurun_out/${T}_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --single-device --assoc mcf --frames 132 --steps 3 --warmup 1 --no-verify > $OUT/${T}_bench_2ranks_mcf.json 2>> $OUT/${T}_bench.err || exit 1
+timeout -k 10 400 python bench.py --full --gpus 2 --backend gloo --single-device --workload c4 --steps 2 --warmup 1 --cpu-frames 0 > $OUT/${T}_bench_2ranks_c4.json 2>> $OUT/${T}_bench.err || exit 1

@@ -204,3 +204,63 @@ def test_round_4_lines_c4_c5_certificate_steady_state_and_matching_counters():
     assert 'EXTRAPOLATED' in json.load(open(os.path.join(ROOT, 'profiles', 'r04j_bench_c5.json')))['cpu_baseline']['sample']
     two = json.load(open(os.path.join(ROOT, 'profiles', 'r04j_bench_2ranks_c4.json')))
     assert two['n_gpus'] == 2 and two['tracks_identical_on_all_ranks'] is True and two['verify']['flow_certificate']['ok'] is True
+
+
+class _FakeDetections:
+    """What dump_outputs reads of an AxonDetections: _host_dets(), _track_flat, IDed_dets_all."""
+    def __init__(self, F=40, cap=64, n_ids=30, seed=3):
+        import pandas as pd
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        self.cnt = rng.integers(0, cap, F).astype(np.int32)
+        self.conf = rng.random((F, cap), dtype=np.float32)
+        self.x, self.y = (rng.integers(0, 512, (F, cap)).astype(np.int32) for _ in range(2))
+        self._track_flat = rng.integers(-1, n_ids, int(self.cnt.sum())).astype(np.int32)
+        vals = rng.random((n_ids, 3 * F))
+        vals[vals < 0.3] = np.nan
+        self.IDed_dets_all = pd.DataFrame(vals)
+
+    def _host_dets(self):
+        return self.cnt, self.conf, self.x, self.y
+
+
+def test_dump_outputs_writes_float_arrays_of_what_the_step_returned(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files holding the detection lists, trajectory ids and IDed_dets_all of the
+    last step; past the size limit every array keeps the same seeded sample of rows, and the row indices go beside it."""
+    import numpy as np
+    b = _bench_module()
+    ad = _FakeDetections()
+    b.dump_outputs(str(tmp_path / 'all'), ad, True)
+    got = {f[:-4]: np.load(tmp_path / 'all' / f) for f in os.listdir(tmp_path / 'all')}
+    assert set(got) == {'det_count', 'det_conf', 'det_x', 'det_y', 'track', 'ided_dets_all', 'ided_dets_all_present'}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    valid = np.arange(ad.conf.shape[1])[None, :] < ad.cnt[:, None]
+    assert np.array_equal(got['det_count'], ad.cnt) and np.array_equal(got['det_conf'], ad.conf[valid])
+    assert np.array_equal(got['det_x'], ad.x[valid]) and np.array_equal(got['det_y'], ad.y[valid])
+    assert np.array_equal(got['track'], ad._track_flat)
+    ided = ad.IDed_dets_all.to_numpy()
+    assert np.isnan(ided).any() and np.array_equal(got['ided_dets_all_present'], ~np.isnan(ided))
+    assert np.array_equal(np.where(got['ided_dets_all_present'] == 1, got['ided_dets_all'], np.nan), ided, equal_nan=True)
+    b.dump_outputs(str(tmp_path / 'dets'), ad, False)
+    assert sorted(os.listdir(tmp_path / 'dets')) == ['det_conf.npy', 'det_count.npy', 'det_x.npy', 'det_y.npy']
+    # over the limit: a seeded sample, the same on every call, within the limit
+    monkeypatch.setattr(b, 'DUMP_LIMIT_BYTES', 20000)
+    for run in ('s1', 's2'):
+        b.dump_outputs(str(tmp_path / run), ad, True)
+    names = sorted(os.listdir(tmp_path / 's1'))
+    assert names == sorted(os.listdir(tmp_path / 's2')) and 'track_rows.npy' in names and 'ided_dets_all_rows.npy' in names
+    assert sum(os.path.getsize(tmp_path / 's1' / f) - 128 for f in names) <= 20000
+    for f in names:
+        a = np.load(tmp_path / 's1' / f)
+        assert np.isfinite(a).all() and np.array_equal(a, np.load(tmp_path / 's2' / f)), f
+    rows = np.load(tmp_path / 's1' / 'track_rows.npy').astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 's1' / 'det_x_rows.npy'), rows)          # one length, one sample
+    assert np.array_equal(np.load(tmp_path / 's1' / 'track.npy'), ad._track_flat[rows])
+    ided_rows = np.load(tmp_path / 's1' / 'ided_dets_all_rows.npy').astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 's1' / 'ided_dets_all.npy'), np.nan_to_num(ided[ided_rows], nan=0.0))
+    assert np.array_equal(np.load(tmp_path / 's1' / 'ided_dets_all_present_rows.npy'), ided_rows)
+
+
+def test_full_and_dump_outputs_are_options_of_the_benchmark():
+    r = _bench('--help')
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout

@@ -1863,7 +1863,7 @@ def test_bare_multi_gpu_bench_invocation_runs_two_ranks_on_this_gpu():
     root = os.path.join(os.path.dirname(__file__), '..')
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--single-device',
-                        '--frames', '36', '--steps', '2', '--warmup', '1', '--no-verify'], env=env, stdout=subprocess.PIPE,
+                        '--frames', '36', '--steps', '2', '--warmup', '1', '--full', '--no-verify'], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1884,7 +1884,7 @@ def test_bench_workloads_c4_and_c5_one_share_and_two_ranks_on_this_gpu(wl):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['AXT_MCF_MIN_LEAF'] = '256'                      # small time blocks, so that the shared solve has leaves to share
     def run(*argv):
-        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', wl, '--steps', '1', '--warmup', '1', *argv],
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', wl, '--steps', '1', '--warmup', '1', '--full', *argv],
                            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1946,7 +1946,7 @@ def test_bench_lines_of_the_other_workloads_run_and_verify():
     root = os.path.join(os.path.dirname(__file__), '..')
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     def run(*argv):
-        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), *argv], env=env, stdout=subprocess.PIPE,
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', *argv], env=env, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1958,6 +1958,35 @@ def test_bench_lines_of_the_other_workloads_run_and_verify():
         a = run('--workload', 'assoc-c3', '--assoc', assoc, '--steps', '2', '--warmup', '1')
         assert a['verified'] is True and a['config']['input'] == 'detections_hbm_resident' and a['roofline']['bound'] == 'hbm'
         assert a['n_ids'] > 20 and a['value'] > 0 and a['unit'] == 'frames/s'
+
+
+def test_plain_bench_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `python bench.py --steps K --warmup W` times K steps and prints the headline only (what --full adds stays out);
+    --dump-outputs writes what the last timed step computed, and two runs with the same arguments write the same arrays."""
+    import json, subprocess, sys
+    root = os.path.join(os.path.dirname(__file__), '..')
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    lines = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--frames', '24', '--steps', '3', '--warmup', '1',
+                            '--dump-outputs', str(tmp_path / run)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    b = lines[0]
+    assert b['steps'] == 3 and b['warmup'] == 1 and b['unit'] == 'frames/s' and b['higher_is_better'] is True and b['dtype'] == 'f32'
+    assert abs(b['value'] - 20 * 1e3 / b['ms_per_step']) / b['value'] < 1e-2 and 'detect+associate' in b['metric']
+    for k in ('roofline', 'cpu_baseline', 'verified', 'stages', 'other_association_variant', 'host_input_variant'):
+        assert k not in b, k
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['det_conf.npy', 'det_count.npy', 'det_x.npy', 'det_y.npy', 'ided_dets_all.npy', 'ided_dets_all_present.npy', 'track.npy']
+    assert names == sorted(os.listdir(tmp_path / 'b'))
+    for f in names:
+        a, c = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, c), f
+    assert int(np.load(tmp_path / 'a' / 'det_count.npy').sum()) == b['detections'] > 0
+    assert np.load(tmp_path / 'a' / 'ided_dets_all.npy').shape == (b['n_ids'], 3 * 20)
 
 
 def test_the_references_example_sequence_with_only_the_import_changed(tmp_path, monkeypatch, weights):
