@@ -81,6 +81,11 @@ SIGNATURES = {
     'axt_detection_confusion': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'axt_arc_cost_int': (c_int64, [c_double, c_int, c_int64, c_int64]),
+    'axt_track_links': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    'axt_link_paths': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                               c_int, c_void_p, c_void_p, c_void_p]),
+    'axt_link_cells': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               ctypes.POINTER(c_int64), c_void_p]),
 }
 
 _lib = None

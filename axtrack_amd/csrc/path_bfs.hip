@@ -43,9 +43,10 @@ __global__ __launch_bounds__(256) void path_sssp_kernel(
     const int *__restrict__ xa, const int *__restrict__ ya, int na,
     const int *__restrict__ xb, const int *__restrict__ yb, int nb,
     const unsigned char *__restrict__ mask, int H, int W, int max_dist, int conn8, long win_cells_cap,
-    Scratch sc, int *__restrict__ D)
+    Scratch sc, int *__restrict__ D, int paired)
 {
     const int src = blockIdx.x, tid = threadIdx.x;
+    if (paired) { xb += src; yb += src; }            // (source, target) pairs: nb == 1, the target of source src
     int *Drow = D + (long)src * nb;
     const int sx = xa[src], sy = ya[src];
     const bool src_in = sx >= 0 && sx < W && sy >= 0 && sy < H;
@@ -124,10 +125,11 @@ __global__ __launch_bounds__(256) void path_sssp_kernel(
 __global__ __launch_bounds__(64) void path_backtrack_kernel(
     const int *__restrict__ xb, const int *__restrict__ yb, int nb, const unsigned char *__restrict__ mask, int H, int W,
     int max_dist, int conn8, long win_cells_cap, const u64 *__restrict__ key_base, const int *__restrict__ D,
-    int *__restrict__ cells)
+    int *__restrict__ cells, int paired)
 {
     const int src = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
     if (j >= nb) return;
+    if (paired) { xb += src; yb += src; }
     const int d = D[(long)src * nb + j];
     if (d >= max_dist) return;
     const u64 *key = key_base + (long)src * win_cells_cap;
@@ -157,10 +159,13 @@ __global__ __launch_bounds__(64) void path_backtrack_kernel(
 
 }  // namespace
 
-int axt_path_cost_masked(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_t *d_xb, const int32_t *d_yb,
-                         int nb, const uint8_t *d_mask, int H, int W, int max_dist, int conn8, int32_t *d_D,
-                         hipStream_t st, int32_t *d_cells)
+// paired == 0: every source against every target (D [na, nb], cells [na, nb, max_dist]); paired != 0: source k against
+// target k only (nb == na; D [na], cells [na, max_dist])
+static int path_cost_masked_impl(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_t *d_xb, const int32_t *d_yb,
+                                 int nb, const uint8_t *d_mask, int H, int W, int max_dist, int conn8, int32_t *d_D,
+                                 hipStream_t st, int32_t *d_cells, int paired)
 {
+    const int nbk = paired ? 1 : nb;                  // targets per source
     const long win = (long)H * W;
     // sources are processed in batches so that the HBM scratch (24 bytes per window cell and source) stays bounded
     const long bytes_per_src = win * (8 + 4 + 4 + 4);
@@ -176,17 +181,36 @@ int axt_path_cost_masked(const int32_t *d_xa, const int32_t *d_ya, int na, const
     sc.list_b = sc.list_a + batch * win;
     for (long s0 = 0; s0 < na; s0 += batch) {
         const int n = (int)((na - s0 < batch) ? na - s0 : batch);
-        hipLaunchKernelGGL(path_sssp_kernel, dim3(n), dim3(256), 0, st, d_xa + s0, d_ya + s0, n, d_xb, d_yb, nb, d_mask, H,
-                           W, max_dist, conn8, win, sc, d_D + s0 * nb);
+        const int32_t *xb = paired ? d_xb + s0 : d_xb, *yb = paired ? d_yb + s0 : d_yb;
+        hipLaunchKernelGGL(path_sssp_kernel, dim3(n), dim3(256), 0, st, d_xa + s0, d_ya + s0, n, xb, yb, nbk, d_mask, H,
+                           W, max_dist, conn8, win, sc, d_D + s0 * nbk, paired);
         AXT_LAUNCH_CHECK();
         if (d_cells) {
-            hipLaunchKernelGGL(path_backtrack_kernel, dim3((nb + 63) / 64, n), dim3(64), 0, st, d_xb, d_yb, nb, d_mask, H, W,
-                               max_dist, conn8, win, (const u64 *)sc.key, (const int *)(d_D + s0 * nb), d_cells + s0 * nb * max_dist);
+            hipLaunchKernelGGL(path_backtrack_kernel, dim3((nbk + 63) / 64, n), dim3(64), 0, st, xb, yb, nbk, d_mask, H, W,
+                               max_dist, conn8, win, (const u64 *)sc.key, (const int *)(d_D + s0 * nbk), d_cells + s0 * nbk * max_dist,
+                               paired);
             AXT_LAUNCH_CHECK();
         }
     }
     AXT_CHECK_HIP(hipFreeAsync(raw, st));
     return AXT_OK;
+}
+
+int axt_path_cost_masked(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_t *d_xb, const int32_t *d_yb,
+                         int nb, const uint8_t *d_mask, int H, int W, int max_dist, int conn8, int32_t *d_D,
+                         hipStream_t st, int32_t *d_cells)
+{
+    return path_cost_masked_impl(d_xa, d_ya, na, d_xb, d_yb, nb, d_mask, H, W, max_dist, conn8, d_D, st, d_cells, 0);
+}
+
+// The same exact search and walk-back for a list of (source, target) pairs instead of the cross product (recon.hip's
+// fallback): D i32 [n], cells i32 [n, max_dist] (rows of pairs without a path are left alone).
+int axt_path_cells_pairs(const int32_t *d_xa, const int32_t *d_ya, const int32_t *d_xb, const int32_t *d_yb, int n,
+                         const uint8_t *d_mask, int H, int W, int max_dist, int conn8, int32_t *d_D, int32_t *d_cells,
+                         hipStream_t st)
+{
+    if (n <= 0) return AXT_OK;
+    return path_cost_masked_impl(d_xa, d_ya, n, d_xb, d_yb, n, d_mask, H, W, max_dist, conn8, d_D, st, d_cells, 1);
 }
 
 // =====================================================================================================================
@@ -837,6 +861,13 @@ extern "C" void axt_grid_destroy(axt_grid *g)
 }
 
 extern "C" const uint8_t *axt_grid_mask(const axt_grid *g) { return g ? g->d_mask : nullptr; }
+const int32_t *axt_grid_label(const axt_grid *g) { return g ? g->d_label : nullptr; }
+// the component fields d_off [n_comp][H][W] (NULL when the mask has none)
+const uint8_t *axt_grid_off_field(const axt_grid *g, int *n_comp)
+{
+    *n_comp = g ? g->n_comp : 0;
+    return g ? g->d_off : nullptr;
+}
 
 // Fills Dtmp (layout above) for every source detection; exact-search fallback included. Synchronises the stream.
 int axt_masked_distance_table(const axt_grid *g, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,

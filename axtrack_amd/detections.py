@@ -421,6 +421,7 @@ class AxonDetections(object):
         '{name}_astar_dets_paths.pkl' (the reference's format: per frame pair a nested list of coo matrices / None)
         instead of computing them; 'to' writes such a file (astar_dets_paths)."""
         self._len_table = _len_table
+        self._recon = None                                  # the reconstructions belong to one association
         if assigedIDs_cache != 'from':
             if astar_paths_cache == 'from':
                 self._len_table = self._length_table_from_paths(self.from_cache('astar_dets_paths'))
@@ -955,6 +956,92 @@ class AxonDetections(object):
         wait()
         return df
 
+    # ------------------------------------------------------------------ axon reconstructions (AxonDetections.py:924-934)
+    def reconstruction_arrays(self, interpolate_missing=True):
+        """The axon reconstructions as numpy arrays (the low-level accessor beside ided_arrays()). Per link -- a detection
+        and the next detection of its identity within MCF_MAX_NUM_MISSES + 1 frames, in ascending tail order:
+        'tail_frame', 'tail_slot', 'head_frame', 'head_slot', 'axon_id', 'gap', 'len' (cells of the link's minimum-cost
+        path; max_px_assoc_dist = no path), 'cell_ptr' [n_links+1] and 'cells' (y*W + x along the path, source first: the
+        cells astar_dets_paths() holds for that pair). Per interpolated frame (the frames a gap link skips; none with
+        interpolate_missing=False): 'interp_axon_id', 'interp_frame', 'interp_x', 'interp_y', 'interp_link' and
+        'interp_index' (position along the link's path, _interp_index). The GPU work (hotpath.track_links +
+        hotpath.link_paths) runs once per assign_ids() and is cached."""
+        if getattr(self, '_shard', None) is not None:
+            raise NotImplementedError('axon reconstructions of a frame-sharded run are not implemented: reconstruct in a '
+                                      'single process (AxonDetections without gather_detections)')
+        if not getattr(self, '_solved', False):
+            raise ValueError('no identities: run assign_ids() first (or the association was infeasible)')
+        if getattr(self, '_recon', None) is None:
+            self._recon = self._trace_links()
+        r = dict(self._recon)
+        if not interpolate_missing:
+            for k in ('interp_axon_id', 'interp_frame', 'interp_x', 'interp_y', 'interp_link', 'interp_index'):
+                r[k] = r[k][:0]
+        return r
+
+    def _trace_links(self):
+        max_gap = self.P['MCF_MAX_NUM_MISSES'] + 1
+        track = self._track_dev()
+        F, cap = track.shape
+        H, W = self.dataset.sizey, self.dataset.sizex
+        links = hp.track_links(track, self.d_count, max_gap)
+        if self.dataset.mask3d is not None:
+            grids, index = self._mask_grids()           # the mask _masked_dets_paths searches the pair ending in t on
+            head_group = torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(self.device)
+        else:
+            grids, head_group = [self._mask_dev()], None
+        length, cell_ptr, cells, interp = hp.link_paths(links, self.d_x, self.d_y, H, W, grids, head_group,
+                                                        self.max_px_assoc_dist, self.conn8, max_gap)
+        links_h, len_h, ptr_h, cells_h, interp_h, track_h = (a.copy() for a in hp.to_host(links, length, cell_ptr, cells,
+                                                                                            interp, track))
+        tail, head, gap = (links_h[:, k].astype(np.int64) for k in range(3))
+        out = dict(tail_frame=tail // cap, tail_slot=tail % cap, head_frame=head // cap, head_slot=head % cap,
+                   axon_id=track_h.reshape(-1)[tail].astype(np.int64), gap=gap, len=len_h.astype(np.int64),
+                   cell_ptr=ptr_h.astype(np.int64), cells=cells_h.astype(np.int64), max_dist=self.max_px_assoc_dist,
+                   shape=(H, W))
+        li, kk = np.nonzero(interp_h >= 0) if interp_h.size else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+        c = interp_h[li, kk].astype(np.int64)
+        k = kk.astype(np.int64) + 1
+        out.update(interp_axon_id=out['axon_id'][li], interp_frame=out['tail_frame'][li] + k, interp_x=c % W,
+                   interp_y=c // W, interp_link=li.astype(np.int64), interp_index=_interp_index(k, out['len'][li], gap[li]))
+        return out
+
+    def get_axon_reconstructions(self, t=None, axon_name=None, include_history=True, interpolate_missing=True, ymin=0,
+                                 ymax=0, xmin=0, xmax=0):
+        """The paths the tracked growth cones took (the reference's stub, AxonDetections.py:930-934, in the format its
+        caller reads, video_plotting.py:164-168,301-304): a DataFrame with columns (axonID, coord in {'X', 'Y'}, frameID)
+        and one row per position along a segment (float, NaN-padded). The segment of frame t of an axon is the
+        minimum-cost path from its previous position -- detected, or interpolated with interpolate_missing -- to its
+        position at t, both ends included (consecutive segments share a cell); an axon's first frame has none. Without
+        interpolate_missing a link across missed frames is one segment, keyed by its head frame; a link without a path
+        (farther than max_px_assoc_dist) has none.
+        t: None = every frame; include_history: the segments of frames <= t (else == t only). axon_name: a name
+        ('Axon_007') or a list of names. Cells outside [ymin, ymax) x [xmin, xmax) are NaN and coordinates are shifted
+        by (xmin, ymin), as the caller shifts its anchors; a max of 0 means the frame edge.
+        frameID is the detection frame's true position: it does NOT carry the frame-label quirk of IDed_dets_all's
+        columns (REPRODUCE_FRAME_LABEL_QUIRK)."""
+        r = self.reconstruction_arrays(interpolate_missing)
+        seg = _recon_segments(r, interpolate_missing)
+        names = None if axon_name is None else ([axon_name] if isinstance(axon_name, str) else list(axon_name))
+        return _recon_frame(seg, r['cells'], r['shape'], t, names, include_history, ymin, ymax, xmin, xmax)
+
+    def _reconstruct_axons(self):
+        """AxonDetections.py:924-928: the reconstructions of the whole timelapse."""
+        return self.get_axon_reconstructions()
+
+    def get_axon_growth(self, interpolate_missing=True):
+        """Per axon and frame where it has a detected or interpolated position, indexed by (axonID, frameID): anchor_x,
+        anchor_y, conf (NaN where interpolated), interpolated, step_px (moves of the segment ending here -- a diagonal
+        move counts 1, as in the tracker's path lengths; 0 at the axon's first frame, NaN where the link has no path),
+        length_px (cumulative; NaN from the first unknown step on), and with the timelapse's pixelsize length_um, with
+        pixelsize and dt (minutes per frame) speed_um_per_min = step over dt x the frames the step spans. frameID as in
+        get_axon_reconstructions (no label quirk)."""
+        r = self.reconstruction_arrays(interpolate_missing)
+        seg = _recon_segments(r, interpolate_missing)
+        frame, ids, conf, x, y = self.ided_arrays()
+        return _growth_table(frame, ids, conf, x, y, r, seg, getattr(self.dataset, 'pixelsize', None),
+                             getattr(self.dataset, 'dt', None))
+
     def _track_dev(self):
         """Trajectory id of every detection slot on the device, i32 [F,cap] (-1: none)."""
         t = getattr(self, '_d_track', None)
@@ -1022,6 +1109,117 @@ def _axon_number(name):
 def _axon_index(ids):
     names = [_AXON_NAMES[i] if i < 2048 else f'Axon_{i:0>3}' for i in ids]
     return pd.Index(names, name='axonID')
+
+
+def _interp_index(k, L, g):
+    """Cell index along a link's path of L cells at which the k-th of the g-1 frames a gap-g link skips is placed:
+    round(k (L-1) / g), halves up -- the same rule as axt_link_cells."""
+    k, L, g = (np.asarray(v, np.int64) for v in (k, L, g))
+    return (2 * k * (L - 1) + g) // (2 * g)
+
+
+def _recon_segments(r, interpolate_missing):
+    """reconstruction_arrays() -> the segments, sorted by (axon, frame): dict of arrays axon, frame (where the segment
+    ends), start (into r['cells']), n (cells; 0 = the link has no path), step (moves, NaN without a path), span (frames
+    the segment covers), interp_end (the segment ends at an interpolated position)."""
+    L, g, ptr = r['len'], r['gap'], r['cell_ptr'][:-1]
+    has = (L > 0) & (L < r['max_dist'])
+    split = has & (g >= 2) if interpolate_missing else np.zeros(len(L), bool)
+    whole = ~split
+    parts = [dict(axon=r['axon_id'][whole], frame=r['head_frame'][whole], start=ptr[whole], n=np.where(has, L, 0)[whole],
+                  step=np.where(has, L - 1, np.nan)[whole], span=g[whole].astype(np.float64),
+                  interp_end=np.zeros(int(whole.sum()), bool))]
+    for k in range(1, int(g.max()) + 1 if len(g) else 1):
+        sel = split & (g >= k)
+        Ls, gs = L[sel], g[sel]
+        a = _interp_index(k - 1, Ls, gs)
+        b = np.where(k == gs, Ls - 1, _interp_index(k, Ls, gs))
+        parts.append(dict(axon=r['axon_id'][sel], frame=r['tail_frame'][sel] + k, start=ptr[sel] + a, n=b - a + 1,
+                          step=(b - a).astype(np.float64), span=np.ones(len(Ls)), interp_end=k < gs))
+    seg = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+    order = np.lexsort((seg['frame'], seg['axon']))
+    return {key: v[order] for key, v in seg.items()}
+
+
+def _recon_frame(seg, cells, shape, t, names, include_history, ymin, ymax, xmin, xmax):
+    """The DataFrame of get_axon_reconstructions from the segments (host only)."""
+    H, W = shape
+    keep = seg['n'] > 0
+    if t is not None:
+        keep &= (seg['frame'] <= t) if include_history else (seg['frame'] == t)
+    axon_names = np.array([f'Axon_{int(i):0>3}' for i in seg['axon']], dtype=object)
+    if names is not None:
+        keep &= np.isin(axon_names, np.asarray(names, dtype=object))
+    axon, frame, start, n, axon_names = seg['axon'][keep], seg['frame'][keep], seg['start'][keep], seg['n'][keep], axon_names[keep]
+    cols_names = ('axonID', 'coord', 'frameID')
+    if len(n) == 0:
+        return pd.DataFrame([], columns=pd.MultiIndex.from_arrays([[], [], []], names=cols_names), dtype=np.float64)
+    nseg = len(n)
+    # columns: per axon (in ascending id) its X columns (ascending frame), then its Y columns
+    first = np.r_[True, axon[1:] != axon[:-1]]
+    grp = np.cumsum(first) - 1
+    g_start = np.nonzero(first)[0]
+    g_count = np.diff(np.r_[g_start, nseg])
+    xcol = 2 * g_start[grp] + (np.arange(nseg) - g_start[grp])
+    ycol = xcol + g_count[grp]
+    offs = np.r_[0, np.cumsum(n)]
+    segi = np.repeat(np.arange(nseg), n)
+    rows = np.arange(offs[-1]) - offs[segi]
+    c = cells[start[segi] + rows]
+    X, Y = (c % W).astype(np.float64), (c // W).astype(np.float64)
+    ymax, xmax = (ymax or H), (xmax or W)
+    out = (Y < ymin) | (Y >= ymax) | (X < xmin) | (X >= xmax)
+    X[out], Y[out] = np.nan, np.nan
+    arr = np.full((int(n.max()), 2 * nseg), np.nan)
+    arr[rows, xcol[segi]] = X - xmin
+    arr[rows, ycol[segi]] = Y - ymin
+    col_axon = np.empty(2 * nseg, dtype=object)
+    col_coord = np.empty(2 * nseg, dtype=object)
+    col_frame = np.empty(2 * nseg, np.int64)
+    col_axon[xcol], col_axon[ycol] = axon_names, axon_names
+    col_coord[xcol], col_coord[ycol] = 'X', 'Y'
+    col_frame[xcol], col_frame[ycol] = frame, frame
+    columns = pd.MultiIndex.from_arrays([col_axon, col_coord, col_frame], names=cols_names)
+    return pd.DataFrame(arr, columns=columns, copy=False)
+
+
+def _growth_table(frame, ids, conf, x, y, r, seg, pixelsize, dt):
+    """The DataFrame of get_axon_growth from the IDed detections and the segments (host only)."""
+    ni = len(r['interp_frame'])
+    a = np.concatenate([np.asarray(ids, np.int64), r['interp_axon_id']])
+    f = np.concatenate([np.asarray(frame, np.int64), r['interp_frame']])
+    ax = np.concatenate([np.asarray(x, np.float64), r['interp_x'].astype(np.float64)])
+    ay = np.concatenate([np.asarray(y, np.float64), r['interp_y'].astype(np.float64)])
+    cf = np.concatenate([np.asarray(conf, np.float64), np.full(ni, np.nan)])
+    interp = np.r_[np.zeros(len(frame), bool), np.ones(ni, bool)]
+    order = np.lexsort((f, a))
+    a, f, ax, ay, cf, interp = a[order], f[order], ax[order], ay[order], cf[order], interp[order]
+    n = len(a)
+    first = np.r_[True, a[1:] != a[:-1]] if n else np.zeros(0, bool)
+    # step / span of the segment that ends at (axon, frame)
+    step, span = np.full(n, np.nan), np.full(n, np.nan)
+    if n and len(seg['axon']):
+        key_rows = a * (int(f.max()) + 2) + f
+        key_seg = seg['axon'] * (int(f.max()) + 2) + seg['frame']
+        pos = np.searchsorted(key_rows, key_seg)                     # (rows are sorted by (axon, frame): keys ascend)
+        ok = (pos < n) & (key_rows[np.minimum(pos, n - 1)] == key_seg)
+        step[pos[ok]], span[pos[ok]] = seg['step'][ok], seg['span'][ok]
+    step[first] = 0.0
+    # cumulative per axon; NaN from the first unknown step on
+    grp = np.cumsum(first) - 1
+    cs = np.cumsum(np.nan_to_num(step))
+    base = (cs - np.nan_to_num(step))[first][grp] if n else cs
+    unknown = np.cumsum(np.isnan(step))
+    unknown_before = (unknown - np.isnan(step))[first][grp] if n else unknown
+    length = np.where(unknown - unknown_before > 0, np.nan, cs - base)
+    data = {'anchor_x': ax, 'anchor_y': ay, 'conf': cf, 'interpolated': interp, 'step_px': step, 'length_px': length}
+    if pixelsize is not None:
+        data['length_um'] = length * float(pixelsize)
+        if dt is not None:
+            data['speed_um_per_min'] = step * float(pixelsize) / (float(dt) * span)
+    index = pd.MultiIndex.from_arrays([np.array([f'Axon_{int(i):0>3}' for i in a], dtype=object), f],
+                                      names=('axonID', 'frameID'))
+    return pd.DataFrame(data, index=index)
 
 
 def _splitmix64(x):

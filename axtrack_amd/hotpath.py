@@ -463,6 +463,50 @@ def ided_table(track, conf, x, y, count, n_ids, label_quirk=True, id_row=None, n
     return host.numpy(), torch.cuda.current_stream(dev).synchronize       # ... and calls this before handing it on
 
 
+def track_links(track, count, max_gap):
+    """The links of the tracks (what the reference's unbuilt _reconstruct_axons starts from, AxonDetections.py:924-934):
+    track i32 [F, cap] (-1 = none) -> i32 device tensor [n_links, 3] of (tail slot f*cap+i, head slot, gap), the head
+    being the first detection of the same id within max_gap frames, in ascending tail order (axt_track_links)."""
+    n_frames, cap = track.shape
+    dev = track.device
+    links = torch.empty((max(n_frames * cap, 1), 3), dtype=torch.int32, device=dev)
+    work = torch.empty((2 * n_frames * cap + 2 * n_frames + 1,), dtype=torch.int32, device=dev)
+    n = ctypes.c_int64(0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().axt_track_links(track.data_ptr(), count.data_ptr(), n_frames, cap, int(max_gap), links.data_ptr(),
+                                               work.data_ptr(), ctypes.byref(n), _stream()), 'axt_track_links')
+    return links[:int(n.value)]
+
+
+def link_paths(links, x, y, H, W, grids, head_group=None, max_dist=MAX_PX_ASSOC_DIST, conn8=False, max_gap=2):
+    """One minimum-cost path per link (axt_link_paths + axt_link_cells): the cells path_cells (masked grid) or the
+    closed-form staircase of astar_dets_paths (all-ones mask) gives for that pair. grids: list of Grid / None (all ones),
+    one per distinct mask; head_group: None (one grid) or i32 [F] device tensor, the grid of the links that end in frame f.
+    Returns device tensors (len i32 [n] (max_dist = no path), cell_ptr i64 [n+1], cells i32 y*W+x, source first,
+    interp i32 [n, max_gap-1]: the cell of the interpolated anchor of frame tail+k, -1 where there is none)."""
+    n = int(links.shape[0])
+    dev = x.device
+    lib = _lib.load()
+    length = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev)
+    stage = torch.empty((max(n, 1), int(max_dist)), dtype=torch.int32, device=dev)
+    cell_ptr = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    interp = torch.empty((max(n, 1), max(int(max_gap) - 1, 1)), dtype=torch.int32, device=dev)
+    total = ctypes.c_int64(0)
+    cap = int(x.shape[1])
+    with torch.cuda.device(dev):
+        for g, grid in enumerate(grids):
+            _lib.check(lib.axt_link_paths(grid._h if grid is not None else None, x.data_ptr(), y.data_ptr(), cap,
+                                          links.data_ptr(), n, _lib.dptr(head_group), g, int(H), int(W), int(max_dist),
+                                          int(bool(conn8)), length.data_ptr(), stage.data_ptr(), _stream()), 'axt_link_paths')
+        _lib.check(lib.axt_link_cells(links.data_ptr(), n, length.data_ptr(), stage.data_ptr(), int(max_dist), int(max_gap),
+                                      cell_ptr.data_ptr(), None, None, ctypes.byref(total), _stream()), 'axt_link_cells(count)')
+        cells = torch.empty((max(int(total.value), 1),), dtype=torch.int32, device=dev)
+        _lib.check(lib.axt_link_cells(links.data_ptr(), n, length.data_ptr(), stage.data_ptr(), int(max_dist), int(max_gap),
+                                      cell_ptr.data_ptr(), cells.data_ptr(), interp.data_ptr(), ctypes.byref(total),
+                                      _stream()), 'axt_link_cells(fill)')
+    return length[:n], cell_ptr, cells[:int(total.value)], interp[:n, :int(max_gap) - 1]
+
+
 def detection_confusion(conf, x, y, count, gx, gy, gcount, thrs, min_dist=23, k_mask=-1):
     """compute_TP_FP_FN (AxonDetections.py:409-466) for all frames and thresholds at once: i32 [F,3,n_thr] on the
     device (TP, FP, FN); with k_mask >= 0 also (fp_mask u8 [F,cap], fn_mask u8 [F,gcap]) for that threshold."""

@@ -392,6 +392,36 @@ int axt_ided_table(const int32_t *d_track, const float *d_conf, const int32_t *d
                    int label_quirk, int32_t *d_work, double *d_table, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Axon reconstructions (AxonDetections._reconstruct_axons / get_axon_reconstructions, stubs at
+ * AxonDetections.py:924-934; read by video_plotting.py:164-168,301-304). recon.hip.
+ * ------------------------------------------------------------------------------------------ */
+/* The links of the tracks: for every detection slot (f, i) of d_track i32 [n_frames, cap] (-1 = none) with id k, the
+ * first detection of k in frames f+1 .. f+max_gap (max_gap = MCF_MAX_NUM_MISSES + 1). d_links i32 [n_frames*cap, 3]
+ * receives (tail slot f*cap+i, head slot, gap) of each link in ascending tail order (deterministic);
+ * d_work i32 [2*n_frames*cap + 2*n_frames + 1]; *n_links = number of links. Synchronises the stream. */
+int axt_track_links(const int32_t *d_track, const int32_t *d_count, int n_frames, int cap, int max_gap,
+                    int32_t *d_links, int32_t *d_work, int64_t *n_links, void *stream);
+
+/* One minimum-cost path per link (d_links as axt_track_links writes them; d_x / d_y i32 [n_frames, cap]): exactly the
+ * cells, in the same order, that the package returns for that pair -- grid == NULL: the closed-form staircase of
+ * AxonDetections.astar_dets_paths (4-connected: columns first, then rows; 8-connected: the diagonal first, then
+ * straight); with a grid: what axt_path_cells gives for that (source, target) pair (windowed searches in LDS, the exact
+ * search for what they cannot decide). Only the links whose HEAD frame f has d_head_group[f] == group (all links for
+ * d_head_group == NULL): one call per distinct mask of a time-varying mask. d_len i32 [n_links] (zeroed before the first
+ * call) receives the number of cells, max_dist = no path; d_stage i32 [n_links, max_dist] the cells y*W + x, source
+ * first. Reads back one count (links for the exact search) when grid != NULL. */
+int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const int32_t *d_y, int cap, const int32_t *d_links,
+                   int n_links, const int32_t *d_head_group, int group, int H, int W, int max_dist, int conn8,
+                   int32_t *d_len, int32_t *d_stage, void *stream);
+
+/* The paths of axt_link_paths as CSR. Phase 1 (d_cells == NULL): d_cell_ptr i64 [n_links+1] = prefix sum of the lengths
+ * (0 for no path), *n_cells = total (synchronises). Phase 2: d_cells i32 [n_cells] filled from d_stage, and
+ * d_interp i32 [n_links, max_gap-1]: for a link of gap g >= 2 with a path of L cells, entry k-1 (k = 1 .. g-1) = the
+ * cell at index (2k(L-1) + g) / (2g) of the path (the interpolated anchor of frame tail+k), -1 otherwise. */
+int axt_link_cells(const int32_t *d_links, int n_links, const int32_t *d_len, const int32_t *d_stage, int max_dist,
+                   int max_gap, int64_t *d_cell_ptr, int32_t *d_cells, int32_t *d_interp, int64_t *n_cells, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Detection metrics: compute_TP_FP_FN (AxonDetections.py:409-466) for every frame
  * and every confidence threshold. Detections as axt_decode_stitch_nms leaves them; labels d_gx, d_gy
  * i32 [n_frames, gcap], d_gcount i32 [n_frames]; d_thrs f64 [n_thr] on the device (the reference's
