@@ -2,7 +2,8 @@
 
 Drop-in for the reference's public API on that path (reference __init__.py:1-16):
 setup_inference, prepare_input_data, inference -> AxonDetections.IDed_dets_all; PKG_DIR, _compute_astar_path;
-visualize_inference exists and says that plotting is out of scope.
+visualize_inference exists and says that matplotlib / video plotting is out of scope; render_inference draws the
+annotated frames on the GPU and writes PNG frames or one animated PNG.
 The compute lives in csrc/libaxtrack_hip.so (C ABI: include/axtrack_hip.h); there is no CPU
 fallback -- importing works anywhere, running needs the GPU and the built library.
 """
@@ -10,7 +11,8 @@ from .interface import setup_inference, prepare_input_data, inference, visualize
 from .utils import _compute_astar_path
 from .detections import AxonDetections
 from .hotpath import Detector
+from .render import render_inference
 from .timelapse import Timelapse
 
 __all__ = ['setup_inference', 'prepare_input_data', 'inference', 'visualize_inference', 'PKG_DIR', 'DEPLOYED_MODEL_DIR',
-           '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse']
+           '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse', 'render_inference']

@@ -1042,6 +1042,22 @@ class AxonDetections(object):
         return _growth_table(frame, ids, conf, x, y, r, seg, getattr(self.dataset, 'pixelsize', None),
                              getattr(self.dataset, 'dt', None))
 
+    # ------------------------------------------------------------------ rendering (video_plotting.py:17-320)
+    def render_frames(self, which_dets='IDed', t_y_x_slice=(None, None, None), draw_grid=True, draw_scalebar=False,
+                      draw_axon_reconstructions=False, draw_true_dets=False, draw_brightened_bg=False, axon_subset=None,
+                      description='', annotate=True):
+        """The annotated frames video_plotting.draw_frame draws, as uint8 RGB on the timelapse's device: torch.uint8
+        [T', H', W', 3] for t_y_x_slice = ((tmin, tmax), (ymin, ymax), (xmin, xmax)), None = the whole axis (as draw_all
+        takes it). Drawn by one HIP kernel (axt_render_frames), bottom to top: the frame in red, the brightened background
+        (draw_brightened_bg), the tile grid (draw_grid), the trails of get_axon_reconstructions(t, include_history=True)
+        (draw_axon_reconstructions, 'IDed' only), the ground-truth outlines (draw_true_dets), the dashed boxes of
+        get_frame_dets(which_dets, t) in palette[n % 20], their labels 'Ax{n:03}' and the header (annotate), the scale bar
+        (draw_scalebar, needs the timelapse's pixelsize). axon_subset: names ('Axon_007') whose boxes, labels and trails
+        are drawn. The rules are in DESIGN.md 6.8b; a host-resident timelapse is made resident first."""
+        from .render import render_frames
+        return render_frames(self, which_dets, t_y_x_slice, draw_grid, draw_scalebar, draw_axon_reconstructions,
+                             draw_true_dets, draw_brightened_bg, axon_subset, description, annotate)
+
     def _track_dev(self):
         """Trajectory id of every detection slot on the device, i32 [F,cap] (-1: none)."""
         t = getattr(self, '_d_track', None)

@@ -530,6 +530,25 @@ def detection_confusion(conf, x, y, count, gx, gy, gcount, thrs, min_dist=23, k_
 _HOST_STAGING = {}
 
 
+def render_tile_size():
+    """Edge of the output tiles the render lists are binned by (axt_render_tile_size)."""
+    return int(_lib.load().axt_render_tile_size())
+
+
+def render_frames(frames, mask, mask_stride, ts, H, W, ymin, xmin, Ho, Wo, grid, bg, trail_ptr, trail, trail_col, prim_ptr,
+                  prims, tables):
+    """video_plotting.draw_frame / draw_detections of the output frames ts (axt_render_frames): u8 [len(ts), Ho, Wo, 3] on
+    the frames' device. frames: detection frame t at frames[t]; mask: u8 (None = all ones), frame t at mask + t * mask_stride
+    elements; the binned lists as axtrack_amd.render builds them."""
+    _require_gpu()
+    out = torch.empty((int(ts.numel()), Ho, Wo, 3), dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.load().axt_render_frames(
+        frames.data_ptr(), _lib.dptr(mask), int(mask_stride), ts.data_ptr(), int(ts.numel()), int(H), int(W), int(ymin),
+        int(xmin), int(Ho), int(Wo), int(grid), int(bool(bg)), trail_ptr.data_ptr(), trail.data_ptr(), trail_col.data_ptr(),
+        prim_ptr.data_ptr(), prims.data_ptr(), tables.data_ptr(), out.data_ptr(), _stream()), 'axt_render_frames')
+    return out
+
+
 def to_host(*tensors):
     """Device tensors -> numpy arrays through pinned staging buffers (kept per dtype and grown as needed): the arc list of a
     300 k-detection timelapse is 120 MB, which a pageable copy moves at a few GB/s and a pinned one at PCIe speed. The copies

@@ -436,6 +436,27 @@ int axt_detection_confusion(const float *d_conf, const int32_t *d_x, const int32
                             int gcap, const double *d_thrs, int n_thr, int min_dist, int k_mask,
                             int32_t *d_confusion, uint8_t *d_fp_mask, uint8_t *d_fn_mask, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rendering (video_plotting.py draw_all / setup_frame_drawing / draw_frame / draw_detections, which redraw every
+ * frame as matplotlib patches): annotated uint8 RGB frames, DESIGN.md 6.8b.
+ * axt_render_tile_size: edge of the square output tiles the primitive lists are binned by (64).
+ * axt_render_frames: d_out u8 [n_out, Ho, Wo, 3] = the slice [ymin, ymin+Ho) x [xmin, xmin+Wo) of the detection frames
+ * d_ts i32 [n_out] (ascending). d_frames: f32 [.., H, W], detection frame t at d_frames + t*H*W (the caller skips the
+ * context frames). Background (R8, 0, 0), R8 = rint(clamp(v, 0, 1) * 255); bg != 0: brightened with the weight map
+ * blurred over the whole frame and the mask of frame t (d_mask + t*mask_stride, u8; NULL = all ones); grid > 0: the
+ * lines x % grid == 0 or y % grid == 0 (frame coordinates) blended with white. Trails: d_trail i32 [n, 4] (frame,
+ * key, x, y in output coordinates; binned per output tile, d_trail_ptr i32 [n_tiles+1], sorted by frame within a
+ * tile): the cells with frame <= the output frame's, 5 x 5 squares, the largest key wins, colour
+ * palette[d_trail_col[key]]. Primitives: d_prims i32 [m, 8] (x0, y0, kind, a, b, key, 0, 0: kind 0 dashed box
+ * outline a x a, 1 solid ground-truth outline, 2 glyph a = char - 32 at scale b, 3 rectangle a x b) binned per
+ * (output frame, tile): d_prim_ptr i32 [n_out*n_tiles+1]; key = layer << 24 | (n + 1), the largest key wins, layer 3
+ * is grey (107). d_tables u8: palette [20, 3], then the glyph rows [95, 7]. Asynchronous. */
+int axt_render_tile_size(void);
+int axt_render_frames(const float *d_frames, const uint8_t *d_mask, int64_t mask_stride, const int32_t *d_ts, int n_out,
+                      int H, int W, int ymin, int xmin, int Ho, int Wo, int grid, int bg, const int32_t *d_trail_ptr,
+                      const int32_t *d_trail, const uint8_t *d_trail_col, const int32_t *d_prim_ptr,
+                      const int32_t *d_prims, const uint8_t *d_tables, uint8_t *d_out, void *stream);
+
 /* Integer arc cost used by the flow network (the costs libmot hands its solver at AxonDetections.py:663-690, from
  * observation_model / transition_model, mincostflow_models.py:6-27,67-119): round(cost * 1e6) << 16 | hash16(kind, a, b).
  * kind 0 entry, 1 exit, 2 observation, 3 transition. The low 16 bits make the optimum unique
