@@ -1456,6 +1456,7 @@ struct axt_detector {
     float *d_bfc[3] = {};
     float *d_act[8] = {};       // activations after conv block i (chunk-sized for i < 4)
     float *d_slab = nullptr, *d_fc1 = nullptr, *d_fc2 = nullptr;
+    bool act0_written = false;  // the last front launch ran the separate stride-2 kernels (the fused one never writes d_act[0]); axt_debug_cnn_activation
     float *d_pad = nullptr;     // frames re-pitched to a multiple of 4 floats per row (only for such timelapses)
     size_t pad_cap = 0;
     size_t bytes = 0;
@@ -1741,11 +1742,13 @@ int run_front_a(axt_detector *d, const float *frames, int Hf, int Wf, int t0, in
     if (d->fuse01 && Wf % 4 == 0) {
         // blocks 0 and 1 in one kernel (its 16-byte input pieces need aligned rows: other widths take the separate kernels)
         ProfSpan ps(d, st, 0, nb);
+        d->act0_written = false;
         if ((rc = axt_launch_conv_fused01(frames, d->d_wconv[0], d->d_bconv[0], d->d_wconv[1], d->d_bconv[1], d->d_act[1], nb, st,
                                       Hf, Wf, t0, tstep, item0, n_tiles, tl))) return rc;
     } else {
     {
         ProfSpan ps(d, st, 0, nb);
+        d->act0_written = true;
         const float *src = frames;
         int pitch = Wf, t_first = 0;
         if (Wf % 4 != 0) {
@@ -2132,6 +2135,45 @@ int axt_cnn_back(axt_detector *det, int n_items, float *d_yolo, void *stream)
 }
 
 }  // extern "C"
+
+// Test-only read-back of the buffers a forward pass leaves behind (not in include/axtrack_hip.h; tests/helpers.py binds it).
+// which 0..7: d_act[which], the output of conv block `which` after its pool where the block pools; 8, 9: d_fc1, d_fc2 after
+// the sigmoid. h_out receives n items from slot slot0 as dense [n, C, H, W] ([n, 1024] for 8 and 9). Every buffer is stored
+// as dense f32 NCHW / [items][1024] already (conv_epilogue, reduce_bias_act), so this is one copy and no conversion.
+// Synchronises the device first; nothing here is on the forward path.
+// Which item sits in which slot after a pass (forward_items, axt_cnn_front_frames, axt_cnn_back), items numbered as the
+// pass numbers them:
+//   buffers 4-9 hold the last group of max_batch items in order: item base + j in slot j (axt_cnn_front_frames: the
+//     call's item k in slot item0 + k of buffer 4; buffers 5-9 are written by axt_cnn_back for items 0..n_items-1);
+//   buffers 2-3 hold the last chunk_b group of that max_batch group: its item j in slot j;
+//   buffers 0-1 hold the last chunk_a group of that chunk_b group: its item j in slot j.
+// Slots past the last group's size keep whatever an earlier group or pass left there.
+// AXT_EINVAL: slot0 + n beyond the buffer (0-1: min(max_batch, chunk_a) items, 2-3: min(max_batch, chunk_b), the rest
+// max_batch), or which == 0 after a front launch that ran the fused kernel, which never writes block 0's output.
+extern "C" int axt_debug_cnn_activation(const axt_detector *det, int which, int slot0, int n, float *h_out)
+{
+    AXT_REQUIRE(det && h_out, "null argument");
+    AXT_REQUIRE(which >= 0 && which <= 9, "axt_debug_cnn_activation: buffer %d not in 0..9", which);
+    static const size_t per_item[10] = {20u * 256 * 256, 40u * 128 * 128, 80u * 64 * 64, 80u * 64 * 64, 80u * 32 * 32,
+                                        80u * 32 * 32,   80u * 16 * 16,   160u * 16 * 16, (size_t)kFc,  (size_t)kFc};
+    const int cap = std::min(det->max_batch, which < 2 ? kChunkA : which < 4 ? kChunkB : det->max_batch);
+    AXT_REQUIRE(slot0 >= 0 && n >= 0 && slot0 <= cap && n <= cap - slot0, "axt_debug_cnn_activation: slots [%d,%d) exceed the %d of buffer %d",
+                slot0, slot0 + n, cap, which);
+    AXT_REQUIRE(which != 0 || det->act0_written, "axt_debug_cnn_activation: the last pass ran the fused front kernel, which does not write block 0's output");
+    const float *src = which < 8 ? det->d_act[which] : which == 8 ? det->d_fc1 : det->d_fc2;
+    AXT_CHECK_HIP(hipDeviceSynchronize());
+    if (n > 0) AXT_CHECK_HIP(hipMemcpy(h_out, src + (size_t)slot0 * per_item[which], (size_t)n * per_item[which] * sizeof(float), hipMemcpyDeviceToHost));
+    return AXT_OK;
+}
+
+// the compile-time chunk sizes (-DAXT_CHUNK_A/B), so that tests compute the slot of an item instead of assuming them
+extern "C" int axt_debug_cnn_chunks(int *chunk_a, int *chunk_b)
+{
+    AXT_REQUIRE(chunk_a && chunk_b, "null argument");
+    *chunk_a = kChunkA;
+    *chunk_b = kChunkB;
+    return AXT_OK;
+}
 
 #ifdef AXT_WINO_STAMPS
 // diagnostic build: the stamp sums of the last Winograd launch, u64 [1024 workgroups][8 waves][8]

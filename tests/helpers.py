@@ -160,3 +160,41 @@ def check_flow_certificate(obs, entry, exit_, row_ptr, col, cost, nxt, track, to
     if F > min_flow:
         assert pt <= 0, f'one trajectory fewer would pay: pi(T) = {pt} > 0 with the flow count above min_flow'
     return {'arcs': int(len(col)), 'arcs_with_flow': int(on.sum()), 'trajectories': F, 'used': int(used.sum())}
+
+
+# ---- test-only exports of cnn.hip (not in include/axtrack_hip.h, not in _lib.SIGNATURES): bound here by hand
+CNN_BUFFER_SHAPES = [(20, 256, 256), (40, 128, 128), (80, 64, 64), (80, 64, 64), (80, 32, 32), (80, 32, 32), (80, 16, 16),
+                     (160, 16, 16), (1024,), (1024,)]
+
+
+def _cnn_debug_lib():
+    import ctypes
+    from axtrack_amd import _lib
+    lib = _lib.load()
+    lib.axt_debug_cnn_activation.restype = ctypes.c_int
+    lib.axt_debug_cnn_activation.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.axt_debug_cnn_chunks.restype = ctypes.c_int
+    lib.axt_debug_cnn_chunks.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    return lib
+
+
+def cnn_chunks():
+    """(chunk_a, chunk_b) the library was compiled with (axt_debug_cnn_chunks)."""
+    import ctypes
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    assert _cnn_debug_lib().axt_debug_cnn_chunks(ctypes.byref(a), ctypes.byref(b)) == 0
+    return a.value, b.value
+
+
+def cnn_activation_rc(detector, which, slot0, n):
+    """axt_debug_cnn_activation on a hotpath.Detector: (return code, f32 [n, C, H, W] or [n, 1024])."""
+    shape = CNN_BUFFER_SHAPES[which] if 0 <= which < len(CNN_BUFFER_SHAPES) else (1,)
+    out = np.empty((max(int(n), 0),) + shape, np.float32)
+    rc = _cnn_debug_lib().axt_debug_cnn_activation(detector._h, int(which), int(slot0), int(n), out.ctypes.data)
+    return rc, out
+
+
+def cnn_activation(detector, which, slot0, n):
+    rc, out = cnn_activation_rc(detector, which, slot0, n)
+    assert rc == 0, f'axt_debug_cnn_activation(buffer {which}, slots [{slot0},{slot0 + n})) returned {rc}'
+    return out
