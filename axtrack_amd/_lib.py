@@ -86,6 +86,13 @@ SIGNATURES = {
                                c_int, c_void_p, c_void_p, c_void_p]),
     'axt_link_cells': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                ctypes.POINTER(c_int64), c_void_p]),
+    'axt_target_tile_size': (c_int, []),
+    'axt_target_field': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),
+                                 c_void_p]),
+    'axt_target_sample': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p]),
+    'axt_target_paths': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                 c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'axt_render_tile_size': (c_int, []),
     'axt_render_frames': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -862,6 +862,7 @@ extern "C" void axt_grid_destroy(axt_grid *g)
 
 extern "C" const uint8_t *axt_grid_mask(const axt_grid *g) { return g ? g->d_mask : nullptr; }
 const int32_t *axt_grid_label(const axt_grid *g) { return g ? g->d_label : nullptr; }
+void axt_grid_shape(const axt_grid *g, int *H, int *W) { *H = g ? g->H : 0; *W = g ? g->W : 0; }
 // the component fields d_off [n_comp][H][W] (NULL when the mask has none)
 const uint8_t *axt_grid_off_field(const axt_grid *g, int *n_comp)
 {

@@ -5,6 +5,9 @@
 //   * trails: the tile's trail canvas (max key per pixel) stays in LDS across the frames of the run; each frame adds the
 //     5 x 5 squares of the cells whose segment ends at or before it (the tile's cell list is sorted by frame, so the
 //     history is splatted once per workgroup, not once per frame);
+//   * target paths and target cells (kind 4 rectangles, key 1 = path, 2 = target): a byte plane per frame, the paths
+//     first, the target cells after a barrier, so that the target wins wherever both fall (every writer of a pass
+//     stores the same value);
 //   * boxes, labels, header: one LDS key plane per frame, filled from the (frame, tile) primitive list with LDS max
 //     atomics: key = layer << 24 | (n + 1), so the upper layer wins and, within a layer, the larger n; ground-truth
 //     outlines set a flag plane (the same value from every writer);
@@ -27,7 +30,8 @@ constexpr int GLYPHS = 95;           // printable ASCII 32..126
 
 // one drawing primitive in output coordinates (axtrack_amd/render.py:_PRIM_FIELDS)
 struct Prim { int x0, y0, kind, a, b, key, pad0, pad1; };
-enum { P_DASHED = 0, P_SOLID = 1, P_GLYPH = 2, P_RECT = 3 };
+enum { P_DASHED = 0, P_SOLID = 1, P_GLYPH = 2, P_RECT = 3, P_TARGET = 4 };
+enum { TGT_PATH = 1, TGT_CELL = 2 };
 
 struct RenderArgs {
     const float *frames;        // detection frame t at frames + t * H * W (the context frames are skipped by the caller)
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(NT) void render_tiles(RenderArgs a)
 {
     __shared__ uint16_t bufA[BW * BW], bufB[BW * BW];
     __shared__ uint32_t trail[RT * RT], over[RT * RT];
-    __shared__ uint8_t gt[RT * RT];
+    __shared__ uint8_t gt[RT * RT], tgt[RT * RT];
     const int ntiles = a.ntx * a.nty;
     const int tile = blockIdx.x % ntiles, run = blockIdx.x / ntiles;
     const int oy0 = (tile / a.ntx) * RT, ox0 = (tile % a.ntx) * RT;
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(NT) void render_tiles(RenderArgs a)
     for (int i = i0; i < i1; ++i) {
         const int f = a.ts[i];
         __syncthreads();                                      // (the previous frame's reads of the planes are done)
-        for (int k = tid; k < RT * RT; k += NT) { over[k] = 0u; gt[k] = 0; }
+        for (int k = tid; k < RT * RT; k += NT) { over[k] = 0u; gt[k] = 0; tgt[k] = 0; }
         // trail cells of segments ending at or before f: [p, q)
         int lo = p, hi = pend;
         while (lo < hi) {
@@ -131,11 +135,24 @@ __global__ __launch_bounds__(NT) void render_tiles(RenderArgs a)
                         }
                     }
                 }
-            } else {
+            } else if (pr.kind == P_RECT) {
                 const int ya = max(y0, 0), yb = min(y0 + pr.b, RT), xa = max(x0, 0), xb = min(x0 + pr.a, RT);
                 for (int yy = ya; yy < yb; ++yy)
                     for (int xx = xa; xx < xb; ++xx) atomicMax(&over[yy * RT + xx], key);
+            } else if (pr.kind == P_TARGET && pr.key == TGT_PATH) {
+                const int ya = max(y0, 0), yb = min(y0 + pr.b, RT), xa = max(x0, 0), xb = min(x0 + pr.a, RT);
+                for (int yy = ya; yy < yb; ++yy)
+                    for (int xx = xa; xx < xb; ++xx) tgt[yy * RT + xx] = TGT_PATH;
             }
+        }
+        __syncthreads();                                      // (the paths are down: the target cells go over them)
+        for (int j = q0 + tid; j < q1; j += NT) {
+            if (a.prims[j].kind != P_TARGET || a.prims[j].key != TGT_CELL) continue;
+            const Prim pr = a.prims[j];
+            const int x0 = pr.x0 - ox0, y0 = pr.y0 - oy0;
+            const int ya = max(y0, 0), yb = min(y0 + pr.b, RT), xa = max(x0, 0), xb = min(x0 + pr.a, RT);
+            for (int yy = ya; yy < yb; ++yy)
+                for (int xx = xa; xx < xb; ++xx) tgt[yy * RT + xx] = TGT_CELL;
         }
         const float *frame = a.frames + (long long)f * HW;
         const uint8_t *mask = a.mask ? a.mask + (long long)f * a.mask_stride : nullptr;
@@ -207,6 +224,8 @@ __global__ __launch_bounds__(NT) void render_tiles(RenderArgs a)
                     if (a.grid && (gx % a.grid == 0 || gy % a.grid == 0)) {
                         r = blend(38, 255, r); g = blend(38, 255, g); b = blend(38, 255, b);
                     }
+                    const int tg = tgt[ly * RT + lx];
+                    if (tg) r = g = b = (tg == TGT_CELL) ? 255 : 217;
                     const uint32_t tk = trail[ly * RT + lx];
                     if (tk) {
                         const uint8_t *c = pal + 3 * a.trail_col[tk];

@@ -76,6 +76,7 @@ class AxonDetections(object):
         self.reproduce_label_quirk = bool(parameters.get('REPRODUCE_FRAME_LABEL_QUIRK', True))
         self._det_tables = None
         self._n_ids, self._n_tracks_dev = None, None
+        self._target_cells, self.structure_outputchannel_coo = None, None
 
     @property
     def n_ids(self):
@@ -1042,21 +1043,153 @@ class AxonDetections(object):
         return _growth_table(frame, ids, conf, x, y, r, seg, getattr(self.dataset, 'pixelsize', None),
                              getattr(self.dataset, 'dt', None))
 
+    # ------------------------------------------------------------------ target screens (video_plotting.py:170-177,308-309)
+    def _require_target(self, ids=False):
+        if getattr(self, '_shard', None) is not None:
+            raise NotImplementedError('target screens of a frame-sharded run are not implemented: screen in a single '
+                                      'process (AxonDetections without gather_detections)')
+        if getattr(self, '_target_cells', None) is None:
+            raise ValueError('no target: call set_target() first')
+        if ids and not getattr(self, '_solved', False):
+            raise ValueError('no identities: run assign_ids() first (or the association was infeasible)')
+
+    def set_target(self, target, reach_px=None):
+        """The target of the screen (the reference's StructureScreen.structure_outputchannel_coo, read at
+        video_plotting.py:176): (y, x), a bool array [H, W], or an int array [n, 2] of (y, x) cells -- non-empty and inside
+        the grid. Sets structure_outputchannel_coo = (y, x): for a region its cell nearest the centroid (ties: the first in
+        row-major order). reach_px: a growth cone within this many moves has reached the target (default
+        axon_box_size // 2). Drops the cached fields."""
+        H, W = self.dataset.sizey, self.dataset.sizex
+        cells = _parse_target(target, H, W)
+        reach = self.axon_box_size // 2 if reach_px is None else int(reach_px)
+        if reach < 0:
+            raise ValueError('reach_px must be >= 0')
+        self._target_cells, self.reach_px = cells, reach
+        self.structure_outputchannel_coo = _region_centre(cells, W)
+        self._target_fields, self._target_dets, self._target_path_cache = {}, None, None
+
+    def _target_groups(self):
+        """(grids, index): one device grid (None = all ones) per distinct mask, and the group of every frame (None: one)."""
+        if self.dataset.mask3d is not None:
+            grids, index = self._mask_grids()
+            return grids, np.ascontiguousarray(index, np.int32)
+        return [self._mask_dev()], None
+
+    def _target_field_of_group(self, g, grid):
+        key = (g, self.conn8)
+        if key not in self._target_fields:
+            H, W = self.dataset.sizey, self.dataset.sizex
+            cells = torch.from_numpy(self._target_cells.astype(np.int32)).to(self.device)
+            self._target_fields[key] = hp.target_field(cells, H, W, grid, self.conn8)
+        return self._target_fields[key]
+
+    def target_field(self, t=None):
+        """(off, moves) i32 [H, W] on the device: for every cell the off-mask cells entered and the moves of its
+        minimum-cost path to the target (hotpath.target_field), on the mask of detection frame t -- t is needed when the
+        mask changes over time (the mask _mask_dev(t) gives). Cached per distinct mask and connectivity."""
+        self._require_target()
+        grids, index = self._target_groups()
+        if index is None:
+            return self._target_field_of_group(0, grids[0])
+        if t is None:
+            raise ValueError('the mask changes over time: a frame index is needed')
+        return self._target_field_of_group(int(index[t]), grids[int(index[t])])
+
+    def _target_samples(self):
+        """(off, moves) of every detection slot on the device, i32 [F, cap] (-1: empty slot or outside the grid), with the
+        fields, grids and per-frame field index they were read from."""
+        self._require_target()
+        key = (self.d_x.data_ptr(), self.d_count.data_ptr(), self.conn8)
+        if self._target_dets is None or self._target_dets[0] != key:
+            grids, index = self._target_groups()
+            fields = [self._target_field_of_group(g, grid) for g, grid in enumerate(grids)]
+            if index is None:
+                off, moves, d_index = fields[0][0], fields[0][1], None
+            else:
+                off, moves = torch.stack([f[0] for f in fields]), torch.stack([f[1] for f in fields])
+                d_index = torch.from_numpy(index).to(self.device)
+            d_off, d_moves = hp.target_sample(off, moves, self.d_x, self.d_y, self.d_count, d_index)
+            self._target_dets = (key, d_off, d_moves, fields, grids, d_index)
+            self._target_path_cache = None
+        return self._target_dets[1:]
+
+    def target_arrays(self):
+        """(frame, axon_id, x, y, off, moves) of every IDed detection, frame-major like ided_arrays(): off / moves = the
+        target field at the detection (-1 outside the grid)."""
+        self._require_target(ids=True)
+        d_off, d_moves = self._target_samples()[:2]
+        off_h, moves_h = (a.copy() for a in hp.to_host(d_off, d_moves))
+        frame, ids, _, x, y = self.ided_arrays()
+        cnt = self._host_dets()[0]
+        valid = np.arange(off_h.shape[1])[None, :] < cnt[:, None]
+        sel = self._track_flat >= 0
+        return frame, ids, x, y, off_h[valid][sel], moves_h[valid][sel]
+
+    def get_target_distances(self):
+        """Per axon and frame where it has an IDed detection, indexed by (axonID, frameID): anchor_x, anchor_y, conf,
+        target_dist_px (moves of the minimum-cost path to the target, a diagonal move counts 1; NaN outside the grid),
+        target_off_mask (off-mask cells that path enters), on_mask_route (it enters none), approach_px (the axon's previous
+        known distance minus this one; NaN at its first frame), reached (target_dist_px <= reach_px), and with the
+        timelapse's pixelsize target_dist_um, with pixelsize and dt (minutes per frame) approach_um_per_min. frameID is
+        the true frame (no label quirk), as in get_axon_growth."""
+        frame, ids, x, y, off, moves = self.target_arrays()
+        conf = self.ided_arrays()[2]
+        return _target_table(frame, ids, conf, x, y, off, moves, self.reach_px, getattr(self.dataset, 'pixelsize', None),
+                             getattr(self.dataset, 'dt', None))
+
+    def get_target_summary(self):
+        """One row per axon: first_frame, last_frame, n_frames, dist_first, dist_last, dist_min, frame_of_min,
+        net_approach_px (dist_first - dist_last) and reached_frame (the first frame within reach_px; NaN if never)."""
+        frame, ids, _, _, _, moves = self.target_arrays()
+        return _target_summary(frame, ids, moves, self.reach_px)
+
+    def _target_paths(self):
+        """(cell_ptr i64 [F*cap+1], cells i64) on the host: the target path of every detection slot (CSR)."""
+        d_off, d_moves, fields, grids, d_index = self._target_samples()
+        if self._target_path_cache is None:
+            H, W = self.dataset.sizey, self.dataset.sizex
+            ptr, cells = hp.target_paths(fields, grids, self.d_x, self.d_y, d_moves, H, W, d_index, self.conn8)
+            self._target_path_cache = tuple(a.astype(np.int64) for a in hp.to_host(ptr, cells))
+        return self._target_path_cache
+
+    def _target_path_slots(self, t):
+        """(axon ids, slots f*cap+i) of the IDed detections of frame t."""
+        cnt = self._host_dets()[0]
+        track = self._track_dev()[t].cpu().numpy()[:cnt[t]]
+        i = np.nonzero(track >= 0)[0]
+        return track[i].astype(np.int64), t * int(self.d_x.shape[1]) + i
+
+    def get_trg_path(self, t, axon_name=None, ymin=0, ymax=0, xmin=0, xmax=0):
+        """The paths to the target of the IDed detections of frame t, in the format the reference's consumer indexes its
+        canvas with (video_plotting.py:173,308-309): {'Axon_007': (ys, xs)} of int arrays, the detection's cell first, a
+        target cell last. axon_name: a name or a list of names. Cells outside [ymin, ymax) x [xmin, xmax) are dropped and
+        the others shifted by (ymin, xmin), like get_axon_reconstructions; a max of 0 means the frame edge. A detection
+        outside the grid has no path."""
+        self._require_target(ids=True)
+        if not 0 <= int(t) < len(self):
+            raise ValueError(f'frame {t} lies outside the timelapse [0, {len(self)})')
+        ptr, cells = self._target_paths()
+        ids, slots = self._target_path_slots(int(t))
+        names = None if axon_name is None else ([axon_name] if isinstance(axon_name, str) else list(axon_name))
+        H, W = self.dataset.sizey, self.dataset.sizex
+        return _trg_path_dict(ids, slots, ptr, cells, (H, W), names, ymin, ymax, xmin, xmax)
+
     # ------------------------------------------------------------------ rendering (video_plotting.py:17-320)
     def render_frames(self, which_dets='IDed', t_y_x_slice=(None, None, None), draw_grid=True, draw_scalebar=False,
                       draw_axon_reconstructions=False, draw_true_dets=False, draw_brightened_bg=False, axon_subset=None,
-                      description='', annotate=True):
+                      description='', annotate=True, draw_target_paths=False):
         """The annotated frames video_plotting.draw_frame draws, as uint8 RGB on the timelapse's device: torch.uint8
         [T', H', W', 3] for t_y_x_slice = ((tmin, tmax), (ymin, ymax), (xmin, xmax)), None = the whole axis (as draw_all
         takes it). Drawn by one HIP kernel (axt_render_frames), bottom to top: the frame in red, the brightened background
         (draw_brightened_bg), the tile grid (draw_grid), the trails of get_axon_reconstructions(t, include_history=True)
-        (draw_axon_reconstructions, 'IDed' only), the ground-truth outlines (draw_true_dets), the dashed boxes of
+        (draw_axon_reconstructions, 'IDed' only), the paths to the target of get_trg_path(t) in (217, 217, 217) and over them
+        the target cells in white, 5 x 5 squares each (draw_target_paths, 'IDed' only, needs set_target()), the ground-truth outlines (draw_true_dets), the dashed boxes of
         get_frame_dets(which_dets, t) in palette[n % 20], their labels 'Ax{n:03}' and the header (annotate), the scale bar
         (draw_scalebar, needs the timelapse's pixelsize). axon_subset: names ('Axon_007') whose boxes, labels and trails
         are drawn. The rules are in DESIGN.md 6.8b; a host-resident timelapse is made resident first."""
         from .render import render_frames
         return render_frames(self, which_dets, t_y_x_slice, draw_grid, draw_scalebar, draw_axon_reconstructions,
-                             draw_true_dets, draw_brightened_bg, axon_subset, description, annotate)
+                             draw_true_dets, draw_brightened_bg, axon_subset, description, annotate, draw_target_paths)
 
     def _track_dev(self):
         """Trajectory id of every detection slot on the device, i32 [F,cap] (-1: none)."""
@@ -1236,6 +1369,113 @@ def _growth_table(frame, ids, conf, x, y, r, seg, pixelsize, dt):
     index = pd.MultiIndex.from_arrays([np.array([f'Axon_{int(i):0>3}' for i in a], dtype=object), f],
                                       names=('axonID', 'frameID'))
     return pd.DataFrame(data, index=index)
+
+
+def _parse_target(target, H, W):
+    """set_target's argument -> the sorted unique cells y*W + x (i64), validated."""
+    a = np.asarray(target)
+    if a.dtype == bool:
+        if a.shape != (H, W):
+            raise ValueError(f'a target mask must have the grid\'s shape {(H, W)}, got {a.shape}')
+        yx = np.argwhere(a)
+    elif a.ndim == 1 and a.size == 2:
+        yx = a.reshape(1, 2)
+    elif a.ndim == 2 and a.shape[1] == 2:
+        yx = a
+    else:
+        raise ValueError('target must be (y, x), a bool array [H, W] or an int array [n, 2] of (y, x)')
+    if not (np.issubdtype(yx.dtype, np.integer) or (yx.size and np.all(yx == np.floor(yx)))) and yx.size:
+        raise ValueError('target cells must be integers')
+    yx = yx.astype(np.int64)
+    if len(yx) == 0:
+        raise ValueError('the target is empty')
+    if (yx[:, 0] < 0).any() or (yx[:, 0] >= H).any() or (yx[:, 1] < 0).any() or (yx[:, 1] >= W).any():
+        raise ValueError(f'target cells must lie inside the grid [0, {H}) x [0, {W})')
+    return np.unique(yx[:, 0] * W + yx[:, 1])
+
+
+def _region_centre(cells, W):
+    """(y, x) of the cell nearest the centroid of the cells (sorted y*W + x); ties: the first in row-major order."""
+    y, x = cells // W, cells % W
+    n = len(cells)
+    d2 = (n * y - y.sum()) ** 2 + (n * x - x.sum()) ** 2          # n^2 x the squared distance, in integers
+    k = int(np.argmin(d2))
+    return int(y[k]), int(x[k])
+
+
+def _axon_names(a):
+    return np.array([f'Axon_{int(i):0>3}' for i in a], dtype=object)
+
+
+def _target_table(frame, ids, conf, x, y, off, moves, reach_px, pixelsize, dt):
+    """The DataFrame of get_target_distances from the IDed detections and their field samples (host only)."""
+    a, f = np.asarray(ids, np.int64), np.asarray(frame, np.int64)
+    order = np.lexsort((f, a))
+    a, f = a[order], f[order]
+    ax, ay, cf = (np.asarray(v, np.float64)[order] for v in (x, y, conf))
+    off, moves = np.asarray(off, np.int64)[order], np.asarray(moves, np.int64)[order]
+    n = len(a)
+    known = moves >= 0
+    dist = np.where(known, moves, np.nan).astype(np.float64)
+    offc = np.where(known, off, np.nan).astype(np.float64)
+    first = np.r_[True, a[1:] != a[:-1]] if n else np.zeros(0, bool)
+    start = np.maximum.accumulate(np.where(first, np.arange(n), 0)) if n else np.zeros(0, np.int64)
+    # the last earlier row of the same axon with a known distance
+    last_known = np.maximum.accumulate(np.where(known, np.arange(n), -1)) if n else np.zeros(0, np.int64)
+    prev = np.r_[-1, last_known[:-1]] if n else last_known
+    has_prev = prev >= start
+    pk = np.maximum(prev, 0)
+    approach = np.where(has_prev & known, dist[pk] - dist, np.nan) if n else dist
+    span = np.where(has_prev, f - f[pk], 1).astype(np.float64) if n else dist
+    data = {'anchor_x': ax, 'anchor_y': ay, 'conf': cf, 'target_dist_px': dist, 'target_off_mask': offc,
+            'on_mask_route': known & (off == 0), 'approach_px': approach, 'reached': known & (moves <= int(reach_px))}
+    if pixelsize is not None:
+        data['target_dist_um'] = dist * float(pixelsize)
+        if dt is not None:
+            data['approach_um_per_min'] = approach * float(pixelsize) / (float(dt) * span)
+    index = pd.MultiIndex.from_arrays([_axon_names(a), f], names=('axonID', 'frameID'))
+    return pd.DataFrame(data, index=index)
+
+
+def _target_summary(frame, ids, moves, reach_px):
+    """The DataFrame of get_target_summary (host only): one row per axon, in ascending id."""
+    a, f = np.asarray(ids, np.int64), np.asarray(frame, np.int64)
+    order = np.lexsort((f, a))
+    a, f, moves = a[order], f[order], np.asarray(moves, np.int64)[order]
+    dist = np.where(moves >= 0, moves, np.nan).astype(np.float64)
+    uniq, start, count = np.unique(a, return_index=True, return_counts=True)
+    cols = {k: [] for k in ('first_frame', 'last_frame', 'n_frames', 'dist_first', 'dist_last', 'dist_min', 'frame_of_min',
+                            'net_approach_px', 'reached_frame')}
+    for s0, c in zip(start, count):
+        d, fr = dist[s0:s0 + c], f[s0:s0 + c]
+        ok = ~np.isnan(d)
+        k = int(np.argmin(np.where(ok, d, np.inf))) if ok.any() else -1
+        hit = np.nonzero(ok & (d <= int(reach_px)))[0]
+        cols['first_frame'].append(int(fr[0])); cols['last_frame'].append(int(fr[-1])); cols['n_frames'].append(int(c))
+        cols['dist_first'].append(d[0]); cols['dist_last'].append(d[-1])
+        cols['dist_min'].append(d[k] if k >= 0 else np.nan)
+        cols['frame_of_min'].append(float(fr[k]) if k >= 0 else np.nan)
+        cols['net_approach_px'].append(d[0] - d[-1])
+        cols['reached_frame'].append(float(fr[hit[0]]) if len(hit) else np.nan)
+    return pd.DataFrame(cols, index=pd.Index(_axon_names(uniq), name='axonID'))
+
+
+def _trg_path_dict(ids, slots, cell_ptr, cells, shape, names, ymin, ymax, xmin, xmax):
+    """get_trg_path's dict from the CSR target paths (host only): axon ids and slots of one frame's IDed detections."""
+    H, W = shape
+    ymax, xmax = (ymax or H), (xmax or W)
+    out = {}
+    for k, s0 in zip(ids, slots):
+        name = f'Axon_{int(k):0>3}'
+        if names is not None and name not in names:
+            continue
+        c = cells[cell_ptr[s0]:cell_ptr[s0 + 1]]
+        if len(c) == 0:
+            continue
+        ys, xs = c // W, c % W
+        keep = (ys >= ymin) & (ys < ymax) & (xs >= xmin) & (xs < xmax)
+        out[name] = ((ys[keep] - ymin).astype(np.int64), (xs[keep] - xmin).astype(np.int64))
+    return out
 
 
 def _splitmix64(x):

@@ -507,6 +507,65 @@ def link_paths(links, x, y, H, W, grids, head_group=None, max_dist=MAX_PX_ASSOC_
     return length[:n], cell_ptr, cells[:int(total.value)], interp[:n, :int(max_gap) - 1]
 
 
+def target_field(target_cells, H, W, mask=None, conn8=False, return_rounds=False):
+    """The target screen's field (axt_target_field; the StructureScreen video_plotting.py:170-177 reads): for every cell
+    of the [H, W] grid the key (off-mask cells entered, moves) of its minimum-cost path to the nearest of target_cells
+    (i32 device tensor of y*W + x) on weights {1 on mask, 65536 off}. mask: None (all ones), a Grid, or an array.
+    Returns device tensors (off i32 [H,W], moves i32 [H,W]), with return_rounds also the rounds the search took."""
+    _require_gpu()
+    dev = target_cells.device
+    cells = target_cells.to(torch.int32).contiguous()
+    if mask is not None and not isinstance(mask, Grid):
+        mask = Grid(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask, conn8, dev)
+    off = torch.empty((int(H), int(W)), dtype=torch.int32, device=dev)
+    moves = torch.empty((int(H), int(W)), dtype=torch.int32, device=dev)
+    rounds = ctypes.c_int(0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().axt_target_field(mask._h if mask is not None else None, int(H), int(W), int(bool(conn8)),
+                                                cells.data_ptr(), int(cells.numel()), off.data_ptr(), moves.data_ptr(),
+                                                ctypes.byref(rounds), _stream()), 'axt_target_field')
+    return (off, moves, int(rounds.value)) if return_rounds else (off, moves)
+
+
+def target_sample(off, moves, x, y, count, field_index=None):
+    """The field at every detection slot (axt_target_sample): off / moves i32 [H,W] or [n_fields,H,W]; field_index i32 [F]
+    device tensor, the field of every frame (needed for several fields). Returns (off, moves) i32 [F,cap], -1 for empty
+    slots and for detections outside the grid."""
+    n_frames, cap = x.shape
+    H, W = int(off.shape[-2]), int(off.shape[-1])
+    n_fields = int(off.shape[0]) if off.dim() == 3 else 1
+    d_off = torch.empty((n_frames, cap), dtype=torch.int32, device=x.device)
+    d_moves = torch.empty((n_frames, cap), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().axt_target_sample(off.data_ptr(), moves.data_ptr(), n_fields, _lib.dptr(field_index), H, W,
+                                                 x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames, cap,
+                                                 d_off.data_ptr(), d_moves.data_ptr(), _stream()), 'axt_target_sample')
+    return d_off, d_moves
+
+
+def target_paths(fields, grids, x, y, det_moves, H, W, field_index=None, conn8=False):
+    """The target paths of all detection slots as CSR (axt_target_paths): fields = list of (off, moves) i32 [H,W] device
+    tensors and grids = list of Grid / None, one per distinct mask; field_index i32 [F] device tensor (None: one field).
+    Returns device tensors (cell_ptr i64 [F*cap+1], cells i32 y*W + x, detection first, target cell last)."""
+    n_frames, cap = x.shape
+    dev = x.device
+    lib = _lib.load()
+    cell_ptr = torch.empty((n_frames * cap + 1,), dtype=torch.int64, device=dev)
+    total = ctypes.c_int64(0)
+
+    def call(grid, off, moves, group, cells):
+        _lib.check(lib.axt_target_paths(grid._h if grid is not None else None, _lib.dptr(off), _lib.dptr(moves), int(H), int(W),
+                                        int(bool(conn8)), x.data_ptr(), y.data_ptr(), n_frames, cap, det_moves.data_ptr(),
+                                        _lib.dptr(field_index), group, cell_ptr.data_ptr(), _lib.dptr(cells),
+                                        ctypes.byref(total), _stream()), 'axt_target_paths')
+    with torch.cuda.device(dev):
+        call(None, None, None, 0, None)
+        cells = torch.empty((max(int(total.value), 1),), dtype=torch.int32, device=dev)
+        for g, (grid, (off, moves)) in enumerate(zip(grids, fields)):
+            call(grid, off, moves, g, cells)
+    return cell_ptr, cells[:int(total.value)]
+
+
 def detection_confusion(conf, x, y, count, gx, gy, gcount, thrs, min_dist=23, k_mask=-1):
     """compute_TP_FP_FN (AxonDetections.py:409-466) for all frames and thresholds at once: i32 [F,3,n_thr] on the
     device (TP, FP, FN); with k_mask >= 0 also (fp_mask u8 [F,cap], fn_mask u8 [F,gcap]) for that threshold."""

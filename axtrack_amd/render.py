@@ -24,7 +24,9 @@ PALETTE = np.array([[int(round(c * 255)) for c in colorsys.hsv_to_rgb(k / 20, 1.
 WHITE_ALPHA_GRID, WHITE_ALPHA_GT, BG_ALPHA_DIM = 38, 154, 26
 HEADER_RGB = (107, 107, 107)
 LAYER_BOX, LAYER_LABEL, LAYER_HEADER = 1, 2, 3
-P_DASHED, P_SOLID, P_GLYPH, P_RECT = 0, 1, 2, 3
+P_DASHED, P_SOLID, P_GLYPH, P_RECT, P_TARGET = 0, 1, 2, 3, 4
+TARGET_PATH_RGB, TARGET_RGB = (217, 217, 217), (255, 255, 255)
+TGT_PATH, TGT_CELL = 1, 2          # keys of the P_TARGET rectangles
 
 # 5 x 7 font of printable ASCII 32..126: five column bytes per glyph, bit 0 = top row (the classic LCD character set)
 _FONT_COLUMNS = bytes.fromhex(
@@ -178,9 +180,68 @@ def _trail_cells(dets, t_last, subset):
     return frame[segi], key[segi], c % W, c // W, col
 
 
+def _run_rects(ys, xs, pid):
+    """The 5 x 5 squares of the cells of paths, with every straight run merged: cells (ys, xs) of all paths one after the
+    other, pid = the path of every cell. A horizontal or vertical run of k cells becomes ONE (k + 4) x 5 (5 x (k + 4))
+    rectangle; cells that only diagonal steps touch keep their own square. Returns (first cell index, x0, y0, w, h) of the
+    rectangles: together exactly the pixels of the per-cell squares."""
+    ys, xs, pid = (np.asarray(a, np.int64) for a in (ys, xs, pid))
+    n = len(ys)
+    if n == 0:
+        return tuple(np.zeros(0, np.int64) for _ in range(5))
+    dy, dx = np.diff(ys), np.diff(xs)
+    straight = (pid[1:] == pid[:-1]) & (np.abs(dy) + np.abs(dx) == 1)
+    cont = np.zeros(n - 1, bool)                                   # step k continues the run of step k - 1
+    cont[1:] = straight[1:] & straight[:-1] & (dy[1:] == dy[:-1]) & (dx[1:] == dx[:-1])
+    first = np.nonzero(straight & ~cont)[0]
+    goes_on = np.zeros(n - 1, bool)                                # step k + 1 continues the run of step k
+    goes_on[:-1] = cont[1:]
+    last = np.nonzero(straight & ~goes_on)[0] + 1                  # (index of the run's last CELL)
+    covered = np.zeros(n, bool)
+    covered[:-1] |= straight
+    covered[1:] |= straight
+    single = np.nonzero(~covered)[0]
+    a = np.r_[first, single]
+    b = np.r_[last, single]
+    return (a, np.minimum(xs[a], xs[b]) - 2, np.minimum(ys[a], ys[b]) - 2, np.abs(xs[b] - xs[a]) + 5,
+            np.abs(ys[b] - ys[a]) + 5)
+
+
+def _target_prims(dets, ts, subset, ymin, xmin):
+    """The target layer's rectangles, rows (i, x0, y0, kind, a, b, key): the target paths of the drawn axons' detections
+    (get_trg_path(t) of every output frame), then the target cells of every output frame."""
+    W = dets.dataset.sizex
+    inv = np.full(len(dets), -1, np.int64)
+    inv[ts] = np.arange(len(ts))
+    cnt = dets._host_dets()[0]
+    cap = int(dets.d_x.shape[1])
+    frame_of = np.repeat(np.arange(len(cnt)), cnt)
+    idx_in = np.arange(len(frame_of)) - dets._offs[frame_of]
+    track = dets._track_flat
+    sel = (track >= 0) & (inv[frame_of] >= 0)
+    if subset is not None:
+        sel &= np.isin(track, subset)
+    slots = frame_of[sel] * cap + idx_in[sel]
+    ptr, cells = dets._target_paths()
+    n = ptr[slots + 1] - ptr[slots]
+    pid = np.repeat(np.arange(len(slots)), n)
+    c = cells[np.repeat(ptr[slots], n) + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)]
+    k, x0, y0, w, h = _run_rects(c // W - ymin, c % W - xmin, pid)
+    i = inv[frame_of[sel]][pid[k]] if len(k) else k
+    rows = [np.stack([i, x0, y0, np.full(len(k), P_TARGET), w, h, np.full(len(k), TGT_PATH)], 1)]
+    tc = dets._target_cells
+    _, x0, y0, w, h = _run_rects(tc // W - ymin, tc % W - xmin, np.zeros(len(tc), np.int64))
+    one = np.stack([np.zeros(len(x0), np.int64), x0, y0, np.full(len(x0), P_TARGET), w, h, np.full(len(x0), TGT_CELL)], 1)
+    for j in range(len(ts)):
+        r = one.copy()
+        r[:, 0] = j
+        rows.append(r)
+    return rows
+
+
 def render_frames(dets, which_dets='IDed', t_y_x_slice=(None, None, None), draw_grid=True, draw_scalebar=False,
                   draw_axon_reconstructions=False, draw_true_dets=False, draw_brightened_bg=False, axon_subset=None,
-                  description='', annotate=True, _frames=None):
+                  description='', annotate=True, draw_target_paths=False, _frames=None):
     """AxonDetections.render_frames (see there). _frames: the detection frames to draw (render_inference's chunks)."""
     ds = dets.dataset
     if getattr(dets, '_shard', None) is not None:
@@ -198,8 +259,12 @@ def render_frames(dets, which_dets='IDed', t_y_x_slice=(None, None, None), draw_
         raise ValueError('no labels: call set_groundtruth() first')
     if draw_axon_reconstructions and which_dets != 'IDed':
         raise ValueError("draw_axon_reconstructions goes with which_dets='IDed' (the reconstructions are the IDed tracks')")
+    if draw_target_paths and which_dets != 'IDed':
+        raise ValueError("draw_target_paths goes with which_dets='IDed' (the paths start at the IDed detections)")
     if which_dets == 'IDed' and not getattr(dets, '_solved', False):
         raise ValueError('no identities: run assign_ids() first (or the association was infeasible)')
+    if draw_target_paths:
+        dets._require_target(ids=True)
     H, W = ds.sizey, ds.sizex
     (tmin, tmax), (ymin, ymax), (xmin, xmax) = ((0, n) if v is None else tuple(v) for v, n in zip(t_y_x_slice, (T, H, W)))
     if not (0 <= tmin <= tmax <= T and 0 <= ymin < ymax <= H and 0 <= xmin < xmax <= W):
@@ -246,9 +311,11 @@ def render_frames(dets, which_dets='IDed', t_y_x_slice=(None, None, None), draw_
         cap = '200 um'
         rows.append(_text_prims([cap] * len(k), k, np.full(len(k), Wo - 4 * s - (6 * s * len(cap) - s)),
                                 np.full(len(k), yb + 4 * s), s, np.full(len(k), LAYER_HEADER << 24)))
+    if draw_target_paths:
+        rows += _target_prims(dets, ts, subset, ymin, xmin)
     pr = np.concatenate([r.reshape(-1, 7) for r in rows]).astype(np.int64)
     ext_w = np.where(pr[:, 3] == P_GLYPH, 5 * pr[:, 5], pr[:, 4])
-    ext_h = np.where(pr[:, 3] == P_GLYPH, 7 * pr[:, 5], np.where(pr[:, 3] == P_RECT, pr[:, 5], pr[:, 4]))
+    ext_h = np.where(pr[:, 3] == P_GLYPH, 7 * pr[:, 5], np.where((pr[:, 3] == P_RECT) | (pr[:, 3] == P_TARGET), pr[:, 5], pr[:, 4]))
     idx, bins = _bin(pr[:, 0], pr[:, 1], pr[:, 2], ext_w, ext_h, Ho, Wo, rt, len(ts))
     prims = np.zeros((len(idx), 8), np.int32)
     prims[:, :6] = pr[idx, 1:7]
@@ -357,7 +424,7 @@ def render_inference(axon_dets, which_dets='IDed', dest_dir=None, animated=False
                 raise ValueError(f'{k}={v!r} has no meaning in axtrack_amd.render_inference (frames and APNG only; '
                                  f'DESIGN.md section 9)')
     allowed = {'draw_grid', 'draw_scalebar', 'draw_axon_reconstructions', 'draw_true_dets', 'draw_brightened_bg',
-               'axon_subset', 'description', 'annotate'}
+               'axon_subset', 'description', 'annotate', 'draw_target_paths'}
     bad = set(kwargs) - allowed
     if bad:
         raise TypeError(f'render_inference got unexpected keywords {sorted(bad)}')

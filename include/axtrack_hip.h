@@ -422,6 +422,45 @@ int axt_link_cells(const int32_t *d_links, int n_links, const int32_t *d_len, co
                    int max_gap, int64_t *d_cell_ptr, int32_t *d_cells, int32_t *d_interp, int64_t *n_cells, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Target screens: every growth cone's distance and path to a target through the structure -- the "StructureScreen" the
+ * reference's drawing code reads and never shipped (video_plotting.py:170-177,308-309: get_trg_path(t, ymin, ymax),
+ * structure_outputchannel_coo). target.hip, DESIGN.md 6.8c.
+ * ------------------------------------------------------------------------------------------ */
+/* The field of a set of target cells over the whole grid: for every cell c the key (off, moves) of the minimum-cost
+ * 4-connected (conn8: 8-connected) path from c to any target cell on the weights {1 on mask, 65536 off} of
+ * AxonDetections.py:598 -- off = off-mask cells entered, moves = steps, ordered lexicographically as in axt_path_cost
+ * (for one target cell moves + 1 is what axt_path_cost returns wherever its gate lets it answer); (0, 0) on the targets.
+ * d_target_cells i32 [n_targets] = y*W + x on the device (entries outside the grid are ignored), n_targets >= 1;
+ * grid = NULL: all-ones mask (the same kernel). d_off / d_moves i32 [H, W]. Tiled label-correcting search, one launch per
+ * round over the tiles whose halo improved (axt_target_tile_size: the tile edge); the host reads a counter back every few
+ * rounds and returns AXT_ERUNTIME beyond n_tiles * 4 * tile rounds. Scratch (8 bytes per cell) is allocated on the
+ * stream. *n_rounds (may be NULL) = rounds that had work. The result is the unique fixed point: byte-identical from run
+ * to run. Synchronises the stream. */
+int axt_target_tile_size(void);
+int axt_target_field(const axt_grid *grid, int H, int W, int conn8, const int32_t *d_target_cells, int n_targets,
+                     int32_t *d_off, int32_t *d_moves, int *n_rounds, void *stream);
+
+/* The field at every detection slot: d_det_off / d_det_moves i32 [n_frames, cap] = (off, moves) at (d_y, d_x) of the
+ * slot, -1 for slots >= d_count[f] and for detections outside the grid (the decode does not clamp). d_off / d_moves i32
+ * [n_fields, H, W]; d_field_index i32 [n_frames] = the field of frame f (one per distinct mask of a time-varying mask;
+ * NULL with n_fields == 1; an index outside [0, n_fields) gives -1). Asynchronous. */
+int axt_target_sample(const int32_t *d_off, const int32_t *d_moves, int n_fields, const int32_t *d_field_index, int H,
+                      int W, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
+                      int32_t *d_det_off, int32_t *d_det_moves, void *stream);
+
+/* The target paths of the detection slots as CSR, in the shape of axt_link_cells. The path of a detection starts at its
+ * cell; every step goes to the first neighbour n (up, down, left, right, then the diagonals in axt_path_cells' order)
+ * with key(c) == key(n) + (mask[n] ? 0 : 1, 1); it has moves + 1 cells and ends in a target cell.
+ * Phase 1 (d_cells == NULL): d_cell_ptr i64 [n_frames*cap + 1] = prefix sum of d_det_moves + 1 (0 where it is -1),
+ * *n_cells = total (synchronises). Phase 2: d_cells i32 [*n_cells] receives y*W + x, detection first, for the slots
+ * whose frame f has d_field_index[f] == group (all slots for d_field_index == NULL) from the ONE field d_off / d_moves
+ * i32 [H, W] and its grid (NULL = all ones): one call per distinct mask. One thread per detection. Asynchronous. */
+int axt_target_paths(const axt_grid *grid, const int32_t *d_off, const int32_t *d_moves, int H, int W, int conn8,
+                     const int32_t *d_x, const int32_t *d_y, int n_frames, int cap, const int32_t *d_det_moves,
+                     const int32_t *d_field_index, int group, int64_t *d_cell_ptr, int32_t *d_cells, int64_t *n_cells,
+                     void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Detection metrics: compute_TP_FP_FN (AxonDetections.py:409-466) for every frame
  * and every confidence threshold. Detections as axt_decode_stitch_nms leaves them; labels d_gx, d_gy
  * i32 [n_frames, gcap], d_gcount i32 [n_frames]; d_thrs f64 [n_thr] on the device (the reference's
@@ -448,7 +487,8 @@ int axt_detection_confusion(const float *d_conf, const int32_t *d_x, const int32
  * key, x, y in output coordinates; binned per output tile, d_trail_ptr i32 [n_tiles+1], sorted by frame within a
  * tile): the cells with frame <= the output frame's, 5 x 5 squares, the largest key wins, colour
  * palette[d_trail_col[key]]. Primitives: d_prims i32 [m, 8] (x0, y0, kind, a, b, key, 0, 0: kind 0 dashed box
- * outline a x a, 1 solid ground-truth outline, 2 glyph a = char - 32 at scale b, 3 rectangle a x b) binned per
+ * outline a x a, 1 solid ground-truth outline, 2 glyph a = char - 32 at scale b, 3 rectangle a x b, 4 rectangle a x b of the target layer that lies between the
+ * grid and the trails: key 1 = a target path, (217, 217, 217), key 2 = target cells, white, over the paths) binned per
  * (output frame, tile): d_prim_ptr i32 [n_out*n_tiles+1]; key = layer << 24 | (n + 1), the largest key wins, layer 3
  * is grey (107). d_tables u8: palette [20, 3], then the glyph rows [95, 7]. Asynchronous. */
 int axt_render_tile_size(void);
