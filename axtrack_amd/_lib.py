@@ -93,6 +93,11 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p]),
     'axt_target_paths': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                  c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    'axt_segment_tile_size': (c_int, []),
+    'axt_segment_edges': (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'axt_segment_histogram': (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p]),
+    'axt_segment_close': (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_void_p, c_void_p]),
+    'axt_segment_flood': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     'axt_render_tile_size': (c_int, []),
     'axt_render_frames': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

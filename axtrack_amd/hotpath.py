@@ -566,6 +566,67 @@ def target_paths(fields, grids, x, y, det_moves, H, W, field_index=None, conn8=F
     return cell_ptr, cells[:int(total.value)]
 
 
+def segment_tile_size():
+    """Tile edge of the flood's reachability search (axt_segment_tile_size)."""
+    return int(_lib.load().axt_segment_tile_size())
+
+
+def segment_edges(img, sigma=1.0):
+    """filters.prewitt + filters.gaussian of 00_segment_bg.ipynb's segment_microchannels in one launch
+    (axt_segment_edges). img: uint16 (or int16-viewed) [H,W] device tensor. Returns device tensors (P f32 [H,W] edge
+    magnitude, G f32 [H,W] smoothed, minmax f32 [2] = min(G), max(G))."""
+    _require_gpu()
+    H, W = img.shape
+    assert img.is_contiguous() and img.element_size() == 2
+    P = torch.empty((H, W), dtype=torch.float32, device=img.device)
+    G = torch.empty((H, W), dtype=torch.float32, device=img.device)
+    minmax = torch.empty((2,), dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.load().axt_segment_edges(img.data_ptr(), int(H), int(W), float(sigma), P.data_ptr(), G.data_ptr(),
+                                                 minmax.data_ptr(), _stream()), 'axt_segment_edges')
+    return P, G, minmax
+
+
+def segment_histogram(G, mn, mx):
+    """np.histogram(G, 256, range=(mn, mx)) of the notebook's threshold_otsu(prewitt_gaussian) (axt_segment_histogram).
+    G: f32 device tensor. Returns the counts as an i64 [256] device tensor."""
+    _require_gpu()
+    assert G.is_contiguous() and G.dtype == torch.float32
+    hist = torch.empty((256,), dtype=torch.int64, device=G.device)
+    with torch.cuda.device(G.device):
+        _lib.check(_lib.load().axt_segment_histogram(G.data_ptr(), int(G.numel()), float(mn), float(mx), hist.data_ptr(),
+                                                     _stream()), 'axt_segment_histogram')
+    return hist
+
+
+def segment_close(P, thr, k=4):
+    """morphology.binary_closing(prewitt > thr, morphology.square(k)) of segment_microchannels (axt_segment_close).
+    P: f32 [H,W] device tensor. Returns a u8 [H,W] device tensor of 0 / 1."""
+    _require_gpu()
+    H, W = P.shape
+    assert P.is_contiguous() and P.dtype == torch.float32
+    out = torch.empty((H, W), dtype=torch.uint8, device=P.device)
+    with torch.cuda.device(P.device):
+        _lib.check(_lib.load().axt_segment_close(P.data_ptr(), int(H), int(W), float(thr), int(k), out.data_ptr(), _stream()),
+                   'axt_segment_close')
+    return out
+
+
+def segment_flood(img, seed_y, seed_x, conn8=True, return_rounds=False):
+    """flood(filled_mask, floodpoint) of the notebook's flood_initial_mask (axt_segment_flood). img: u8 / bool [H,W]
+    device tensor. Returns a u8 [H,W] device tensor, 1 on the cells connected to the seed through cells of the seed's
+    value; with return_rounds also the rounds the search took."""
+    _require_gpu()
+    H, W = img.shape
+    img = img.to(torch.uint8).contiguous()
+    out = torch.empty((H, W), dtype=torch.uint8, device=img.device)
+    rounds = ctypes.c_int(0)
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.load().axt_segment_flood(img.data_ptr(), int(H), int(W), int(seed_y), int(seed_x), int(bool(conn8)),
+                                                 out.data_ptr(), ctypes.byref(rounds), _stream()), 'axt_segment_flood')
+    return (out, int(rounds.value)) if return_rounds else out
+
+
 def detection_confusion(conf, x, y, count, gx, gy, gcount, thrs, min_dist=23, k_mask=-1):
     """compute_TP_FP_FN (AxonDetections.py:409-466) for all frames and thresholds at once: i32 [F,3,n_thr] on the
     device (TP, FP, FN); with k_mask >= 0 also (fp_mask u8 [F,cap], fn_mask u8 [F,gcap]) for that threshold."""

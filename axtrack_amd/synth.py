@@ -149,6 +149,15 @@ def corridor_mask(H, W, width=40, pitch=128):
     return (y[:, None] | x[None, :])
 
 
+def transmission_image(mask, seed=0):
+    """Synthetic transmission image of a microstructure, u16 [H, W]: 28000 inside the channels of `mask`, 20000
+    outside, blurred by the optics (Gaussian, sigma 1.5) and with N(0, 300) sensor noise of default_rng(seed)."""
+    from scipy.ndimage import gaussian_filter
+    img = gaussian_filter(20000.0 + 8000.0 * np.asarray(mask, np.float64), 1.5)
+    img = img + np.random.default_rng(seed).normal(0.0, 300.0, img.shape)
+    return np.clip(np.rint(img), 0, 65535).astype(np.uint16)
+
+
 def synth_detections(n_frames, H, W, n_alive=75, seed=0, mean_life=120, p_detect=0.92, clutter=0.08, max_step=10.0,
                      jitter=2.0, min_dist=23, cap=None):
     """Detections of a scene of MOVING growth cones, for association-only workloads (random walk of

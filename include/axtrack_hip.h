@@ -461,6 +461,49 @@ int axt_target_paths(const axt_grid *grid, const int32_t *d_off, const int32_t *
                      void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mask preparation: the microchannel mask from a transmission image, which the reference makes by hand in a notebook
+ * with napari and scikit-image (data_prep_nbs/00_segment_bg.ipynb). segment.hip, DESIGN.md 6.8d, where every stage is
+ * defined in terms of SciPy and numpy. Image sizes: H, W > 0 and H * W <= 2^31 - 1.
+ * ------------------------------------------------------------------------------------------ */
+/* segment_microchannels, `filters.prewitt(transm_chnl)` and `filters.gaussian(prewitt, sigma=gaussion_sigma)`, in one
+ * launch. d_img u16 [H, W]. d_P f32 [H, W] = sqrt((gy^2 + gx^2) / 2), gy / gx = the 3 x 3 Prewitt differences along
+ * the rows / columns divided by 3, the image continued by reflection (d c b a | a b c d); the 3 x 3 sums are exact.
+ * d_G f32 [H, W] = d_P smoothed by the separable Gaussian of 2 radius + 1 taps, radius = int(4 sigma + 0.5), weights
+ * exp(-x^2 / 2 sigma^2) normalised in f64 and rounded to f32, d_P continued by its nearest edge value.
+ * d_minmax f32 [2] = min(d_G), max(d_G), exact (integer atomics on the bit patterns of values >= 0).
+ * sigma > 0, radius <= 16 and min(H, W) >= 2 radius + 2, else AXT_EINVAL. Asynchronous. */
+int axt_segment_edges(const uint16_t *d_img, int H, int W, double sigma, float *d_P, float *d_G, float *d_minmax,
+                      void *stream);
+
+/* The histogram `threshold_otsu(prewitt_gaussian)` starts from (segment_microchannels): d_hist i64 [256] = the counts
+ * np.histogram(d_G, 256, range=(mn, mx)) gives for the n values of d_G taken as f64: v falls into bin i with
+ * e_i <= v < e_i+1, the last bin closed, e_i = mn + i (mx - mn) / 256 in f64 and e_256 = mx; values outside [mn, mx]
+ * are not counted. mn == mx: everything equal to mn falls into bin 0. Integer counts: identical from run to run. The
+ * threshold itself is 256 numbers of host arithmetic (axtrack_amd.segment.otsu_threshold_from_hist). 1 <= n <= 2^31 - 1,
+ * mn <= mx finite, else AXT_EINVAL. Asynchronous. */
+int axt_segment_histogram(const float *d_G, int64_t n, double mn, double mx, int64_t *d_hist, void *stream);
+
+/* `prewitt_bin = prewitt > threshold` and `morphology.binary_closing(prewitt_bin, morphology.square(bin_closing_dim))`
+ * (segment_microchannels): d_out u8 [H, W] (0 / 1) = the erosion of the dilation of (f64)d_P > thr by k x k ones. With
+ * a = k / 2 and b = k - 1 - a per axis: dilation = OR over [y - b, y + a], 0 outside the image; erosion = AND over
+ * [y - a, y + b], 1 outside (scipy.ndimage.binary_erosion(binary_dilation(B, ones), ones, border_value=1)). The image
+ * is bit-packed between the steps; scratch (H * ceil(W / 64) * 16 bytes) is allocated on the stream. 2 <= k <= 32 and
+ * thr a number, else AXT_EINVAL. Asynchronous. */
+int axt_segment_close(const float *d_P, int H, int W, double thr, int k, uint8_t *d_out, void *stream);
+
+/* flood_initial_mask, `flood(filled_mask, floodpoint)`: d_out u8 [H, W] = 1 on the cells connected to the seed
+ * (seed_y, seed_x) through cells with the seed's value of d_img u8 [H, W] (zero / non-zero; the seed may sit on either),
+ * 4-connected or (conn8) 8-connected: lab == lab[seed] for lab = scipy.ndimage.label(img == img[seed], structure).
+ * Tiled reachability search on bit planes, one launch per round over the tiles whose halo grew (axt_segment_tile_size:
+ * the tile edge); the host reads a counter back every few rounds and returns AXT_ERUNTIME beyond n_tiles * 4 * tile
+ * rounds. Scratch (H * ceil(W / 64) * 16 bytes) is allocated on the stream. *rounds_out (may be NULL) = rounds that had
+ * work. The result is the unique fixed point: byte-identical from run to run. A seed outside the image: AXT_EINVAL.
+ * Synchronises the stream. */
+int axt_segment_tile_size(void);
+int axt_segment_flood(const uint8_t *d_img, int H, int W, int seed_y, int seed_x, int conn8, uint8_t *d_out,
+                      int *rounds_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Detection metrics: compute_TP_FP_FN (AxonDetections.py:409-466) for every frame
  * and every confidence threshold. Detections as axt_decode_stitch_nms leaves them; labels d_gx, d_gy
  * i32 [n_frames, gcap], d_gcount i32 [n_frames]; d_thrs f64 [n_thr] on the device (the reference's
