@@ -24,6 +24,8 @@ SIGNATURES = {
     'axt_cnn_forward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'axt_cnn_forward_frames': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                        c_void_p, c_void_p]),
+    'axt_cnn_features_frames': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                        c_void_p, c_void_p]),
     'axt_cnn_front_frames': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     'axt_cnn_back': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'axt_cnn_flops_per_tile': (c_double, []),
@@ -98,6 +100,18 @@ SIGNATURES = {
     'axt_segment_histogram': (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p]),
     'axt_segment_close': (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_void_p, c_void_p]),
     'axt_segment_flood': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    'axt_yolo_targets': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'axt_head_trainer_create': (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [c_int, ctypes.POINTER(c_void_p)]),
+    'axt_head_trainer_destroy': (None, [c_void_p]),
+    'axt_head_trainer_device_bytes': (c_size_t, [c_void_p]),
+    'axt_head_trainer_read_weights': (c_int, [c_void_p] * 7),
+    'axt_head_trainer_read_moments': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              ctypes.POINTER(c_int64)]),
+    'axt_head_trainer_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'axt_head_trainer_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double,
+                                      c_void_p, c_void_p, c_void_p]),
+    'axt_head_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
+                                      c_double, c_double, c_void_p]),
     'axt_render_tile_size': (c_int, []),
     'axt_render_frames': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1814,8 +1814,9 @@ int run_front_b(axt_detector *d, int nb, float *act4_out, hipStream_t st)
     return AXT_OK;
 }
 
-// layers 5..7 + the three linear layers for nb items whose block-4 output is in d_act[4]
-int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
+// conv layers 5..7 for nb items whose block-4 output is in d_act[4]: d_act[7] [item,160,16,16] is what the first linear
+// layer reads (the flatten of model.py:50-53 is this buffer as it stands)
+int run_back_conv(axt_detector *d, int nb, hipStream_t st)
 {
     int rc;
     {
@@ -1838,6 +1839,14 @@ int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
                            : launch_conv<80, 160, false, 8, 5>(d->d_act[6], d->d_wconv[7], d->d_bconv[7], d->d_act[7], 16, 2, nb, st);
         if (rc) return rc;
     }
+    return AXT_OK;
+}
+
+// layers 5..7 + the three linear layers for nb items whose block-4 output is in d_act[4]
+int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
+{
+    int rc;
+    if ((rc = run_back_conv(d, nb, st))) return rc;
     {
         ProfSpan ps(d, st, 8, nb);
         if ((rc = launch_gemm(d->d_act[7], kFeat, d->d_wfc[0], kFc, d->d_slab, nb, kFeat, kFc1Split, st))) return rc;
@@ -1865,8 +1874,10 @@ int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
     return AXT_OK;
 }
 
+// d_feat != nullptr: stop after conv block 10 and copy its output, the input of the first linear layer, to
+// d_feat [n_items, 40960] (axt_cnn_features_frames); d_yolo is not written then
 int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, int tstep, int n_items, int n_tiles,
-                  const TileList &tl, float *d_yolo, hipStream_t st)
+                  const TileList &tl, float *d_yolo, hipStream_t st, float *d_feat = nullptr)
 {
     for (int base = 0; base < n_items; base += d->max_batch) {
         const int nb = (n_items - base < d->max_batch) ? n_items - base : d->max_batch;
@@ -1879,6 +1890,13 @@ int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, 
             }
             const int rc = run_front_b(d, nbb, d->d_act[4] + (size_t)cb * 80 * 32 * 32, st);
             if (rc) return rc;
+        }
+        if (d_feat) {
+            const int rc = run_back_conv(d, nb, st);
+            if (rc) return rc;
+            AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)base * kFeat, d->d_act[7], (size_t)nb * kFeat * sizeof(float),
+                                         hipMemcpyDeviceToDevice, st));
+            continue;
         }
         const int rc = run_back(d, nb, d_yolo + (size_t)base * kOut, st);
         if (rc) return rc;
@@ -2091,6 +2109,26 @@ int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, 
     }
     if (n_frames == 0) return AXT_OK;
     return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, d_yolo, (hipStream_t)stream);
+}
+
+int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
+                            const int32_t *h_tile_yx, int n_tiles, float *d_feat, void *stream)
+{
+    AXT_REQUIRE(det && d_frames && d_feat && h_tile_yx, "null argument");
+    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
+    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",
+                t0, t0 + n_frames, T_all);
+    TileList tl;
+    tl.n = n_tiles;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * AXT_TILE < H && tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
+                    ty, tx, H, W);
+        tl.yx[2 * k] = (short)ty;
+        tl.yx[2 * k + 1] = (short)tx;
+    }
+    if (n_frames == 0) return AXT_OK;
+    return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, nullptr, (hipStream_t)stream, d_feat);
 }
 
 int axt_cnn_front_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,

@@ -10,6 +10,7 @@ import torch
 from . import _lib
 
 TILE, S, CELLS = 512, 12, 144
+FEATURES = 160 * 16 * 16                # what the first linear layer reads per tile (model.py:50-53)
 CONF_FLOOR = float(np.float32(0.55))   # all_conf_thrs.min() as f32 (AxonDetections.py:76,122)
 MAX_PX_ASSOC_DIST = 500                # AxonDetections.py:77
 AXON_BOX_SIZE = 70                     # AxonDetections.py:78
@@ -66,6 +67,7 @@ class Detector:
                        'axt_detector_create')
         self._h = handle
         self._lib = lib
+        self.state_dict_source = state_dict     # training.fine_tune_head starts the linear head from these tensors
         self.arith = 'f32'              # axt_detector_create leaves the handle in its default mode (f32 Winograd)
         self.fused_front = os.environ.get('AXT_FUSE_S2', '1') != '0'     # what axt_detector_create read
         self.set_arith(arith)
@@ -159,6 +161,22 @@ class Detector:
                        'axt_cnn_forward_frames')
         return out
 
+
+    def features_frames(self, frames, tile_yx, t0=0, n_frames=None):
+        """The frozen trunk of detect_frames: frames f32 [T_all,H,W] on the GPU -> [n_frames * n_tiles, 40960], the input of
+        the first linear layer per (frame, tile) item in the flatten order of model.py:50-53 (axt_cnn_features_frames).
+        What training.HeadTrainer trains on."""
+        T_all, H, W = frames.shape
+        if n_frames is None:
+            n_frames = T_all - 4 - t0
+        tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+        out = torch.empty((n_frames * len(tile_yx), FEATURES), dtype=torch.float32, device=self.device)
+        assert frames.is_contiguous() and frames.dtype == torch.float32 and frames.device == self.device
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_cnn_features_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,
+                                                         tile_yx.ctypes.data, len(tile_yx), out.data_ptr(), _stream()),
+                       'axt_cnn_features_frames')
+        return out
 
     def front_frames(self, frames, tile_yx, t0, n_frames, item0):
         """Conv blocks 0-5 of detection frames t0 .. t0+n_frames-1 into the detector's batch buffer from item `item0`

@@ -228,6 +228,8 @@ class Timelapse:
         from . import hotpath as hp
         self.make_resident()
         occ = hp.tile_occupancy_bytes(self.frames)
+        # this object holds one rank's block of frames (what reads whole timelapses, training.fine_tune_head, refuses it)
+        self.frame_sharded = dist.is_initialized() and dist.get_world_size(group) > 1
         if dist.is_initialized() and dist.get_world_size(group) > 1:
             if dist.get_backend(group) == 'gloo':
                 occ_h = occ.cpu()

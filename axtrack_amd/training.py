@@ -1,0 +1,262 @@
+"""Fine-tuning of the detector's linear head on labelled frames.
+
+The convolutional trunk stays frozen: its output per (frame, tile) item -- what the first linear layer reads -- is computed
+once by the inference kernels (Detector.features_frames), and an epoch is nothing but head steps on that table: forward
+(model.py:105-117), YOLO_AXTrack_loss (loss.py:18-68), backward and torch.optim.Adam with L2 weight decay
+(core_functionality.py:81), all in csrc/train.hip. The epoch loop restates one_epoch / run_epoch
+(core_functionality.py:109-165) without what cached features rule out (augmentation, the prepare_data resampling loop) and
+without the every-tenth-epoch metrics (call get_detection_metrics with a Detector built from the returned state dict)."""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .hotpath import S, CELLS, _require_gpu, _stream
+
+COMPONENTS = ('total_no_object_loss', 'total_object_loss', 'total_xy_anchors_loss', 'total_summed_loss',
+              'total_pos_labels_rate')
+FC_KEYS = ('fcs.1.weight', 'fcs.1.bias', 'fcs.3.weight', 'fcs.3.bias', 'fcs.5.weight', 'fcs.5.bias')
+# deployed_model/params.txt: what a key missing from `parameters` takes
+TRAIN_DEFAULTS = dict(LR=0.0005, WEIGHT_DECAY=0.0005, LR_DECAYRATE=15, L_OBJECT=49.5, L_COORD_ANCHOR=49.5, L_NOBJECT=1,
+                      BATCH_SIZE=32, SHUFFLE=True, DROP_LAST=False)
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8          # torch.optim.Adam's defaults, which the reference leaves alone
+
+
+def label_arrays(labels):
+    """labels in the format AxonDetections.set_groundtruth takes -- per detection frame (x, y) or (x, y, ids) -> i32
+    [F, cap] x, y (unused slots -1) and i32 [F] counts. Negative coordinates mean "no label" (the reference's fillna(-1))."""
+    cap = max([len(l[0]) for l in labels] + [1])
+    lx = np.full((len(labels), cap), -1, np.int32)
+    ly = np.full((len(labels), cap), -1, np.int32)
+    cnt = np.zeros(len(labels), np.int32)
+    for t, l in enumerate(labels):
+        x, y = np.asarray(l[0], np.int64), np.asarray(l[1], np.int64)
+        if len(x) != len(y):
+            raise ValueError(f'frame {t}: {len(x)} x anchors and {len(y)} y anchors')
+        lx[t, :len(x)] = x
+        ly[t, :len(y)] = y
+        cnt[t] = len(x)
+    return lx, ly, cnt
+
+
+def yolo_targets(labels, tile_yx, device='cuda:0'):
+    """Timelapse.construct_tiles (target half, :513-548) + tiled_target2yolo_format (:451-490) for the kept tiles:
+    -> f32 [F, n_tiles, 12, 12, 4] on the GPU, dim 2 the x cell, dim 3 the y cell, last (1, x_in_cell, y_in_cell, label
+    index). `labels` may also be the (lx, ly, count) arrays of label_arrays()."""
+    _require_gpu()
+    if isinstance(labels, tuple) and len(labels) == 3 and getattr(labels[2], 'ndim', 0) == 1 and np.ndim(labels[0]) == 2:
+        lx, ly, cnt = (np.ascontiguousarray(a, np.int32) for a in labels)
+    else:
+        lx, ly, cnt = label_arrays(labels)
+    dev = torch.device(device)
+    tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+    F, cap = lx.shape
+    out = torch.empty((F, len(tile_yx), S, S, 4), dtype=torch.float32, device=dev)
+    d_lx, d_ly, d_cnt = (torch.from_numpy(a).to(dev) for a in (lx, ly, cnt))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().axt_yolo_targets(d_lx.data_ptr(), d_ly.data_ptr(), d_cnt.data_ptr(), F, cap,
+                                                tile_yx.ctypes.data, len(tile_yx), out.data_ptr(), _stream()),
+                   'axt_yolo_targets')
+    return out
+
+
+def learning_rate(lr, decayrate, epoch):
+    """LR * e^(-sqrt(E) / LR_DECAYRATE) (the LambdaLR of core_functionality.py:83-87), LR if the rate is falsy."""
+    return float(lr * np.e ** ((-1 / decayrate) * np.sqrt(epoch))) if decayrate else float(lr)
+
+
+def epoch_batches(n_items, batch_size, shuffle, drop_last, rng):
+    """The index batches of one epoch as the reference's DataLoader forms them (core_functionality.py:99-107): a
+    permutation drawn from `rng` when shuffling, batches of batch_size, the last smaller one kept unless drop_last."""
+    order = rng.permutation(n_items) if shuffle else np.arange(n_items)
+    batches = [order[i:i + batch_size] for i in range(0, n_items, batch_size)]
+    if drop_last and batches and len(batches[-1]) < batch_size:
+        batches.pop()
+    return [np.ascontiguousarray(b, np.int32) for b in batches]
+
+
+def _np32(v):
+    v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    return np.ascontiguousarray(v, np.float32)
+
+
+class HeadTrainer:
+    """Device-resident fcs.1/3/5 with their Adam moments (axt_head_trainer). forward / loss / step work on batches picked
+    by index from a feature table [n_items, K0] and a target table [n_items, 12, 12, 4] that stay on the GPU."""
+
+    def __init__(self, state_dict, parameters=None, max_batch=64, device='cuda:0'):
+        _require_gpu()
+        self.device = torch.device(device)
+        self.max_batch = int(max_batch)
+        self.P = dict(TRAIN_DEFAULTS)
+        self.P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
+        self._sd = state_dict
+        for k in FC_KEYS:
+            if k not in state_dict:
+                raise KeyError(f'state_dict lacks {k}')
+        w = [_np32(state_dict[k]) for k in FC_KEYS]
+        self.dims = (w[0].shape[1], w[0].shape[0], w[2].shape[0], w[4].shape[0])
+        if w[2].shape[1] != self.dims[1] or w[4].shape[1] != self.dims[2] or any(
+                w[2 * i + 1].shape != (self.dims[i + 1],) for i in range(3)):
+            raise ValueError(f'inconsistent head shapes: {[a.shape for a in w]}')
+        self._lib = _lib.load()
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_create(*self.dims, *[a.ctypes.data for a in w], self.max_batch,
+                                                         ctypes.byref(handle)), 'axt_head_trainer_create')
+        self._h = handle
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self._lib.axt_head_trainer_destroy(h)
+
+    @property
+    def device_bytes(self):
+        return int(self._lib.axt_head_trainer_device_bytes(self._h))
+
+    def _index(self, index, n):
+        """Batch rows as a device i32 tensor, checked against the table's n rows (on the host where the index is there)."""
+        if index is None:
+            index = np.arange(n)
+        if isinstance(index, torch.Tensor):
+            index = index.to(self.device, torch.int32).contiguous()
+            bad = bool(((index < 0) | (index >= n)).any())
+        else:
+            index = np.ascontiguousarray(index, np.int32)
+            bad = bool(((index < 0) | (index >= n)).any())
+            index = torch.from_numpy(index).to(self.device)
+        if bad:
+            raise IndexError(f'batch index outside the table of {n} rows')
+        if not 1 <= len(index) <= self.max_batch:
+            raise ValueError(f'a batch of {len(index)} rows; this trainer takes 1..{self.max_batch}')
+        return index
+
+    def _check_table(self, t, width, what):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device and t.dim() >= 2
+                and t[0].numel() == width):
+            raise ValueError(f'{what} must be a contiguous f32 tensor [n, {width}] on {self.device}')
+
+    def forward(self, features, index=None):
+        """features f32 [n_items, K0] on the GPU, index: which rows form the batch (default: all) -> [B, 12, 12, 3]."""
+        self._check_table(features, self.dims[0], 'features')
+        index = self._index(index, features.shape[0])
+        out = torch.empty((len(index), S, S, 3), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_forward(self._h, features.data_ptr(), index.data_ptr(), len(index),
+                                                          out.data_ptr(), _stream()), 'axt_head_trainer_forward')
+        return out
+
+    def loss(self, yolo, targets, index=None, read=True):
+        """YOLO_AXTrack_loss of the batch grids `yolo` [B,12,12,3] against rows `index` of the target table
+        [n_items,12,12,4] -> (components: dict of the reference's five names, or None with read=False; dY [B,12,12,3])."""
+        targets = targets.reshape(-1, S, S, 4)
+        self._check_table(targets, CELLS * 4, 'targets')
+        self._check_table(yolo, CELLS * 3, 'yolo')
+        index = self._index(index, targets.shape[0])
+        if len(index) != yolo.shape[0]:
+            raise ValueError(f'{yolo.shape[0]} grids for {len(index)} targets')
+        dy = torch.empty_like(yolo)
+        comp = np.zeros(5, np.float64)
+        P = self.P
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_loss(self._h, yolo.data_ptr(), targets.data_ptr(), index.data_ptr(),
+                                                       len(index), float(P['L_OBJECT']), float(P['L_NOBJECT']),
+                                                       float(P['L_COORD_ANCHOR']), comp.ctypes.data if read else None,
+                                                       dy.data_ptr(), _stream()), 'axt_head_trainer_loss')
+        return (dict(zip(COMPONENTS, (float(c) for c in comp))) if read else None), dy
+
+    def step(self, features, index, dy, lr=None, eps=ADAM_EPS):
+        """Backward pass of the batch the last forward() ran, and one Adam step (lr: default P['LR']; eps: Adam's, which the
+        reference leaves at torch's default)."""
+        self._check_table(features, self.dims[0], 'features')
+        self._check_table(dy, CELLS * 3, 'dy')
+        index = self._index(index, features.shape[0])
+        if len(index) != dy.shape[0]:
+            raise ValueError(f'{dy.shape[0]} gradients for a batch of {len(index)}')
+        P = self.P
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_step(self._h, features.data_ptr(), index.data_ptr(), len(index),
+                                                       dy.data_ptr(), float(P['LR'] if lr is None else lr), ADAM_BETAS[0],
+                                                       ADAM_BETAS[1], float(eps), float(P['WEIGHT_DECAY']), _stream()),
+                       'axt_head_trainer_step')
+
+    def weights(self):
+        """The six fcs.* tensors as numpy arrays, in FC_KEYS order."""
+        K0, H1, H2, NO = self.dims
+        out = [np.empty(s, np.float32) for s in ((H1, K0), (H1,), (H2, H1), (H2,), (NO, H2), (NO,))]
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_read_weights(self._h, *[a.ctypes.data for a in out]),
+                       'axt_head_trainer_read_weights')
+        return out
+
+    def moments(self, layer):
+        """Adam state of linear layer 0..2: (m of the weights, v of the weights, m of the bias, v of the bias, step count)."""
+        k, n = self.dims[layer], self.dims[layer + 1]
+        out = [np.empty((n, k), np.float32), np.empty((n, k), np.float32), np.empty(n, np.float32), np.empty(n, np.float32)]
+        step = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_read_moments(self._h, layer, *[a.ctypes.data for a in out],
+                                                               ctypes.byref(step)), 'axt_head_trainer_read_moments')
+        return (*out, int(step.value))
+
+    def state_dict(self):
+        """The state dict this trainer was built from with the six fcs.* tensors replaced by the trained ones (numpy f32)."""
+        sd = dict(self._sd)
+        sd.update(zip(FC_KEYS, self.weights()))
+        return sd
+
+
+def save_checkpoint(state_dict, filename):
+    """The reference's checkpoint layout (utils.py:258-264) without optimiser state; setup_inference(weights=filename)
+    and the reference's load_checkpoint read it."""
+    sd = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v))) for k, v in state_dict.items()}
+    torch.save({'state_dict': sd, 'optimizer': None, 'lr_schedular': None}, filename)
+
+
+def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir=None, seed=None):
+    """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
+    one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
+    (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
+    reference's five loss components, each the mean over the epoch's batches. dest_dir: E{epoch:04}.pth checkpoints for
+    the epochs in parameters['MODEL_CHECKPOINTS'] (default: the last one)."""
+    import pandas as pd
+    from .hotpath import Detector
+    if getattr(timelapse, 'frame_sharded', False):
+        raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
+                                  'process on the whole timelapse')
+    if len(labels) != len(timelapse):
+        raise ValueError(f'{len(labels)} label frames for {len(timelapse)} detection frames')
+    P = dict(TRAIN_DEFAULTS)
+    P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
+    if isinstance(model, Detector):
+        detector, sd = model, getattr(model, 'state_dict_source', None)
+        if sd is None:
+            raise ValueError('this Detector does not remember its state dict; pass the state dict instead')
+    else:
+        sd = model.get('state_dict', model)
+        detector = Detector(sd, max_batch=32, device=timelapse.device)
+    timelapse.make_resident()
+    tile_yx = timelapse.tile_yx
+    features = detector.features_frames(timelapse.frames, tile_yx)
+    targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
+    bs = int(P['BATCH_SIZE'])
+    trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
+    rng = np.random.default_rng(seed)
+    checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
+    history = {}
+    for epoch in range(epochs):
+        lr = learning_rate(P['LR'], P['LR_DECAYRATE'], epoch)
+        rows = []
+        for batch in epoch_batches(features.shape[0], bs, P['SHUFFLE'], P['DROP_LAST'], rng):
+            yolo = trainer.forward(features, batch)
+            comp, dy = trainer.loss(yolo, targets, batch)
+            trainer.step(features, batch, dy, lr=lr)
+            rows.append([comp[k] for k in COMPONENTS])
+        history[epoch] = np.mean(np.array(rows, np.float64).reshape(-1, 5), axis=0)
+        if dest_dir is not None and epoch in checkpoints:
+            os.makedirs(dest_dir, exist_ok=True)
+            save_checkpoint(trainer.state_dict(), f'{dest_dir}/E{epoch:04}.pth')
+    return trainer.state_dict(), pd.DataFrame(history, index=list(COMPONENTS))

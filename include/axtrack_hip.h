@@ -99,6 +99,13 @@ int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, 
                            int t0, int n_frames, const int32_t *h_tile_yx, int n_tiles,
                            float *d_yolo, void *stream);
 
+/* The trunk alone, for training the linear head on cached features: the arguments and the chunking of
+ * axt_cnn_forward_frames, stopping after conv block 10. d_feat f32 [n_frames*n_tiles, 40960] in the reference's flatten
+ * order c*256 + h*16 + w (model.py:50-53): exactly the values the forward pass hands its first linear layer, in the
+ * detector's current arithmetic and fused-front setting. Asynchronous. */
+int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
+                            const int32_t *h_tile_yx, int n_tiles, float *d_feat, void *stream);
+
 /* The same forward pass in two calls, for input that arrives in chunks (Timelapse.from_host_u16: the reference's inference()
  * starts from a host Timelapse and construct_tiles() moves it to the device, Timelapse.py:492-566): axt_cnn_front_frames runs
  * conv blocks 0-5 (through the second max-pool) for the (frame, tile) items of frames t0 .. t0+n_frames-1 and leaves their
@@ -539,6 +546,52 @@ int axt_render_frames(const float *d_frames, const uint8_t *d_mask, int64_t mask
                       int H, int W, int ymin, int xmin, int Ho, int Wo, int grid, int bg, const int32_t *d_trail_ptr,
                       const int32_t *d_trail, const uint8_t *d_trail_col, const int32_t *d_prim_ptr,
                       const int32_t *d_prims, const uint8_t *d_tables, uint8_t *d_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fine-tuning of the linear head fcs.1/3/5 on labelled frames with the convolutional trunk frozen
+ * (core_functionality.py:81-165, loss.py:18-68, Timelapse.py:451-548), DESIGN.md 6.8e.
+ *
+ * axt_yolo_targets: labels -> YOLO targets (Timelapse.construct_tiles :513-548 + tiled_target2yolo_format :451-490 for
+ * the kept tiles). d_lx, d_ly i32 [F, cap] whole-frame pixel anchors, d_lcount i32 [F]; negative coordinates mean "no
+ * label". d_target f32 [F, n_tiles, 12, 12, 4]: dim 2 the x cell, dim 3 the y cell, last (1, x_in_cell, y_in_cell,
+ * label index), every other cell zero. A label belongs to tile (ty, tx) iff ty*512 <= y < (ty+1)*512 and likewise x;
+ * labels of tiles that are not listed are dropped. Cell arithmetic in f32 as the reference's (bit-equal); of two labels
+ * in a cell the one with the higher index wins all four channels (one thread per cell scans the labels: no race).
+ *
+ * axt_head_trainer: device-resident master weights ([out,in] row-major f32, state_dict layout), Adam moments m, v (f32,
+ * zero), the step count and the activations of the last forward batch. NOUT = 432, max_batch <= 64.
+ * _forward: d_index i32 [B] (NULL = rows 0..B-1) picks rows of the feature table d_feat [., K0];
+ *   d_yolo [B, NOUT] = (sigma(sigma(X W1^T + b1) W2^T + b2)) W3^T + b3 (model.py:105-117). Split-K, slabs summed in a
+ *   fixed order.
+ * _loss: YOLO_AXTrack_loss.forward on d_yolo [B,432] and rows d_index of the target table d_target [., 12,12,4];
+ *   h_components f64 [5] (NULL: not read back, no synchronisation): total_no_object_loss, total_object_loss,
+ *   total_xy_anchors_loss, total_summed_loss, total_pos_labels_rate, accumulated in f64 in a fixed tree; d_dy f32
+ *   [B,432] (NULL: none) its gradient with respect to d_yolo. Synchronises the stream when h_components is given.
+ * _step: backward pass from d_dy through the activations _forward stashed for this batch (same B), all of it from
+ *   the weights as they stand, then for every weight matrix one kernel that forms g = sum_b dZ[b,n] In[b,k] +
+ *   weight_decay w in ascending b without storing it and updates m, v, w in place as torch.optim.Adam does
+ *   (t = the handle's step count after its increment). Biases likewise. No atomics: byte-identical from run to run.
+ * _read_weights / _read_moments (layer 0..2; any pointer may be NULL): device -> host, synchronous.
+ * ------------------------------------------------------------------------------------------ */
+int axt_yolo_targets(const int32_t *d_lx, const int32_t *d_ly, const int32_t *d_lcount, int F, int cap,
+                     const int32_t *h_tile_yx, int n_tiles, float *d_target, void *stream);
+typedef struct axt_head_trainer axt_head_trainer;
+int axt_head_trainer_create(int K0, int H1, int H2, int NOUT, const float *h_w1, const float *h_b1, const float *h_w2,
+                            const float *h_b2, const float *h_w3, const float *h_b3, int max_batch,
+                            axt_head_trainer **out);
+void axt_head_trainer_destroy(axt_head_trainer *tr);
+size_t axt_head_trainer_device_bytes(const axt_head_trainer *tr);
+int axt_head_trainer_read_weights(const axt_head_trainer *tr, float *h_w1, float *h_b1, float *h_w2, float *h_b2,
+                                  float *h_w3, float *h_b3);
+int axt_head_trainer_read_moments(const axt_head_trainer *tr, int layer, float *h_mw, float *h_vw, float *h_mb,
+                                  float *h_vb, int64_t *step);
+int axt_head_trainer_forward(axt_head_trainer *tr, const float *d_feat, const int32_t *d_index, int B, float *d_yolo,
+                             void *stream);
+int axt_head_trainer_loss(axt_head_trainer *tr, const float *d_yolo, const float *d_target, const int32_t *d_index, int B,
+                          double lambda_obj, double lambda_noobj, double lambda_coord, double *h_components, float *d_dy,
+                          void *stream);
+int axt_head_trainer_step(axt_head_trainer *tr, const float *d_feat, const int32_t *d_index, int B, const float *d_dy,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
 
 /* Integer arc cost used by the flow network (the costs libmot hands its solver at AxonDetections.py:663-690, from
  * observation_model / transition_model, mincostflow_models.py:6-27,67-119): round(cost * 1e6) << 16 | hash16(kind, a, b).
