@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void arcs_open_kernel(
                 if (j < nb) {
                     if (TABLE) {        // masked grid: path lengths were computed by the BFS pass (0 = no arc)
                         d = Dtmp[(((long)t * cap + i) * max_gap + (g - 1)) * cap + j];
-                        if (d <= 0) d = max_dist;
+                        if (d <= 0) d = lim + 1;          // (not max_dist: that can be below the limit)
                     } else {
                         d = path_len_open(xa, ya, x[(long)tb * cap + j], y[(long)tb * cap + j], H, W, max_dist, conn8);
                     }

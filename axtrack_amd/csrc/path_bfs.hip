@@ -959,8 +959,11 @@ int axt_masked_distance_table(const axt_grid *g, const int32_t *d_x, const int32
                     if (tb >= n_frames) continue;
                     const int nb = hc[tb] < cap ? hc[tb] : cap;
                     if (nb == 0) continue;
+                    // "no path" is reported as the search's max_dist: keep that above the limit (the marked targets have
+                    // passed the euclidean gate already)
+                    const int md = max_dist > h_dmax[gp] ? max_dist : h_dmax[gp] + 1;
                     int rc = axt_path_cost_masked(d_x + (size_t)t * cap + i, d_y + (size_t)t * cap + i, 1, d_x + (size_t)tb * cap,
-                                                  d_y + (size_t)tb * cap, nb, g->d_mask, g->H, g->W, max_dist, g->conn8, dex, st, nullptr);
+                                                  d_y + (size_t)tb * cap, nb, g->d_mask, g->H, g->W, md, g->conn8, dex, st, nullptr);
                     if (rc) { (void)hipFree(dex); return rc; }
                     hipLaunchKernelGGL(mask_patch_kernel, dim3((nb + 255) / 256), dim3(256), 0, st,
                                        d_Dtmp + (((size_t)t * cap + i) * max_gap + gp) * cap, (const int *)dex, nb, h_dmax[gp]);
