@@ -11,18 +11,10 @@
 // On an all-ones mask that is |dx|+|dy|+1 (max(|dx|,|dy|)+1) in closed form; masked grids run a
 // breadth-first search per source (path_bfs.hip).
 #include "axt_common.h"
+#include "grid.h"
 
 // every rounding in this file is part of the contract with the CPU restatement: no fused multiply-adds
 #pragma clang fp contract(off)
-
-int axt_path_cost_masked(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_t *d_xb, const int32_t *d_yb,
-                         int nb, const uint8_t *d_mask, int H, int W, int max_dist, int conn8, int32_t *d_D,
-                         hipStream_t st, int32_t *d_cells);
-struct axt_grid;
-extern "C" const uint8_t *axt_grid_mask(const axt_grid *g);
-int axt_masked_distance_table(const axt_grid *g, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
-                              const int32_t *d_src_count, int n_frames, int cap, int max_dist, int max_gap,
-                              const int32_t *h_dmax, const int32_t *d_dmax, int16_t *d_Dtmp, hipStream_t st);
 
 namespace {
 
@@ -278,7 +270,7 @@ int axt_path_cost(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_
     if ((long)na * nb == 0) return AXT_OK;
     AXT_REQUIRE(d_xa && d_ya && d_xb && d_yb && d_D, "null argument");
     hipStream_t st = (hipStream_t)stream;
-    if (grid) return axt_path_cost_masked(d_xa, d_ya, na, d_xb, d_yb, nb, axt_grid_mask(grid), H, W, max_dist, conn8, d_D, st, nullptr);
+    if (grid) return axt_path_cost_masked(d_xa, d_ya, na, d_xb, d_yb, nb, grid->d_mask, H, W, max_dist, conn8, d_D, st, nullptr);
     const long n = (long)na * nb;
     hipLaunchKernelGGL(path_cost_open_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_xa, d_ya, na, d_xb,
                        d_yb, nb, H, W, max_dist, conn8, d_D);
@@ -293,7 +285,7 @@ int axt_path_cells(const int32_t *d_xa, const int32_t *d_ya, int na, const int32
     AXT_REQUIRE(grid, "axt_path_cells: needs a masked grid (on an all-ones mask every monotone staircase is a shortest path)");
     if ((long)na * nb == 0) return AXT_OK;
     AXT_REQUIRE(d_xa && d_ya && d_xb && d_yb && d_D && d_cells, "null argument");
-    return axt_path_cost_masked(d_xa, d_ya, na, d_xb, d_yb, nb, axt_grid_mask(grid), H, W, max_dist, conn8, d_D,
+    return axt_path_cost_masked(d_xa, d_ya, na, d_xb, d_yb, nb, grid->d_mask, H, W, max_dist, conn8, d_D,
                                 (hipStream_t)stream, d_cells);
 }
 

@@ -31,6 +31,22 @@ void axt_set_error(const char *fmt, ...);
 
 static inline int axt_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Stream-ordered scratch that every return path gives back: hipMallocAsync on construction (0 bytes: nothing, p stays
+// NULL), hipFreeAsync on the same stream in the destructor. Check with AXT_CHECK_HIP(buf.err) before use.
+struct AxtScratch {
+    void *p = nullptr;
+    hipStream_t st;
+    hipError_t err = hipSuccess;
+    AxtScratch(hipStream_t stream, size_t bytes) : st(stream)
+    {
+        if (bytes && (err = hipMallocAsync(&p, bytes, st)) != hipSuccess) p = nullptr;
+    }
+    ~AxtScratch() { if (p) (void)hipFreeAsync(p, st); }
+    AxtScratch(const AxtScratch &) = delete;
+    AxtScratch &operator=(const AxtScratch &) = delete;
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
 // Launch attributes (hipFuncSetAttribute) and occupancy answers belong to the CURRENT device, not to the process: a
 // second device in one process (Detector(device='cuda:1')) must get its own. One of these per launcher remembers, per
 // device index, that the launcher's kernels are set up there (a bit per device; devices beyond 63 are set up on every

@@ -15,6 +15,7 @@
 // than reading 8 bytes. Costs are the same 64-bit integers as the flow network's (axt_arc_cost_int), so the
 // optimum is unique and any exact LSAP solver (e.g. SciPy's linear_sum_assignment) returns the same matching.
 #include "axt_common.h"
+#include "grid.h"
 
 #include <type_traits>
 
@@ -562,17 +563,10 @@ __global__ void fill2_int_kernel(int *p, int *q, long n, int v)
 
 }  // namespace
 
-int axt_frame_offsets(const int32_t *d_count, int n_frames, int cap, int32_t *d_off, hipStream_t st);
-
 // Pass 1 / pass 2 for the source frames [t_begin, t_end): links into d_pred = pred1 | pred2, each i32 [n_frames*cap]
 // (predecessor index in frame t-1 / t-2, or -1). Frame-sharded runs give every rank its own range and combine the
 // arrays with one element-wise MAX all-reduce (entries not owned stay -1; the one redundant boundary pair is
 // deterministic, so equal on both ranks). d_work i32 [2*n_frames*cap + n_frames + 1].
-struct axt_grid;
-int axt_masked_distance_table(const axt_grid *g, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
-                              const int32_t *d_src_count, int n_frames, int cap, int max_dist, int max_gap,
-                              const int32_t *h_dmax, const int32_t *d_dmax, int16_t *d_Dtmp, hipStream_t st);
-
 namespace {
 __global__ void range_count_kernel(const int *__restrict__ count, int *__restrict__ out, int n, int a, int b)
 {
@@ -619,22 +613,24 @@ static int hungarian_pairs_impl(const int32_t *d_x, const int32_t *d_y, const in
     const int e1 = (max_gap == 2 ? t_end + 1 : t_end) < n_frames - 1 ? (max_gap == 2 ? t_end + 1 : t_end) : n_frames - 1;
     // masked grid: the path lengths of the source frames' detections to the next max_gap frames, from the searches of the
     // arc builder (path_bfs.hip), read by the pair kernels instead of the closed form
-    short *dtab = nullptr;
-    int *aux = nullptr;
-    if (grid && !d_ctab && e1 > t_begin) {
-        AXT_CHECK_HIP(hipMallocAsync((void **)&dtab, sizeof(short) * (size_t)n_frames * cap * max_gap * cap, st));
-        AXT_CHECK_HIP(hipMallocAsync((void **)&aux, sizeof(int) * ((size_t)n_frames + max_gap), st));
-        int *src_count = aux, *dmax_dev = aux + n_frames;
+    const bool need_table = grid && !d_ctab && e1 > t_begin;
+    AxtScratch dtab_buf(st, need_table ? sizeof(short) * (size_t)n_frames * cap * max_gap * cap : 0);
+    AxtScratch aux(st, need_table ? sizeof(int) * ((size_t)n_frames + max_gap) : 0);
+    AXT_CHECK_HIP(dtab_buf.err);
+    AXT_CHECK_HIP(aux.err);
+    const short *dtab = dtab_buf.as<short>();
+    if (need_table) {
+        int *src_count = aux.as<int>(), *dmax_dev = src_count + n_frames;
         hipLaunchKernelGGL(range_count_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, st, d_count, src_count, n_frames, t_begin, e1);
         AXT_LAUNCH_CHECK();
         AXT_CHECK_HIP(hipMemcpyAsync(dmax_dev, h_dmax, sizeof(int) * max_gap, hipMemcpyHostToDevice, st));
-        rc = axt_masked_distance_table(grid, d_x, d_y, d_count, src_count, n_frames, cap, max_dist, max_gap, h_dmax, dmax_dev, dtab, st);
+        rc = axt_masked_distance_table(grid, d_x, d_y, d_count, src_count, n_frames, cap, max_dist, max_gap, h_dmax, dmax_dev, dtab_buf.as<short>(), st);
         if (rc) return rc;
     }
     if (e1 > t_begin) {
         hipLaunchKernelGGL((cap <= 192 ? hungarian_pair_kernel<1, 3> : cap <= 576 ? hungarian_pair_kernel<1, 9> : hungarian_pair_kernel<1, 0>), dim3(e1 - t_begin), dim3(cap <= 576 ? 256 : 64), lds, st, d_x, d_y, d_count, frame_off,
                            n_frames, cap, H, W, max_dist, conn8, h_dmax[0], (const long *)d_cost_units, (long)thr_units,
-                           (const int *)nullptr, (const int *)nullptr, succ1, pred1, cdim, t_begin, (const short *)dtab, max_gap,
+                           (const int *)nullptr, (const int *)nullptr, succ1, pred1, cdim, t_begin, dtab, max_gap,
                            (const long *)d_ctab);
         AXT_LAUNCH_CHECK();
     }
@@ -643,12 +639,8 @@ static int hungarian_pairs_impl(const int32_t *d_x, const int32_t *d_y, const in
         hipLaunchKernelGGL((cap <= 192 ? hungarian_pair_kernel<2, 3> : cap <= 576 ? hungarian_pair_kernel<2, 9> : hungarian_pair_kernel<2, 0>), dim3(e2 - t_begin), dim3(cap <= 576 ? 256 : 64), lds, st, d_x, d_y, d_count, frame_off,
                            n_frames, cap, H, W, max_dist, conn8, h_dmax[1],
                            (const long *)d_cost_units + (max_dist + 1), (long)thr_units, (const int *)succ1,
-                           (const int *)pred1, succ2, pred2, cdim, t_begin, (const short *)dtab, max_gap, (const long *)d_ctab);
+                           (const int *)pred1, succ2, pred2, cdim, t_begin, dtab, max_gap, (const long *)d_ctab);
         AXT_LAUNCH_CHECK();
-    }
-    if (dtab) {
-        AXT_CHECK_HIP(hipFreeAsync(dtab, st));
-        AXT_CHECK_HIP(hipFreeAsync(aux, st));
     }
     return AXT_OK;
 }

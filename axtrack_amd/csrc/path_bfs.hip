@@ -1,14 +1,8 @@
-// Path lengths on a masked grid: weights {1 on mask, 65536 off} (reference AxonDetections.py:598), the A* of
-// utils.py:379 (pyastar2d, absent from the reference tree -- convention in DESIGN.md).
+// Path lengths on a masked grid, by the cost convention of grid.h: key order (off-mask cells entered, moves).
 //
 // For one source detection the lengths to ALL targets come from a single-source search, instead of one A* per
-// (source, target) pair as the reference does (AxonDetections.py:570-576): one workgroup per source.
-//
-// Definition (identical to the CPU checker's): on the whole grid, find the minimum-cost 4-/8-connected path to
-// each target, cost of a move = weight of the cell moved into.
-// With weights {1, 65536} and fewer than 65536 on-mask moves the cost order equals the lexicographic order of
-// (off-mask cells entered, moves), packed here as the 64-bit key off << 32 | moves (moves can exceed 16 bits in
-// a 1001^2 window). The result is moves + 1 cells, or max_dist ("None")
+// (source, target) pair as the reference does (AxonDetections.py:570-576): one workgroup per source. The definition is
+// identical to the CPU checker's; here the 64-bit key. The result is moves + 1 cells, or max_dist ("None")
 // when that exceeds max_dist, the euclidean gate fails or an end point lies outside the grid.
 //
 // Search: frontier label-correcting (parallel Bellman-Ford over worklists). Every cell of the current frontier
@@ -19,18 +13,15 @@
 // themselves); the arc builder's hot path is the bit-parallel LDS search further down and falls back to this one
 // only for the rare targets that one cannot decide.
 #include "axt_common.h"
+#include "grid.h"
 
-#include <new>
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
 
-struct axt_grid;
-extern "C" void axt_grid_destroy(axt_grid *g);
-
 namespace {
 
-typedef unsigned long long u64;
+typedef axt_u64 u64;
 
 struct Scratch {
     u64 *key;          // [n_src][win_cells]
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(256) void path_sssp_kernel(
     int *stamp = sc.stamp + (long)src * win_cells_cap;
     int *cur = sc.list_a + (long)src * win_cells_cap;
     int *nxt = sc.list_b + (long)src * win_cells_cap;
-    for (long c = tid; c < ncell; c += 256) { key[c] = ~0ull; stamp[c] = -1; }
+    for (long c = tid; c < ncell; c += 256) { key[c] = AXT_KEY64_INF; stamp[c] = -1; }
     __shared__ int n_cur, n_nxt;
     __syncthreads();
     if (tid == 0) {
@@ -74,7 +65,6 @@ __global__ __launch_bounds__(256) void path_sssp_kernel(
     __threadfence_block();
     __syncthreads();
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     // ends when the frontier is empty; keys strictly decrease, so at most ncell rounds can do work
     for (long iter = 0; iter < ncell + 8; ++iter) {
         const int n = n_cur;
@@ -84,10 +74,10 @@ __global__ __launch_bounds__(256) void path_sssp_kernel(
             const u64 k = __hip_atomic_load(&key[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const int cy = c / ww, cx = c - cy * ww;
             for (int d = 0; d < nn; ++d) {
-                const int ny = cy + dy8[d], nx = cx + dx8[d];
+                const int ny = cy + AXT_NB_DY[d], nx = cx + AXT_NB_DX[d];
                 if (ny < 0 || ny >= wh || nx < 0 || nx >= ww) continue;
                 const bool on = mask[(long)(ny + y0) * W + (nx + x0)] == 1;
-                const u64 nk = k + 1ull + (on ? 0ull : (1ull << 32));
+                const u64 nk = k + 1ull + (on ? 0ull : AXT_KEY64_OFF);
                 const int nc = ny * ww + nx;
                 const u64 old = atomicMin(&key[nc], nk);
                 if (nk < old) {
@@ -108,8 +98,8 @@ __global__ __launch_bounds__(256) void path_sssp_kernel(
         const long dx = tx - sx, dy = ty - sy;
         if (tx >= x0 && tx <= x1 && ty >= y0 && ty <= y1 && dx * dx + dy * dy < (long)max_dist * max_dist) {
             const u64 k = key[(long)(ty - y0) * ww + (tx - x0)];
-            if (k != ~0ull) {
-                const u64 moves = k & 0xffffffffull;
+            if (k != AXT_KEY64_INF) {
+                const u64 moves = k & AXT_KEY64_MOVES;
                 if (moves + 1 <= (u64)max_dist) out = (int)moves + 1;
             }
         }
@@ -135,25 +125,19 @@ __global__ __launch_bounds__(64) void path_backtrack_kernel(
     const u64 *key = key_base + (long)src * win_cells_cap;
     int *out = cells + ((long)src * nb + j) * max_dist;
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     int cx = xb[j], cy = yb[j];
     for (int k = d - 1; k >= 0; --k) {
         const long c = (long)cy * W + cx;
         out[k] = (int)c;
         if (k == 0) break;
-        const u64 want = key[c] - (1ull + (mask[c] == 1 ? 0ull : (1ull << 32)));
-        int found = -1;
-        for (int q = 0; q < nn && found < 0; ++q) {
-            const int ny = cy + dy8[q], nx = cx + dx8[q];
-            if (ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
-            if (key[(long)ny * W + nx] == want) found = q;
-        }
+        const u64 want = key[c] - (1ull + (mask[c] == 1 ? 0ull : AXT_KEY64_OFF));
+        const int found = axt_first_neighbour(cy, cx, H, W, nn, [=](int ny, int nx) { return key[(long)ny * W + nx] == want; });
         if (found < 0) {                                   // cannot happen at the fixed point; leave a visible mark
             for (int r = 0; r < k; ++r) out[r] = -1;
             break;
         }
-        cy += dy8[found];
-        cx += dx8[found];
+        cy += AXT_NB_DY[found];
+        cx += AXT_NB_DX[found];
     }
 }
 
@@ -172,11 +156,11 @@ static int path_cost_masked_impl(const int32_t *d_xa, const int32_t *d_ya, int n
     long batch = (long)(8ll << 30) / bytes_per_src;     // <= 8 GiB of scratch
     if (batch < 1) batch = 1;
     if (batch > na) batch = na;
-    unsigned char *raw = nullptr;
-    AXT_CHECK_HIP(hipMallocAsync((void **)&raw, (size_t)(batch * bytes_per_src), st));
+    AxtScratch raw(st, (size_t)(batch * bytes_per_src));
+    AXT_CHECK_HIP(raw.err);
     Scratch sc;
-    sc.key = reinterpret_cast<u64 *>(raw);
-    sc.stamp = reinterpret_cast<int *>(raw + batch * win * 8);
+    sc.key = raw.as<u64>();
+    sc.stamp = reinterpret_cast<int *>(raw.as<unsigned char>() + batch * win * 8);
     sc.list_a = sc.stamp + batch * win;
     sc.list_b = sc.list_a + batch * win;
     for (long s0 = 0; s0 < na; s0 += batch) {
@@ -192,7 +176,6 @@ static int path_cost_masked_impl(const int32_t *d_xa, const int32_t *d_ya, int n
             AXT_LAUNCH_CHECK();
         }
     }
-    AXT_CHECK_HIP(hipFreeAsync(raw, st));
     return AXT_OK;
 }
 
@@ -230,21 +213,6 @@ int axt_path_cells_pairs(const int32_t *d_xa, const int32_t *d_ya, const int32_t
 // step is a 4-/8-neighbour dilation of whole 32-cell words, AND-ed with the mask. One workgroup per source serves
 // the targets of BOTH following frames (gaps 1 and 2).
 // =====================================================================================================================
-struct axt_grid {
-    int H = 0, W = 0, Ww = 0, conn8 = 0;
-    unsigned char *d_mask = nullptr;     // [H][W] 0/1
-    unsigned int *d_bits = nullptr;      // [H][Ww] bit x%32 of word x/32, zero-padded
-    int *d_label = nullptr;              // [H][W] connected-component label >= 1 on the mask, 0 off it
-    // [n_comp][H][W] u8: fewest off-mask cells any path from component `label` has to enter to reach the cell (the
-    // cell itself included when it is off the mask), saturated at 255; NULL when the mask has too many components
-    unsigned char *d_off = nullptr;
-    int n_comp = 0;
-    bool has_fields = false;             // d_off covers every component (trivially so for an empty mask)
-    // [n_comp][4 or 8][H][Ww] bit rows: bit x of row y of direction d is set iff stepping INTO (y,x) from its
-    // neighbour (y+oy[d], x+ox[d]) keeps the off-cell count minimal: d_off[A][(y,x)] == d_off[A][neighbour] + [cell off]
-    unsigned int *d_tight = nullptr;
-};
-
 namespace {
 
 constexpr int BFS_R = 250;                       // moves; cells <= 251
@@ -260,6 +228,67 @@ __device__ __forceinline__ unsigned int dil_h(const unsigned int *row, int w)
 
 constexpr int BFS_THREADS = 1024;      // one workgroup per CU (LDS-bound): many waves hide the LDS latency of the sweeps
 
+// one move of the all-directions front into word w of row r (row = that row of the bitmap): the 4-/8-neighbour dilation
+// (the row's own dil_h stays inside both branches: hoisted, mask_bfs_kernel spills two more VGPRs)
+__device__ __forceinline__ unsigned int dil_word(const unsigned int *row, int r, int w, bool conn8)
+{
+    unsigned int d;
+    if (conn8) {
+        d = dil_h(row, w);
+        if (r > 0) d |= dil_h(row - BFS_WW, w);
+        if (r + 1 < BFS_WH) d |= dil_h(row + BFS_WW, w);
+    } else {
+        d = dil_h(row, w);
+        if (r > 0) d |= row[w - BFS_WW];
+        if (r + 1 < BFS_WH) d |= row[w + BFS_WW];
+    }
+    return d;
+}
+
+// the deepest move any gap's limit allows (dmax counts cells), within the window
+__device__ __forceinline__ int bfs_depth(const int *__restrict__ dmax, int max_gap)
+{
+    int depth = 0;
+    for (int g = 0; g < max_gap; ++g) depth = max(depth, dmax[g] - 1);
+    return min(depth, BFS_R);
+}
+
+// One barrier per move: per-move flags in LDS (three in rotation) carry "some word changed" and "some target is still
+// open" (as of the previous move's checks), so the checks of move s run beside the dilation of move s + 1. Publishes
+// this thread's two flags of move s, and returns the workgroup's: bit 0 some word changed, bit 1 some target is open.
+__device__ __forceinline__ int bfs_step_flags(int (*s_step)[2], int s, int changed, int my_open, int tid)
+{
+    if (changed) s_step[s % 3][0] = 1;
+    if (my_open) s_step[s % 3][1] = 1;
+    __syncthreads();
+    const int both = s_step[s % 3][0] | (s_step[s % 3][1] << 1);
+    if (tid == 0) s_step[(s + 2) % 3][0] = s_step[(s + 2) % 3][1] = 0;      // for the move after the next one
+    return both;
+}
+
+// After move s: the open targets (tpos >= 0) the front has reached are settled at s + 1 cells -- also those the all-off
+// front `off_front` (two-front search only, else NULL) has reached, while s <= tkv. Returns whether one of this thread's
+// targets is still open.
+__device__ __forceinline__ int bfs_settle_targets(const unsigned int *front, const unsigned int *off_front, const short *tkv, int s,
+                                                  int n_targets, int *tpos, short *tres, int tid)
+{
+    int my_open = 0;
+    for (int e = tid; e < n_targets; e += BFS_THREADS) {
+        const int pos = tpos[e];
+        if (pos < 0) continue;
+        const int r = pos / (BFS_WW * 32), c = pos - r * (BFS_WW * 32);
+        const bool by_off = off_front && (off_front[r * BFS_WW + (c >> 5)] >> (c & 31) & 1u) && s <= (int)tkv[e];
+        const bool by_front = front[r * BFS_WW + (c >> 5)] >> (c & 31) & 1u;
+        if (by_off || by_front) {
+            tres[e] = (short)(s + 1);
+            tpos[e] = -1;
+        } else {
+            my_open = 1;
+        }
+    }
+    return my_open;
+}
+
 struct BfsGeo { int wy0, wx0, H, W, Ww, depth, sr, sc, n_targets; };
 
 // Breadth-first search over the tight steps of one component's field (bit rows tg, axt_grid::d_tight), bit-parallel on
@@ -271,8 +300,6 @@ struct BfsGeo { int wy0, wx0, H, W, Ww, depth, sr, sc, n_targets; };
 //                 and, from move best_a + 1 on, the front over the mask in v0/v1 (tight steps of component best_comp,
 //                 seeded with the mask cells next to the all-off front). A target is settled by the all-off front at
 //                 move s iff s <= tkv (see the kernel), else by the other front.
-// One barrier per move: per-move flags in LDS (three in rotation) carry "some word changed" and "some target is still
-// open" (as of the previous move's checks), so the checks of move s run beside the dilation of move s + 1.
 template <int NDIR>
 __device__ __forceinline__ void bfs_owned(bool off, unsigned int *c0, unsigned int *c1, unsigned int *v0, unsigned int *v1,
                                           const unsigned int *__restrict__ tg, const unsigned int *__restrict__ bits,
@@ -281,7 +308,6 @@ __device__ __forceinline__ void bfs_owned(bool off, unsigned int *c0, unsigned i
 {
     constexpr int NWORDS = BFS_WH * BFS_WW;
     constexpr int KW = (NWORDS + BFS_THREADS - 1) / BFS_THREADS;           // 9
-    constexpr int oy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, ox8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     unsigned int tw[KW][NDIR], mbk[KW], okk[KW];
     const long dstride = (long)G.H * G.Ww;
 #pragma unroll
@@ -314,14 +340,7 @@ __device__ __forceinline__ void bfs_owned(bool off, unsigned int *c0, unsigned i
             unsigned int d_off_front = 0u;
             if (off) {
                 const unsigned int *row = oc + r * BFS_WW;
-                unsigned int d = dil_h(row, w);
-                if (NDIR == 8) {
-                    if (r > 0) d |= dil_h(row - BFS_WW, w);
-                    if (r + 1 < BFS_WH) d |= dil_h(row + BFS_WW, w);
-                } else {
-                    if (r > 0) d |= row[w - BFS_WW];
-                    if (r + 1 < BFS_WH) d |= row[w + BFS_WW];
-                }
+                const unsigned int d = dil_word(row, r, w, NDIR == 8);
                 const unsigned int vo = row[w] | (d & okk[k]);
                 on[e] = vo;
                 changed |= (vo != row[w]);
@@ -334,13 +353,13 @@ __device__ __forceinline__ void bfs_owned(bool off, unsigned int *c0, unsigned i
             } else if (!off || (best_comp > 0 && s > best_a + 1)) {
 #pragma unroll
                 for (int d = 0; d < NDIR; ++d) {
-                    const int rp = r + oy8[d];
+                    const int rp = r + AXT_NB_DY[d];
                     if (rp < 0 || rp >= BFS_WH) continue;
                     const unsigned int *prow = fc + rp * BFS_WW;
                     const unsigned int p0 = prow[w];
                     unsigned int from;
-                    if (ox8[d] < 0) from = (p0 << 1) | (w > 0 ? prow[w - 1] >> 31 : 0u);
-                    else if (ox8[d] > 0) from = (p0 >> 1) | (w + 1 < BFS_WW ? prow[w + 1] << 31 : 0u);
+                    if (AXT_NB_DX[d] < 0) from = (p0 << 1) | (w > 0 ? prow[w - 1] >> 31 : 0u);
+                    else if (AXT_NB_DX[d] > 0) from = (p0 >> 1) | (w + 1 < BFS_WW ? prow[w + 1] << 31 : 0u);
                     else from = p0;
                     vv |= from & tw[k][d];
                 }
@@ -348,29 +367,54 @@ __device__ __forceinline__ void bfs_owned(bool off, unsigned int *c0, unsigned i
             fn[e] = vv;
             changed |= (vv != old);
         }
-        if (changed) s_step[s % 3][0] = 1;
-        if (my_open) s_step[s % 3][1] = 1;
-        __syncthreads();
-        const int both = s_step[s % 3][0] | (s_step[s % 3][1] << 1);
-        if (tid == 0) s_step[(s + 2) % 3][0] = s_step[(s + 2) % 3][1] = 0;      // for the move after the next one
+        const int both = bfs_step_flags(s_step, s, changed, my_open, tid);
         if (!(both & 2)) break;                                        // every target was settled by the previous move
-        my_open = 0;
-        for (int e = tid; e < G.n_targets; e += BFS_THREADS) {
-            const int pos = tpos[e];
-            if (pos < 0) continue;
-            const int r = pos / (BFS_WW * 32), c = pos - r * (BFS_WW * 32);
-            const bool by_off = off && (on[r * BFS_WW + (c >> 5)] >> (c & 31) & 1u) && s <= (int)tkv[e];
-            const bool by_front = fn[r * BFS_WW + (c >> 5)] >> (c & 31) & 1u;
-            if (by_off || by_front) {
-                tres[e] = (short)(s + 1);
-                tpos[e] = -1;
-            } else {
-                my_open = 1;
-            }
-        }
+        my_open = bfs_settle_targets(fn, off ? on : nullptr, tkv, s, G.n_targets, tpos, tres, tid);
         unsigned int *sw = fc; fc = fn; fn = sw;
         sw = oc; oc = on; on = sw;
         if (!(both & 1)) break;                                        // no front moved
+    }
+}
+
+// the end of either search: the lengths within their gap's limit go to the source's rows of Dtmp, longer ones are no arc
+__device__ __forceinline__ void bfs_write_out(const short *tres, const int *__restrict__ dmax, int max_gap, int cap,
+                                              short *__restrict__ drow, int tid)
+{
+    __syncthreads();
+    for (int e = tid; e < max_gap * cap; e += BFS_THREADS) {
+        const int g = e / cap;
+        short r = tres[e];
+        if (r > 0 && r > dmax[g]) r = 0;
+        drow[e] = r;
+    }
+}
+
+// Breadth-first search over the mask M from the front seeded in A (ping-pong with B), one dilation per move, over the
+// bounding box the front can have reached.
+__device__ __forceinline__ void bfs_plain(unsigned int *cur, unsigned int *nxt, const unsigned int *M, int conn8, int depth, int sr,
+                                          int sc, int n_targets, int *tpos, short *tres, int (*s_step)[2], int tid)
+{
+    int my_open = 0;
+    for (int e = tid; e < n_targets; e += BFS_THREADS) my_open |= (tpos[e] >= 0);
+    for (int s = 1; s <= depth; ++s) {
+        // after s moves only the cells within s of the source can be set: rows sr-s..sr+s, words of columns sc-s..sc+s
+        const int rlo = max(0, sr - s), rhi = min(BFS_WH - 1, sr + s);
+        const int wlo = max(0, (sc - s) >> 5), whi = min(BFS_WW - 1, (sc + s) >> 5), nw = whi - wlo + 1;
+        int changed = 0;
+        const float inv_nw = 1.0f / (float)nw;             // e < 9018, nw <= 18: (e + 0.5) * inv_nw truncates to e / nw exactly
+        for (int e = tid; e < (rhi - rlo + 1) * nw; e += BFS_THREADS) {
+            const int rr = (int)(((float)e + 0.5f) * inv_nw);
+            const int r = rlo + rr, w = wlo + (e - rr * nw);
+            const unsigned int *row = cur + r * BFS_WW;
+            const unsigned int v = dil_word(row, r, w, conn8) & M[r * BFS_WW + w];
+            nxt[r * BFS_WW + w] = v;
+            changed |= (v != row[w]);
+        }
+        const int both = bfs_step_flags(s_step, s, changed, my_open, tid);
+        if (!(both & 2)) break;                                        // every target was settled by the previous move
+        my_open = bfs_settle_targets(nxt, nullptr, nullptr, s, n_targets, tpos, tres, tid);
+        unsigned int *sw = cur; cur = nxt; nxt = sw;
+        if (!(both & 1)) break;                                        // the front did not move
     }
 }
 
@@ -399,9 +443,7 @@ __global__ __launch_bounds__(BFS_THREADS) void mask_bfs_kernel(
     short *drow = Dtmp + ((long)t * cap + i) * max_gap * cap;
     const bool s_in = sx >= 0 && sx < W && sy >= 0 && sy < H;
     const int wy0 = sy - BFS_R, wx0 = ((sx - BFS_R) >> 5) << 5;     // window origin; columns word-aligned (floor)
-    int depth = 0;
-    for (int g = 0; g < max_gap; ++g) depth = max(depth, dmax[g] - 1);
-    depth = min(depth, BFS_R);
+    const int depth = bfs_depth(dmax, max_gap);
     // A source ON the mask (component A) knows the fewest off-mask cells k(c) = d_off[A][c] of every cell, and the
     // minimum-cost paths are exactly the paths along which k grows by [cell off the mask] at every step ("tight"
     // steps: a prefix of an optimal path is optimal). Their fewest moves is a plain breadth-first search over tight
@@ -436,17 +478,14 @@ __global__ __launch_bounds__(BFS_THREADS) void mask_bfs_kernel(
     const unsigned int *tg = tight_mode ? tight + (long)(ls_src - 1) * ndir * H * Ww
                              : (off_mode && best_comp > 0) ? tight + (long)(best_comp - 1) * ndir * H * Ww : nullptr;
 
-    // ---- source labels
+    // ---- source labels: its own, or off the mask those of its neighbours
     if (tid == 0) {
         int n = 0;
         if (s_in) {
-            const int ls = label[(long)sy * W + sx];
-            if (ls) s_labels[n++] = ls;
+            if (ls_src) s_labels[n++] = ls_src;
             else {
-                const int nn = conn8 ? 8 : 4;
-                const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
-                for (int d = 0; d < nn; ++d) {
-                    const int ny = sy + dy8[d], nx = sx + dx8[d];
+                for (int d = 0; d < ndir; ++d) {
+                    const int ny = sy + AXT_NB_DY[d], nx = sx + AXT_NB_DX[d];
                     if (ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
                     const int l = label[(long)ny * W + nx];
                     bool seen = l == 0;
@@ -522,72 +561,11 @@ __global__ __launch_bounds__(BFS_THREADS) void mask_bfs_kernel(
         const BfsGeo geo{wy0, wx0, H, W, Ww, depth, sr, sc, max_gap * cap};
         if (conn8) bfs_owned<8>(off_mode, A, Bm, M, V2, tg, bits, geo, tpos, tres, tkv, s_step, best_comp, best_a, tid);
         else bfs_owned<4>(off_mode, A, Bm, M, V2, tg, bits, geo, tpos, tres, tkv, s_step, best_comp, best_a, tid);
-        __syncthreads();
-        for (int e = tid; e < max_gap * cap; e += BFS_THREADS) {
-            const int g = e / cap;
-            short r = tres[e];
-            if (r > 0 && r > dmax[g]) r = 0;
-            drow[e] = r;
-        }
-        return;
+        bfs_write_out(tres, dmax, max_gap, cap, drow, tid);
+        return;                      // (falling through to the write-out below costs two more spilled VGPRs: DESIGN.md 6.6)
     }
-
-    // ---- breadth-first search, one dilation per move
-    unsigned int *cur = A, *nxt = Bm;
-    int my_open = 0;                                                   // (one barrier per move, as above)
-    for (int e = tid; e < max_gap * cap; e += BFS_THREADS) my_open |= (tpos[e] >= 0);
-    for (int s = 1; s <= depth; ++s) {
-        // after s moves only the cells within s of the source can be set: rows sr-s..sr+s, words of columns sc-s..sc+s
-        const int rlo = max(0, sr - s), rhi = min(BFS_WH - 1, sr + s);
-        const int wlo = max(0, (sc - s) >> 5), whi = min(BFS_WW - 1, (sc + s) >> 5), nw = whi - wlo + 1;
-        int changed = 0;
-        const float inv_nw = 1.0f / (float)nw;             // e < 9018, nw <= 18: (e + 0.5) * inv_nw truncates to e / nw exactly
-        for (int e = tid; e < (rhi - rlo + 1) * nw; e += BFS_THREADS) {
-            const int rr = (int)(((float)e + 0.5f) * inv_nw);
-            const int r = rlo + rr, w = wlo + (e - rr * nw);
-            const unsigned int *row = cur + r * BFS_WW;
-            unsigned int v;
-            if (conn8) {
-                v = dil_h(row, w);
-                if (r > 0) v |= dil_h(row - BFS_WW, w);
-                if (r + 1 < BFS_WH) v |= dil_h(row + BFS_WW, w);
-            } else {
-                v = dil_h(row, w);
-                if (r > 0) v |= row[w - BFS_WW];
-                if (r + 1 < BFS_WH) v |= row[w + BFS_WW];
-            }
-            v &= M[r * BFS_WW + w];
-            nxt[r * BFS_WW + w] = v;
-            changed |= (v != row[w]);
-        }
-        if (changed) s_step[s % 3][0] = 1;
-        if (my_open) s_step[s % 3][1] = 1;
-        __syncthreads();
-        const int both = s_step[s % 3][0] | (s_step[s % 3][1] << 1);
-        if (tid == 0) s_step[(s + 2) % 3][0] = s_step[(s + 2) % 3][1] = 0;
-        if (!(both & 2)) break;
-        my_open = 0;
-        for (int e = tid; e < max_gap * cap; e += BFS_THREADS) {
-            const int pos = tpos[e];
-            if (pos < 0) continue;
-            const int r = pos / (BFS_WW * 32), c = pos - r * (BFS_WW * 32);
-            if (nxt[r * BFS_WW + (c >> 5)] >> (c & 31) & 1u) {
-                tres[e] = (short)(s + 1);
-                tpos[e] = -1;
-            } else {
-                my_open = 1;
-            }
-        }
-        unsigned int *sw = cur; cur = nxt; nxt = sw;
-        if (!(both & 1)) break;
-    }
-    __syncthreads();
-    for (int e = tid; e < max_gap * cap; e += BFS_THREADS) {
-        const int g = e / cap;
-        short r = tres[e];
-        if (r > 0 && r > dmax[g]) r = 0;
-        drow[e] = r;
-    }
+    bfs_plain(A, Bm, M, conn8, depth, sr, sc, max_gap * cap, tpos, tres, s_step, tid);
+    bfs_write_out(tres, dmax, max_gap, cap, drow, tid);
 }
 
 // ---- targets in another component of the mask -----------------------------------------------------------------------
@@ -620,17 +598,14 @@ __global__ __launch_bounds__(256) void mask_cross_kernel(
     __shared__ int n_cur, n_nxt, overflow;
     __shared__ int off_s[64];                              // d_off[A][S] - [S off the mask] of the current source
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
-    int depth = 0;
-    for (int g = 0; g < max_gap; ++g) depth = max(depth, dmax[g] - 1);
-    depth = min(depth, BFS_R);
+    const int depth = bfs_depth(dmax, max_gap);
     for (int task = blockIdx.x; task < n_tasks; task += gridDim.x) {
         const int src = tasks[task], t = src / cap;
         const int sx = x[src], sy = y[src];
         const int wy0 = sy - BFS_R, wx0 = sx - BFS_R;
         short *drow = Dtmp + (long)src * max_gap * cap;
         __syncthreads();                                   // the previous task's readers are done with key[]
-        for (long c = tid; c < CROSS_CELLS; c += 256) key[c] = 0xffffffffu;
+        for (long c = tid; c < CROSS_CELLS; c += 256) key[c] = AXT_KEY32_INF;
         __syncthreads();
         if (tid == 0) {
             const int s = BFS_R * CROSS_W + BFS_R;
@@ -650,10 +625,10 @@ __global__ __launch_bounds__(256) void mask_cross_kernel(
             for (int e = tid; e < n; e += 256) {
                 const int c = fa[e];
                 const unsigned int k = __hip_atomic_load(&key[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if ((int)(k & 0xffffu) >= depth) continue;                       // at the move limit: not expanded
+                if ((int)(k & AXT_KEY32_MOVES) >= depth) continue;                       // at the move limit: not expanded
                 const int cy = c / CROSS_W, cx = c - cy * CROSS_W;
                 for (int d = 0; d < nn; ++d) {
-                    const int ny = cy + dy8[d], nx = cx + dx8[d];
+                    const int ny = cy + AXT_NB_DY[d], nx = cx + AXT_NB_DX[d];
                     if (ny < 0 || ny >= CROSS_W || nx < 0 || nx >= CROSS_W) continue;
                     const int gy = wy0 + ny, gx = wx0 + nx;
                     if (gy < 0 || gy >= H || gx < 0 || gx >= W) continue;
@@ -661,7 +636,7 @@ __global__ __launch_bounds__(256) void mask_cross_kernel(
                     // most relaxations fail (a cell is improved once or twice but reached from every side): look first
                     const unsigned int seen = __hip_atomic_load(&key[nc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if ((seen >> 16) == 0u && seen <= k + 1u) continue;                  // cannot be beaten, whatever the cell is
-                    const unsigned int nk = k + 1u + (mask[(long)gy * W + gx] == 1 ? 0u : 0x10000u);
+                    const unsigned int nk = k + 1u + (mask[(long)gy * W + gx] == 1 ? 0u : AXT_KEY32_OFF);
                     if (seen <= nk) continue;
                     const unsigned int old = atomicMin(&key[nc], nk);
                     if (nk < old) {                  // a cell improved twice in one round is listed twice: harmless
@@ -688,7 +663,7 @@ __global__ __launch_bounds__(256) void mask_cross_kernel(
             for (int a = 0; a < n_comp; ++a) ka = min(ka, off_s[a] + (int)off_field[((long)a * H + ty) * W + tx]);
             const unsigned int k = key[(long)(ty - wy0) * CROSS_W + (tx - wx0)];
             short res = 0;
-            if (k != 0xffffffffu && (int)(k >> 16) <= ka && (int)(k & 0xffffu) + 1 <= dmax[g]) res = (short)((k & 0xffffu) + 1);
+            if (k != AXT_KEY32_INF && (int)(k >> 16) <= ka && (int)(k & AXT_KEY32_MOVES) + 1 <= dmax[g]) res = (short)((k & AXT_KEY32_MOVES) + 1);
             drow[e] = res;
         }
     }
@@ -720,154 +695,29 @@ __global__ void mask_patch_kernel(short *__restrict__ drow, const int *__restric
 
 }  // namespace
 
-extern "C" int axt_grid_create(const uint8_t *h_mask, int H, int W, int conn8, axt_grid **out)
+// Which sources still carry a -1 in their rows of Dtmp: `open` = their t * cap + i in ascending order (flag kernel, count,
+// one read-back of the flags), `hc` = the frames' detection counts. Synchronises the stream. d_flags i32 [n_frames*cap + 1].
+static int sources_left_open(const int16_t *d_Dtmp, const int32_t *d_count, const int32_t *d_src_count, int n_frames, int cap,
+                             int max_gap, int *d_flags, hipStream_t st, std::vector<int> &open, std::vector<int> &hc)
 {
-    AXT_REQUIRE(h_mask && out && H > 0 && W > 0, "bad argument");
-    axt_grid *g = new (std::nothrow) axt_grid();
-    if (!g) return AXT_ENOMEM;
-    g->H = H; g->W = W; g->Ww = (W + 31) / 32; g->conn8 = conn8 ? 1 : 0;
-    std::vector<unsigned int> bits((size_t)H * g->Ww, 0u);
-    std::vector<int> label((size_t)H * W, 0);
-    std::vector<unsigned char> m01((size_t)H * W);
-    for (long k = 0; k < (long)H * W; ++k) m01[k] = h_mask[k] == 1;          // AxonDetections.py:598: mask == 1
-    for (int yy = 0; yy < H; ++yy)
-        for (int xx = 0; xx < W; ++xx)
-            if (m01[(size_t)yy * W + xx]) bits[(size_t)yy * g->Ww + (xx >> 5)] |= 1u << (xx & 31);
-    // connected components by flood fill
-    std::vector<int> stack;
-    int next = 0;
-    const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
-    for (long k = 0; k < (long)H * W; ++k) {
-        if (!m01[k] || label[k]) continue;
-        label[k] = ++next;
-        stack.push_back((int)k);
-        while (!stack.empty()) {
-            const int c = stack.back();
-            stack.pop_back();
-            const int cy = c / W, cx = c % W;
-            for (int d = 0; d < nn; ++d) {
-                const int ny = cy + dy8[d], nx = cx + dx8[d];
-                if (ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
-                const int n = ny * W + nx;
-                if (m01[n] && !label[n]) { label[n] = next; stack.push_back(n); }
-            }
-        }
-    }
-    // fewest off-mask cells from every component to every cell (0-1 breadth-first search per component)
-    g->n_comp = next;
-    std::vector<unsigned char> off;
-    constexpr int kMaxComp = 64;
-    if (next >= 1 && next <= kMaxComp && (size_t)next * H * W <= ((size_t)256 << 20)) {
-        off.assign((size_t)next * H * W, 255);
-        std::vector<int> dist((size_t)H * W);
-        std::vector<int> level, later, work;
-        for (int L = 1; L <= next; ++L) {
-            std::fill(dist.begin(), dist.end(), INT32_MAX);
-            level.clear();
-            for (long k = 0; k < (long)H * W; ++k)
-                if (label[k] == L) { dist[k] = 0; level.push_back((int)k); }
-            // Dial's buckets for weights {0, 1}: close the current level over the zero-weight (on-mask) moves, collect
-            // the off-mask cells one level up; 255 levels are all a path of <= 251 cells can use
-            for (int d = 0; d < 255 && !level.empty(); ++d) {
-                work.swap(level);
-                later.clear();
-                while (!work.empty()) {
-                    const int c = work.back();
-                    work.pop_back();
-                    if (dist[c] != d) continue;
-                    const int cy = c / W, cx = c % W;
-                    for (int q = 0; q < nn; ++q) {
-                        const int ny = cy + dy8[q], nx = cx + dx8[q];
-                        if (ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
-                        const int n = ny * W + nx;
-                        const int nd = d + (m01[n] ? 0 : 1);
-                        if (nd < dist[n]) {
-                            dist[n] = nd;
-                            if (nd == d) work.push_back(n); else later.push_back(n);
-                        }
-                    }
-                }
-                level.clear();
-                for (int n : later)
-                    if (dist[n] == d + 1) level.push_back(n);
-            }
-            unsigned char *o = off.data() + (size_t)(L - 1) * H * W;
-            for (long k = 0; k < (long)H * W; ++k)
-                if (dist[k] < 255) o[k] = (unsigned char)dist[k];
-        }
-    }
-    g->has_fields = next == 0 || !off.empty();
-    std::vector<unsigned int> tightv;
-    if (!off.empty()) {
-        const int Ww = g->Ww;
-        const int oy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, ox8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
-        tightv.assign((size_t)next * nn * H * Ww, 0u);
-        for (int L = 0; L < next; ++L) {
-            const unsigned char *o = off.data() + (size_t)L * H * W;
-            for (int d = 0; d < nn; ++d) {
-                unsigned int *tb = tightv.data() + ((size_t)L * nn + d) * H * Ww;
-                for (int yy = 0; yy < H; ++yy) {
-                    const int py = yy + oy8[d];
-                    if (py < 0 || py >= H) continue;
-                    for (int xx = 0; xx < W; ++xx) {
-                        const int px = xx + ox8[d];
-                        if (px < 0 || px >= W) continue;
-                        const int kc = o[(size_t)yy * W + xx], kp = o[(size_t)py * W + px];
-                        if (kc < 255 && kp < 255 && kc == kp + (m01[(size_t)yy * W + xx] ? 0 : 1))
-                            tb[(size_t)yy * Ww + (xx >> 5)] |= 1u << (xx & 31);
-                    }
-                }
-            }
-        }
-    }
-    int rc = AXT_OK;
-    if (!off.empty() && (hipMalloc((void **)&g->d_off, off.size()) != hipSuccess ||
-                         hipMemcpy(g->d_off, off.data(), off.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-        axt_set_error("axt_grid_create: device allocation for the component distance fields failed");
-        axt_grid_destroy(g);
-        return AXT_ENOMEM;
-    }
-    if (!tightv.empty() && (hipMalloc((void **)&g->d_tight, tightv.size() * 4) != hipSuccess ||
-                            hipMemcpy(g->d_tight, tightv.data(), tightv.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
-        axt_set_error("axt_grid_create: device allocation for the tight-step rows failed");
-        axt_grid_destroy(g);
-        return AXT_ENOMEM;
-    }
-    if (hipMalloc((void **)&g->d_mask, (size_t)H * W) != hipSuccess || hipMalloc((void **)&g->d_bits, bits.size() * 4) != hipSuccess ||
-        hipMalloc((void **)&g->d_label, label.size() * 4) != hipSuccess) {
-        axt_set_error("axt_grid_create: device allocation failed");
-        rc = AXT_ENOMEM;
-    } else if (hipMemcpy(g->d_mask, m01.data(), m01.size(), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(g->d_bits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(g->d_label, label.data(), label.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        axt_set_error("axt_grid_create: upload failed");
-        rc = AXT_EHIP;
-    }
-    if (rc) { axt_grid_destroy(g); return rc; }
-    *out = g;
+    int *n_flagged = d_flags + (size_t)n_frames * cap;
+    AXT_CHECK_HIP(hipMemsetAsync(n_flagged, 0, sizeof(int), st));
+    hipLaunchKernelGGL(mask_flag_kernel, dim3(cap, n_frames), dim3(64), 0, st, d_Dtmp, d_src_count, n_frames, cap, max_gap, d_flags,
+                       n_flagged);
+    AXT_LAUNCH_CHECK();
+    int nf = 0;
+    AXT_CHECK_HIP(hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st));
+    AXT_CHECK_HIP(hipStreamSynchronize(st));
+    open.clear();                                 // only now: the caller may have queued an upload from open[] on st
+    if (nf == 0) return AXT_OK;
+    std::vector<int> hf((size_t)n_frames * cap);
+    hc.resize(n_frames);
+    AXT_CHECK_HIP(hipMemcpy(hf.data(), d_flags, hf.size() * 4, hipMemcpyDeviceToHost));
+    AXT_CHECK_HIP(hipMemcpy(hc.data(), d_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+    for (int t = 0; t < n_frames; ++t)
+        for (int i = 0; i < hc[t] && i < cap; ++i)
+            if (hf[(size_t)t * cap + i]) open.push_back(t * cap + i);
     return AXT_OK;
-}
-
-extern "C" void axt_grid_destroy(axt_grid *g)
-{
-    if (!g) return;
-    (void)hipFree(g->d_mask);
-    (void)hipFree(g->d_bits);
-    (void)hipFree(g->d_label);
-    (void)hipFree(g->d_off);
-    (void)hipFree(g->d_tight);
-    delete g;
-}
-
-extern "C" const uint8_t *axt_grid_mask(const axt_grid *g) { return g ? g->d_mask : nullptr; }
-const int32_t *axt_grid_label(const axt_grid *g) { return g ? g->d_label : nullptr; }
-void axt_grid_shape(const axt_grid *g, int *H, int *W) { *H = g ? g->H : 0; *W = g ? g->W : 0; }
-// the component fields d_off [n_comp][H][W] (NULL when the mask has none)
-const uint8_t *axt_grid_off_field(const axt_grid *g, int *n_comp)
-{
-    *n_comp = g ? g->n_comp : 0;
-    return g ? g->d_off : nullptr;
 }
 
 // Fills Dtmp (layout above) for every source detection; exact-search fallback included. Synchronises the stream.
@@ -890,88 +740,59 @@ int axt_masked_distance_table(const axt_grid *g, const int32_t *d_x, const int32
                        g->d_label, g->H, g->W, g->Ww, g->conn8, max_dist, max_gap, d_dmax, d_Dtmp, (const unsigned int *)g->d_tight,
                        (const unsigned char *)g->d_off, g->n_comp, off_mode_ok);
     AXT_LAUNCH_CHECK();
-    int *flags = nullptr, *n_flagged = nullptr;
-    AXT_CHECK_HIP(hipMallocAsync((void **)&flags, sizeof(int) * ((size_t)n_frames * cap + 1), st));
-    n_flagged = flags + (size_t)n_frames * cap;
-    AXT_CHECK_HIP(hipMemsetAsync(n_flagged, 0, sizeof(int), st));
-    hipLaunchKernelGGL(mask_flag_kernel, dim3(cap, n_frames), dim3(64), 0, st, d_Dtmp, d_src_count, n_frames, cap, max_gap, flags,
-                       n_flagged);
-    AXT_LAUNCH_CHECK();
-    int nf = 0;
-    AXT_CHECK_HIP(hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st));
-    AXT_CHECK_HIP(hipStreamSynchronize(st));
-    if (nf > 0) {
-        std::vector<int> hf((size_t)n_frames * cap), hc(n_frames);
-        AXT_CHECK_HIP(hipMemcpy(hf.data(), flags, hf.size() * 4, hipMemcpyDeviceToHost));
-        AXT_CHECK_HIP(hipMemcpy(hc.data(), d_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
-        if (g->has_fields) {
-            // targets in other components / off the mask: windowed search of every flagged source (resolves them all)
-            std::vector<int> tasks;
-            for (int t = 0; t < n_frames; ++t)
-                for (int i = 0; i < hc[t] && i < cap; ++i)
-                    if (hf[(size_t)t * cap + i]) tasks.push_back(t * cap + i);
-            const int n_tasks = (int)tasks.size();
-            if (getenv("AXT_PATH_DEBUG")) fprintf(stderr, "masked arcs: %d sources off the mask or without component fields (windowed search)\n", n_tasks);
-            const int wgs = n_tasks < 512 ? n_tasks : 512;       // two per CU; more only thrash the caches (measured)
-            int *d_tasks = nullptr;
-            unsigned char *scratch = nullptr;
-            AXT_CHECK_HIP(hipMallocAsync((void **)&d_tasks, sizeof(int) * n_tasks, st));
-            AXT_CHECK_HIP(hipMallocAsync((void **)&scratch, (size_t)wgs * CROSS_CELLS * 12, st));
-            AXT_CHECK_HIP(hipMemcpyAsync(d_tasks, tasks.data(), sizeof(int) * n_tasks, hipMemcpyHostToDevice, st));
-            unsigned int *key = reinterpret_cast<unsigned int *>(scratch);
-            int *lists = reinterpret_cast<int *>(scratch + (size_t)wgs * CROSS_CELLS * 4);
-            const bool timed = getenv("AXT_PATH_DEBUG") != nullptr;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (timed) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, st); }
-            hipLaunchKernelGGL(mask_cross_kernel, dim3(wgs), dim3(256), 0, st, (const int *)d_tasks, n_tasks, d_x, d_y, d_count,
-                               n_frames, cap, g->d_mask, (const int *)g->d_label, (const unsigned char *)g->d_off, g->n_comp, g->H, g->W,
-                               g->conn8, max_gap, d_dmax, key, lists, d_Dtmp);
-            AXT_LAUNCH_CHECK();
-            if (timed) {
-                float ms = 0;
-                (void)hipEventRecord(e1, st); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
-                fprintf(stderr, "masked arcs: windowed search of %d sources took %.1f ms\n", n_tasks, ms);
-                (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-            }
-            AXT_CHECK_HIP(hipMemsetAsync(n_flagged, 0, sizeof(int), st));
-            hipLaunchKernelGGL(mask_flag_kernel, dim3(cap, n_frames), dim3(64), 0, st, d_Dtmp, d_src_count, n_frames, cap, max_gap, flags,
-                               n_flagged);
-            AXT_LAUNCH_CHECK();
-            AXT_CHECK_HIP(hipMemcpyAsync(&nf, n_flagged, sizeof(int), hipMemcpyDeviceToHost, st));
-            AXT_CHECK_HIP(hipStreamSynchronize(st));                 // also: tasks[] may go out of scope
-            AXT_CHECK_HIP(hipFreeAsync(d_tasks, st));
-            AXT_CHECK_HIP(hipFreeAsync(scratch, st));
-            if (nf > 0) AXT_CHECK_HIP(hipMemcpy(hf.data(), flags, hf.size() * 4, hipMemcpyDeviceToHost));
+    AxtScratch flags(st, sizeof(int) * ((size_t)n_frames * cap + 1));
+    AXT_CHECK_HIP(flags.err);
+    std::vector<int> open, hc;
+    if (int rc = sources_left_open(d_Dtmp, d_count, d_src_count, n_frames, cap, max_gap, flags.as<int>(), st, open, hc)) return rc;
+    if (!open.empty() && g->has_fields) {
+        // targets in other components / off the mask: windowed search of every flagged source (resolves them all)
+        const int n_tasks = (int)open.size();
+        const bool timed = getenv("AXT_PATH_DEBUG") != nullptr;
+        if (timed) fprintf(stderr, "masked arcs: %d sources off the mask or without component fields (windowed search)\n", n_tasks);
+        const int wgs = n_tasks < 512 ? n_tasks : 512;       // two per CU; more only thrash the caches (measured)
+        AxtScratch d_tasks(st, sizeof(int) * n_tasks), scratch(st, (size_t)wgs * CROSS_CELLS * 12);
+        AXT_CHECK_HIP(d_tasks.err);
+        AXT_CHECK_HIP(scratch.err);
+        AXT_CHECK_HIP(hipMemcpyAsync(d_tasks.p, open.data(), sizeof(int) * n_tasks, hipMemcpyHostToDevice, st));
+        unsigned int *key = scratch.as<unsigned int>();
+        int *lists = reinterpret_cast<int *>(scratch.as<unsigned char>() + (size_t)wgs * CROSS_CELLS * 4);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, st); }
+        hipLaunchKernelGGL(mask_cross_kernel, dim3(wgs), dim3(256), 0, st, (const int *)d_tasks.as<int>(), n_tasks, d_x, d_y, d_count,
+                           n_frames, cap, g->d_mask, (const int *)g->d_label, (const unsigned char *)g->d_off, g->n_comp, g->H, g->W,
+                           g->conn8, max_gap, d_dmax, key, lists, d_Dtmp);
+        AXT_LAUNCH_CHECK();
+        if (timed) {
+            float ms = 0;
+            (void)hipEventRecord(e1, st); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
+            fprintf(stderr, "masked arcs: windowed search of %d sources took %.1f ms\n", n_tasks, ms);
+            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         }
+        // (touches open[], the source of the upload above, only after it has synchronised the stream)
+        if (int rc = sources_left_open(d_Dtmp, d_count, d_src_count, n_frames, cap, max_gap, flags.as<int>(), st, open, hc)) return rc;
     }
-    if (nf > 0) {
-        if (getenv("AXT_PATH_DEBUG")) fprintf(stderr, "masked arcs: %d sources left for the general search\n", nf);
-        std::vector<int> hf((size_t)n_frames * cap), hc(n_frames);
-        AXT_CHECK_HIP(hipMemcpy(hf.data(), flags, hf.size() * 4, hipMemcpyDeviceToHost));
-        AXT_CHECK_HIP(hipMemcpy(hc.data(), d_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
-        int *dex = nullptr;
-        AXT_CHECK_HIP(hipMalloc((void **)&dex, sizeof(int) * cap));
-        for (int t = 0; t < n_frames; ++t)
-            for (int i = 0; i < hc[t] && i < cap; ++i) {
-                if (!hf[(size_t)t * cap + i]) continue;
-                for (int gp = 0; gp < max_gap; ++gp) {
-                    const int tb = t + gp + 1;
-                    if (tb >= n_frames) continue;
-                    const int nb = hc[tb] < cap ? hc[tb] : cap;
-                    if (nb == 0) continue;
-                    // "no path" is reported as the search's max_dist: keep that above the limit (the marked targets have
-                    // passed the euclidean gate already)
-                    const int md = max_dist > h_dmax[gp] ? max_dist : h_dmax[gp] + 1;
-                    int rc = axt_path_cost_masked(d_x + (size_t)t * cap + i, d_y + (size_t)t * cap + i, 1, d_x + (size_t)tb * cap,
-                                                  d_y + (size_t)tb * cap, nb, g->d_mask, g->H, g->W, md, g->conn8, dex, st, nullptr);
-                    if (rc) { (void)hipFree(dex); return rc; }
-                    hipLaunchKernelGGL(mask_patch_kernel, dim3((nb + 255) / 256), dim3(256), 0, st,
-                                       d_Dtmp + (((size_t)t * cap + i) * max_gap + gp) * cap, (const int *)dex, nb, h_dmax[gp]);
-                }
+    if (!open.empty()) {
+        if (getenv("AXT_PATH_DEBUG")) fprintf(stderr, "masked arcs: %d sources left for the general search\n", (int)open.size());
+        AxtScratch dex(st, sizeof(int) * cap);
+        AXT_CHECK_HIP(dex.err);
+        for (const int src : open) {
+            const int t = src / cap;
+            for (int gp = 0; gp < max_gap; ++gp) {
+                const int tb = t + gp + 1;
+                if (tb >= n_frames) continue;
+                const int nb = hc[tb] < cap ? hc[tb] : cap;
+                if (nb == 0) continue;
+                // "no path" is reported as the search's max_dist: keep that above the limit (the marked targets have
+                // passed the euclidean gate already)
+                const int md = max_dist > h_dmax[gp] ? max_dist : h_dmax[gp] + 1;
+                if (int rc = axt_path_cost_masked(d_x + src, d_y + src, 1, d_x + (size_t)tb * cap, d_y + (size_t)tb * cap, nb,
+                                                  g->d_mask, g->H, g->W, md, g->conn8, dex.as<int>(), st, nullptr))
+                    return rc;
+                hipLaunchKernelGGL(mask_patch_kernel, dim3((nb + 255) / 256), dim3(256), 0, st,
+                                   d_Dtmp + ((size_t)src * max_gap + gp) * cap, (const int *)dex.as<int>(), nb, h_dmax[gp]);
             }
+        }
         AXT_CHECK_HIP(hipStreamSynchronize(st));
-        (void)hipFree(dex);
     }
-    AXT_CHECK_HIP(hipFreeAsync(flags, st));
     return AXT_OK;
 }

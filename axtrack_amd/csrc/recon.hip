@@ -43,16 +43,9 @@
 // axt_link_cells: the lengths' prefix sum (cell_ptr), the cells as CSR, and the interpolation anchors of the frames a
 // gap link skips: frame tail+k (k = 1 .. g-1) at cell index (2k(L-1) + g) / (2g) (round half up).
 #include "axt_common.h"
+#include "grid.h"
 
 #include <stdlib.h>
-
-struct axt_grid;
-extern "C" const uint8_t *axt_grid_mask(const axt_grid *g);
-const int32_t *axt_grid_label(const axt_grid *g);
-const uint8_t *axt_grid_off_field(const axt_grid *g, int *n_comp);
-int axt_path_cells_pairs(const int32_t *d_xa, const int32_t *d_ya, const int32_t *d_xb, const int32_t *d_yb, int n,
-                         const uint8_t *d_mask, int H, int W, int max_dist, int conn8, int32_t *d_D, int32_t *d_cells,
-                         hipStream_t st);
 
 namespace {
 
@@ -111,36 +104,12 @@ __global__ __launch_bounds__(LT) void links_find_kernel(const int *__restrict__ 
     if (tid == 0) frame_cnt[f] = total;
 }
 
-// frame_off[0..n] = exclusive prefix sum of cnt[0..n-1] (one workgroup; i64 offsets)
-template <typename T>
-__global__ __launch_bounds__(1024) void scan_kernel(const int *__restrict__ cnt, int n, T *__restrict__ off,
-                                                    int clamp_from)
-{
-    // clamp_from > 0: entries >= clamp_from (or < 0) count as 0 (path lengths: max_dist = no path)
-    __shared__ T s_part[1024];
-    const int tid = threadIdx.x;
-    const long per = (n + 1023) / 1024;
-    const long a = min((long)n, tid * per), b = min((long)n, a + per);
-    T sum = 0;
-    for (long k = a; k < b; ++k) {
-        const int v = cnt[k];
-        sum += (clamp_from > 0 && (v >= clamp_from || v < 0)) ? 0 : (v < 0 ? 0 : v);
-    }
-    s_part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        T run = 0;
-        for (int k = 0; k < 1024; ++k) { const T v = s_part[k]; s_part[k] = run; run += v; }
-        off[n] = run;
-    }
-    __syncthreads();
-    T run = s_part[tid];
-    for (long k = a; k < b; ++k) {
-        off[k] = run;
-        const int v = cnt[k];
-        run += (clamp_from > 0 && (v >= clamp_from || v < 0)) ? 0 : (v < 0 ? 0 : v);
-    }
-}
+// what an entry adds to a prefix sum (axt_scan_kernel): itself; nothing when negative or, with clamp_from > 0, when
+// >= clamp_from (path lengths: max_dist = no path)
+struct ClampedCount {
+    int clamp_from;
+    __device__ int operator()(int v) const { return (v < 0 || (clamp_from > 0 && v >= clamp_from)) ? 0 : v; }
+};
 
 __global__ __launch_bounds__(LT) void links_emit_kernel(const int *__restrict__ count, int cap,
                                                         const int *__restrict__ head, const int *__restrict__ gap,
@@ -263,7 +232,6 @@ __global__ __launch_bounds__(NT) void link_bfs_kernel(const int *__restrict__ li
     __syncthreads();
     const int tr = ty - wy0, tc = tx - wx0;
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     int found = (tr == R && tc == R) ? 0 : -1;
     for (int s = 1; s <= limit && found < 0; ++s) {
         // after s moves only the box of radius s around the source can be reached
@@ -272,9 +240,9 @@ __global__ __launch_bounds__(NT) void link_bfs_kernel(const int *__restrict__ li
         for (int e = tid; e < side * side; e += NT) {
             const int r = lo + e / side, c = lo + e % side;
             if (dist[r * WD + c] != D_UNSEEN) continue;
-            bool hit = false;
+            bool hit = false;                               // (a plain loop: axt_first_neighbour costs a register here)
             for (int q = 0; q < nn && !hit; ++q) {
-                const int rr = r + dy8[q], cc = c + dx8[q];
+                const int rr = r + AXT_NB_DY[q], cc = c + AXT_NB_DX[q];
                 if (rr < 0 || rr >= WD || cc < 0 || cc >= WD) continue;
                 hit = dist[rr * WD + cc] == (unsigned short)(s - 1);
             }
@@ -296,24 +264,21 @@ __global__ __launch_bounds__(NT) void link_bfs_kernel(const int *__restrict__ li
     for (int k = found; k >= 0; --k) {
         out[k] = (wy0 + r) * W + (wx0 + c);
         if (k == 0) break;
-        int q = 0;
-        for (; q < nn; ++q) {
-            const int rr = r + dy8[q], cc = c + dx8[q];
-            if (rr < 0 || rr >= WD || cc < 0 || cc >= WD) continue;
-            if (dist[rr * WD + cc] == (unsigned short)(k - 1)) break;
-        }
-        if (q == nn) {                                      // cannot happen (cell k-1 of a shortest path is a neighbour)
+        const int q = axt_first_neighbour(r, c, WD, WD, nn, [=](int rr, int cc) {
+            return dist[rr * WD + cc] == (unsigned short)(k - 1);
+        });
+        if (q < 0) {                                        // cannot happen (cell k-1 of a shortest path is a neighbour)
             len[l] = LINK_EXACT;
             return;
         }
-        r += dy8[q];
-        c += dx8[q];
+        r += AXT_NB_DY[q];
+        c += AXT_NB_DX[q];
     }
     len[l] = found + 1;
 }
 
-constexpr unsigned int KEY_INF = 0xffffffffu;
-constexpr unsigned int KEY_OFF = 1u << 16;          // one off-mask cell entered
+constexpr unsigned int KEY_INF = AXT_KEY32_INF;
+constexpr unsigned int KEY_OFF = AXT_KEY32_OFF;     // one off-mask cell entered
 
 // One workgroup per link the breadth-first windows left undecided: the keys (off-mask cells entered, moves) of every
 // window cell, label-correcting sweeps over the window until nothing changes; accepted only with the certificate
@@ -352,7 +317,6 @@ __global__ __launch_bounds__(NT) void link_key_kernel(const int *__restrict__ li
     for (int e = tid; e < WD * WD; e += NT) key[e] = (e == R * WD + R) ? 0u : KEY_INF;
     __syncthreads();
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     for (int sweep = 0; sweep < WD * WD; ++sweep) {
         int changed = 0;
         for (int e = tid; e < WD * WD; e += NT) {
@@ -362,7 +326,7 @@ __global__ __launch_bounds__(NT) void link_key_kernel(const int *__restrict__ li
             const unsigned int w = mask[(long)gy * W + gx] == 1 ? 1u : KEY_OFF + 1u;
             unsigned int best = key[e];
             for (int q = 0; q < nn; ++q) {
-                const int rr = r + dy8[q], cc = c + dx8[q];
+                const int rr = r + AXT_NB_DY[q], cc = c + AXT_NB_DX[q];
                 if (rr < 0 || rr >= WD || cc < 0 || cc >= WD) continue;
                 const unsigned int kn = key[rr * WD + cc];
                 if (kn != KEY_INF && kn + w < best) best = kn + w;
@@ -375,7 +339,7 @@ __global__ __launch_bounds__(NT) void link_key_kernel(const int *__restrict__ li
     const int tr = ty - wy0, tc = tx - wx0;
     const unsigned int kt = key[tr * WD + tc];
     if (kt == KEY_INF) return;
-    const int o = (int)(kt >> 16), m = (int)(kt & 0xffffu);
+    const int o = (int)(kt >> 16), m = (int)(kt & AXT_KEY32_MOVES);
     if (m > R || o != lb) return;                           // no certificate: the exact search decides
     if (m + 1 >= max_dist) { len[l] = max_dist; return; }
     int *out = stage + (long)l * max_dist;
@@ -385,15 +349,10 @@ __global__ __launch_bounds__(NT) void link_key_kernel(const int *__restrict__ li
         if (k == 0) break;
         const unsigned int kc = key[r * WD + c];
         const unsigned int want = kc - (mask[(long)(wy0 + r) * W + (wx0 + c)] == 1 ? 1u : KEY_OFF + 1u);
-        int q = 0;
-        for (; q < nn; ++q) {
-            const int rr = r + dy8[q], cc = c + dx8[q];
-            if (rr < 0 || rr >= WD || cc < 0 || cc >= WD) continue;
-            if (key[rr * WD + cc] == want) break;
-        }
-        if (q == nn) return;                                // cannot happen at the fixed point; the exact search decides
-        r += dy8[q];
-        c += dx8[q];
+        const int q = axt_first_neighbour(r, c, WD, WD, nn, [=](int rr, int cc) { return key[rr * WD + cc] == want; });
+        if (q < 0) return;                                  // cannot happen at the fixed point; the exact search decides
+        r += AXT_NB_DY[q];
+        c += AXT_NB_DX[q];
     }
     len[l] = m + 1;
 }
@@ -463,7 +422,8 @@ extern "C" int axt_track_links(const int32_t *d_track, const int32_t *d_count, i
     hipLaunchKernelGGL(links_find_kernel, dim3(n_frames), dim3(LT), 0, st, d_track, d_count, n_frames, cap, max_gap, head,
                        gap, frame_cnt);
     AXT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_kernel<int>, dim3(1), dim3(1024), 0, st, (const int *)frame_cnt, n_frames, frame_off, 0);
+    hipLaunchKernelGGL((axt_scan_kernel<int, ClampedCount>), dim3(1), dim3(1024), 0, st, (const int *)frame_cnt, (long)n_frames, frame_off,
+                       ClampedCount{0});
     AXT_LAUNCH_CHECK();
     hipLaunchKernelGGL(links_emit_kernel, dim3(n_frames), dim3(LT), 0, st, d_count, cap, (const int *)head, (const int *)gap,
                        (const int *)frame_off, d_links);
@@ -490,13 +450,12 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
         AXT_LAUNCH_CHECK();
         return AXT_OK;
     }
-    const uint8_t *mask = axt_grid_mask(grid);
-    const int32_t *label = axt_grid_label(grid);
-    int n_comp = 0;
-    const uint8_t *off_field = axt_grid_off_field(grid, &n_comp);
-    int *counters = nullptr;                  // links left for the exact search
-    AXT_CHECK_HIP(hipMallocAsync((void **)&counters, sizeof(int), st));
-    AXT_CHECK_HIP(hipMemsetAsync(counters, 0, sizeof(int), st));
+    const uint8_t *mask = grid->d_mask, *off_field = grid->d_off;
+    const int32_t *label = grid->d_label;
+    const int n_comp = grid->n_comp;
+    AxtScratch counters(st, sizeof(int));     // links left for the exact search
+    AXT_CHECK_HIP(counters.err);
+    AXT_CHECK_HIP(hipMemsetAsync(counters.p, 0, sizeof(int), st));
     hipLaunchKernelGGL(link_classify_kernel, dim3(nb), dim3(256), 0, st, d_links, n_links, d_x, d_y, cap, d_head_group, group,
                        mask, label, H, W, max_dist, d_len);
     AXT_LAUNCH_CHECK();
@@ -504,7 +463,7 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
     const size_t lds1 = sizeof(unsigned short) * (2 * R1 + 1) * (2 * R1 + 1);
     const size_t lds2 = sizeof(unsigned short) * (2 * R2 + 1) * (2 * R2 + 1);
     static AxtOncePerDevice once;             // (per device: see axt_common.h)
-    if (int rc = axt_max_dynamic_lds(link_bfs_kernel<R2, 1024>, (int)lds2, once)) { (void)hipFreeAsync(counters, st); return rc; }
+    if (int rc = axt_max_dynamic_lds(link_bfs_kernel<R2, 1024>, (int)lds2, once)) return rc;
     hipLaunchKernelGGL((link_bfs_kernel<R1, 256>), dim3(n_links), dim3(256), lds1, st, d_links, d_x, d_y, mask, H, W, max_dist,
                        conn8, 0, d_len, d_stage);
     AXT_LAUNCH_CHECK();
@@ -520,33 +479,27 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
                            st, d_links, d_x, d_y, mask, label, off_field, n_comp, H, W, max_dist, conn8, d_len, d_stage);
         AXT_LAUNCH_CHECK();
     }
-    int *which = nullptr, *xy4 = nullptr;
-    AXT_CHECK_HIP(hipMallocAsync((void **)&which, sizeof(int) * 5 * (size_t)n_links, st));
-    xy4 = which + n_links;
-    hipLaunchKernelGGL(link_exact_list_kernel, dim3(nb), dim3(256), 0, st, d_links, n_links, d_x, d_y, d_len, counters,
+    AxtScratch lists(st, sizeof(int) * 5 * (size_t)n_links);
+    AXT_CHECK_HIP(lists.err);
+    int *which = lists.as<int>(), *xy4 = which + n_links;
+    hipLaunchKernelGGL(link_exact_list_kernel, dim3(nb), dim3(256), 0, st, d_links, n_links, d_x, d_y, d_len, counters.as<int>(),
                        which, xy4);
     AXT_LAUNCH_CHECK();
     int n_exact = 0;
-    AXT_CHECK_HIP(hipMemcpyAsync(&n_exact, counters, sizeof(int), hipMemcpyDeviceToHost, st));
+    AXT_CHECK_HIP(hipMemcpyAsync(&n_exact, counters.p, sizeof(int), hipMemcpyDeviceToHost, st));
     AXT_CHECK_HIP(hipStreamSynchronize(st));
     if (getenv("AXT_PATH_DEBUG")) fprintf(stderr, "link paths: %d of %d links by the exact search\n", n_exact, n_links);
-    int rc = AXT_OK;
-    if (n_exact > 0) {
-        int *D = nullptr, *cells = nullptr;
-        AXT_CHECK_HIP(hipMallocAsync((void **)&D, sizeof(int) * ((size_t)n_exact * (max_dist + 1)), st));
-        cells = D + n_exact;
-        rc = axt_path_cells_pairs(xy4, xy4 + n_links, xy4 + 2 * (long)n_links, xy4 + 3 * (long)n_links, n_exact, mask, H, W, max_dist,
-                                  conn8, D, cells, st);
-        if (rc == AXT_OK) {
-            hipLaunchKernelGGL(link_exact_scatter_kernel, dim3(n_exact), dim3(64), 0, st, (const int *)which, (const int *)D,
-                               (const int *)cells, max_dist, d_len, d_stage);
-            AXT_LAUNCH_CHECK();
-        }
-        AXT_CHECK_HIP(hipFreeAsync(D, st));
-    }
-    AXT_CHECK_HIP(hipFreeAsync(which, st));
-    AXT_CHECK_HIP(hipFreeAsync(counters, st));
-    return rc;
+    if (n_exact == 0) return AXT_OK;
+    AxtScratch exact(st, sizeof(int) * ((size_t)n_exact * (max_dist + 1)));
+    AXT_CHECK_HIP(exact.err);
+    int *D = exact.as<int>(), *cells = D + n_exact;
+    if (int rc = axt_path_cells_pairs(xy4, xy4 + n_links, xy4 + 2 * (long)n_links, xy4 + 3 * (long)n_links, n_exact, mask, H, W,
+                                      max_dist, conn8, D, cells, st))
+        return rc;
+    hipLaunchKernelGGL(link_exact_scatter_kernel, dim3(n_exact), dim3(64), 0, st, (const int *)which, (const int *)D,
+                       (const int *)cells, max_dist, d_len, d_stage);
+    AXT_LAUNCH_CHECK();
+    return AXT_OK;
 }
 
 extern "C" int axt_link_cells(const int32_t *d_links, int n_links, const int32_t *d_len, const int32_t *d_stage,
@@ -556,7 +509,8 @@ extern "C" int axt_link_cells(const int32_t *d_links, int n_links, const int32_t
     AXT_REQUIRE(n_links >= 0 && max_dist > 1 && max_gap >= 1 && d_cell_ptr && n_cells, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     if (!d_cells) {
-        hipLaunchKernelGGL(scan_kernel<long long>, dim3(1), dim3(1024), 0, st, d_len, n_links, (long long *)d_cell_ptr, max_dist);
+        hipLaunchKernelGGL((axt_scan_kernel<long long, ClampedCount>), dim3(1), dim3(1024), 0, st, d_len, (long)n_links,
+                           (long long *)d_cell_ptr, ClampedCount{max_dist});
         AXT_LAUNCH_CHECK();
         long long total = 0;
         AXT_CHECK_HIP(hipMemcpyAsync(&total, d_cell_ptr + n_links, sizeof(total), hipMemcpyDeviceToHost, st));

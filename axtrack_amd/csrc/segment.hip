@@ -30,13 +30,15 @@
 //   steps each way) and the rows above and below (__shfl, for 8 neighbours OR-ed with their own left and right
 //   shifts), the halo (the neighbour tiles' border bits, read once per visit) entering at lanes 0 and 63 and bits 0
 //   and 63. Every sweep but the last reaches at least one more of the tile's 4096 cells. Rounds, worklists, flags and
-//   the three counters in rotation are target.hip's; so is the argument that the result is the unique fixed point:
+//   the three counters in rotation are tile_worklist.h's; so is the argument that the result is the unique fixed point:
 //   reach only grows, a word has one writer (its tile) and is read and written whole, a tile whose border grew marks
 //   the neighbours that have those cells in their halo (for 8 neighbours a corner cell also marks the diagonal tile),
 //   so when a round marks nothing every tile has been swept against the final halo. A cell connected to the seed
 //   by a path that crosses k tile borders is reached after round k; a path minimal in crossings enters no tile twice
 //   through the same one of its 4 * 64 - 4 border cells, so at most n_tiles * 4 * 64 rounds can do work.
 #include "axt_common.h"
+#include "grid.h"
+#include "tile_worklist.h"
 
 namespace {
 
@@ -226,12 +228,11 @@ __global__ __launch_bounds__(256) void unpack_kernel(const u64 *__restrict__ bit
 
 // ------------------------------------------------------------------------------------------------ stage 5
 constexpr int FTS = 64;                      // tile edge: a row of a tile is one word, a tile is one wave
-constexpr int CHECK_EVERY = 16;              // rounds between two reads of the worklist counter
 
 __device__ __forceinline__ u64 word_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// open = cells with the seed's value, reach = 0 but for the seed; ctrl: [0..2] worklist counters in rotation, [3]
-// rounds that had work; the seed's tile is the worklist of round 0
+// open = cells with the seed's value, reach = 0 but for the seed; the worklist state of tile_worklist.h, the seed's tile
+// being the worklist of round 0
 __global__ __launch_bounds__(256) void flood_init_kernel(const unsigned char *__restrict__ img, int H, int W, int WW, int seed_y,
                                                          int seed_x, u64 *__restrict__ open, u64 *__restrict__ reach,
                                                          int *__restrict__ ctrl, int *__restrict__ flags, int *__restrict__ lists,
@@ -262,18 +263,10 @@ __global__ __launch_bounds__(64) void flood_round_kernel(const u64 *__restrict__
                                                          int tiles_y, int conn8, int round, int *__restrict__ ctrl,
                                                          int *__restrict__ flags, int *__restrict__ lists)
 {
-    const int lane = threadIdx.x, tiles_x = WW, n_tiles = tiles_x * tiles_y;
-    const int par = round & 1;
-    const int n_cur = min(ctrl[round % 3], n_tiles);
-    if (blockIdx.x == 0 && lane == 0) {
-        ctrl[(round + 2) % 3] = 0;                    // (nobody reads or writes that counter in this round)
-        if (n_cur > 0) ctrl[3] += 1;                  // (launches of a stream run one after the other)
-    }
-    if ((int)blockIdx.x >= n_cur) return;
-    const int t = lists[par * n_tiles + blockIdx.x];
-    if (t < 0 || t >= n_tiles) return;
+    const int lane = threadIdx.x, tiles_x = WW;
+    const int t = axt_worklist_take(round, tiles_x * tiles_y, ctrl, flags, lists);
+    if (t < 0) return;
     const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    if (lane == 0) flags[par * n_tiles + t] = 0;
     const int y = ty * FTS + lane;
     const bool in = y < H;
     const long at = (long)y * WW + tx;
@@ -323,20 +316,10 @@ __global__ __launch_bounds__(64) void flood_round_kernel(const u64 *__restrict__
     if (grown) __hip_atomic_store(&reach[at], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (in: op = 0 below H)
     const u64 any_l = __ballot((grown & 1ull) != 0), any_r = __ballot((grown >> 63) != 0);
     const u64 g_top = __shfl(grown, 0), g_bot = __shfl(grown, FTS - 1);
-    int dirs = (g_top ? 1 : 0) | (g_bot ? 2 : 0) | (any_l ? 4 : 0) | (any_r ? 8 : 0);       // dy8 / dx8 order below
+    int dirs = (g_top ? 1 : 0) | (g_bot ? 2 : 0) | (any_l ? 4 : 0) | (any_r ? 8 : 0);       // (bits in the neighbour order)
     if (conn8) dirs |= ((g_top & 1ull) ? 16 : 0) | ((g_top >> 63) ? 32 : 0) | ((g_bot & 1ull) ? 64 : 0) | ((g_bot >> 63) ? 128 : 0);
     __threadfence();                                  // the words before the marks
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
-    if (lane < 8 && (dirs >> lane & 1)) {
-        const int ny = ty + dy8[lane], nx = tx + dx8[lane];
-        if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x) {
-            const int nt = ny * tiles_x + nx;
-            if (atomicExch(&flags[(par ^ 1) * n_tiles + nt], 1) == 0) {
-                const int k = atomicAdd(&ctrl[(round + 1) % 3], 1);      // (< n_tiles: a tile enters a worklist once)
-                if (k < n_tiles) lists[(par ^ 1) * n_tiles + k] = nt;
-            }
-        }
-    }
+    axt_worklist_mark(dirs, t, tiles_x, tiles_y, round, ctrl, flags, lists);
 }
 
 int radius_of(double sigma) { return (int)(4.0 * sigma + 0.5); }
@@ -430,42 +413,24 @@ extern "C" int axt_segment_flood(const uint8_t *d_img, int H, int W, int seed_y,
     const int n_tiles = (int)n_tiles_l;
     const size_t words = (size_t)H * WW;
     // scratch: open u64 [H][WW], reach u64 [H][WW], then i32: ctrl [4], flags [2][n_tiles], lists [2][n_tiles]
-    unsigned char *raw = nullptr;
-    AXT_CHECK_HIP(hipMallocAsync((void **)&raw, 2 * words * sizeof(u64) + sizeof(int) * (4 + 4 * (size_t)n_tiles), st));
-    u64 *open = reinterpret_cast<u64 *>(raw), *reach = open + words;
+    AxtScratch raw(st, 2 * words * sizeof(u64) + sizeof(int) * (4 + 4 * (size_t)n_tiles));
+    AXT_CHECK_HIP(raw.err);
+    u64 *open = raw.as<u64>(), *reach = open + words;
     int *ctrl = reinterpret_cast<int *>(reach + words);
     int *flags = ctrl + 4, *lists = flags + 2 * (size_t)n_tiles;
     const dim3 px((unsigned)((long)H * axt_cdiv(W, 256)));
     hipLaunchKernelGGL(flood_init_kernel, px, dim3(256), 0, st, d_img, H, W, WW, seed_y, seed_x, open, reach, ctrl, flags, lists,
                        n_tiles);
-    int rc = AXT_OK;
-    hipError_t e = hipGetLastError();
-    // every round with work lets some path of the region cross one more tile border: see the top
-    const long max_rounds = n_tiles_l * 4 * FTS + 2;
-    int h_ctrl[4] = {0, 0, 0, 0};
-    bool done = false;
-    long round = 0;
-    while (e == hipSuccess && !done && round < max_rounds) {
-        for (int k = 0; k < CHECK_EVERY; ++k, ++round)
-            hipLaunchKernelGGL(flood_round_kernel, dim3(n_tiles), dim3(64), 0, st, (const u64 *)open, reach, H, WW, tiles_y,
-                               conn8 ? 1 : 0, (int)(round % 6), ctrl, flags, lists);      // (the kernel needs round % 2 and % 3)
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_ctrl, ctrl, sizeof(h_ctrl), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        done = h_ctrl[round % 3] == 0;                       // the worklist of the round that would come next
-    }
-    if (e != hipSuccess) {
-        axt_set_error("axt_segment_flood: %s", hipGetErrorString(e));
-        rc = AXT_EHIP;
-    } else if (!done) {
-        axt_set_error("axt_segment_flood: no fixed point after %ld rounds (bound for %d tiles)", max_rounds, n_tiles);
-        rc = AXT_ERUNTIME;
-    } else {
+    int rounds = 0;
+    int rc = axt_worklist_run("axt_segment_flood", [&](int r) {
+        hipLaunchKernelGGL(flood_round_kernel, dim3(n_tiles), dim3(64), 0, st, (const u64 *)open, reach, H, WW, tiles_y,
+                           conn8 ? 1 : 0, r, ctrl, flags, lists);
+    }, ctrl, n_tiles_l, FTS, st, &rounds);
+    if (rc == AXT_OK) {
         hipLaunchKernelGGL(unpack_kernel, px, dim3(256), 0, st, (const u64 *)reach, H, W, WW, d_out);
-        e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { axt_set_error("axt_segment_flood: %s", hipGetErrorString(e)); rc = AXT_EHIP; }
     }
-    (void)hipFreeAsync(raw, st);
-    if (rounds_out) *rounds_out = rc == AXT_OK ? h_ctrl[3] : 0;
+    if (rounds_out) *rounds_out = rc == AXT_OK ? rounds : 0;
     return rc;
 }

@@ -6,7 +6,7 @@
 // every frame reads its distance -- the opposite shape of path_bfs.hip / recon.hip, which answer pair questions inside
 // the 500-cell association gate with one workgroup per source.
 //
-// Definition (the package's path convention, path_bfs.hip): weights {1 on mask, 65536 off}, a move costs the weight of
+// Definition (the package's path convention, grid.h): weights {1 on mask, 65536 off}, a move costs the weight of
 // the cell moved INTO, 4- or 8-connected (a diagonal move counts 1). Minimum cost is the lexicographic order of
 // (off-mask cells entered, moves), packed as the 64-bit key off << 32 | moves. For target cells T, key(c) is the
 // minimum over all paths from c to any cell of T (the cells entered after c count, the target cell included); key = 0
@@ -19,10 +19,8 @@
 //     place (pull: key(v) = min over neighbours u of key(u) + w(u); one writer per cell, keys only decrease) until a
 //     sweep changes nothing: the tile's fixed point for the halo it read. It writes back the cells it improved and, for
 //     every border (corner) whose cells improved, marks the neighbour tile that has them in its halo.
-//   * A round is one launch over the worklist of marked tiles; the marks of round r are the worklist of round r+1
-//     (per-tile flag so that a tile enters once, a counter per round, three counters in rotation so that no launch
-//     resets the counter it reads). Launches have one workgroup per tile of the grid; those beyond the worklist's end
-//     leave at once. No grid-wide barrier, no spinning, no cooperative launch; every loop in the kernel is bounded.
+//   * Rounds, worklists, per-tile flags and the three counters in rotation: tile_worklist.h. Every loop in the kernel
+//     is bounded.
 //   * Within a round a workgroup may read a neighbour's border cell before or after that neighbour improves it: either
 //     value is the cost of a real path (an upper bound), 8-byte keys are read and written whole, and the neighbour marks
 //     this tile whenever its border changed, whatever this tile saw. So when a round marks nothing every tile has been
@@ -30,38 +28,33 @@
 //     weights and key = 0 on T, whose only solution reached from above is the shortest-path key. The result does not
 //     depend on scheduling: byte-identical from run to run.
 //   * After round k every cell whose optimal path crosses at most k tile borders is final, so the number of rounds
-//     grows with the tiles a path crosses, not with its cells. An optimal path is simple and every crossing enters a
-//     tile through one of its 4 TS - 4 border cells, so at most n_tiles * 4 TS rounds can do work; the host stops at
-//     that bound with an error instead of looping. It reads the worklist counter back every 16 rounds.
+//     grows with the tiles a path crosses, not with its cells (the bound at which the host stops: tile_worklist.h).
 //   * Sweeps per tile visit: every sweep finalises at least one more cell of the tile, so TS * TS + 1 bounds them.
 // axt_target_sample: (off, moves) of every detection slot; -1 for empty slots and detections outside the grid (the
 //   decode does not clamp). A per-frame field index serves time-varying masks (one field per distinct mask).
 // axt_target_paths: the target path of a detection starts at its cell and steps to the first neighbour n (up, down,
-//   left, right, then the diagonals in path_bfs.hip's order) with key(c) == key(n) + w(n); it has moves + 1 cells and
+//   left, right, then the diagonals: grid.h's order) with key(c) == key(n) + w(n); it has moves + 1 cells and
 //   ends in T. CSR like axt_link_cells: cell_ptr = scan of moves + 1 (no count pass), one thread per detection.
 #include "axt_common.h"
-
-struct axt_grid;
-extern "C" const uint8_t *axt_grid_mask(const axt_grid *g);
-void axt_grid_shape(const axt_grid *g, int *H, int *W);
+#include "grid.h"
+#include "tile_worklist.h"
 
 namespace {
 
-typedef unsigned long long u64;
+typedef axt_u64 u64;
 
 constexpr int TS = 32;                       // tile edge
 constexpr int TH = TS + 2;                   // with the halo
 constexpr int NT = 256;                      // threads per workgroup
 constexpr int CPT = TS * TS / NT;            // cells per thread
-constexpr u64 KEY_INF = ~0ull;
-constexpr u64 W_ON = 1ull, W_OFF = (1ull << 32) | 1ull;
-constexpr int CHECK_EVERY = 16;              // rounds between two reads of the worklist counter
+constexpr u64 KEY_INF = AXT_KEY64_INF;
+constexpr u64 W_ON = 1ull, W_OFF = AXT_KEY64_OFF | 1ull;
 
 // a key is read and written whole (one 8-byte LDS access) while other threads of the workgroup relax their cells
 __device__ __forceinline__ u64 lds_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_store(u64 *p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// ctrl: [0..2] worklist counters in rotation, [3] rounds that had work
+// ctrl, flags, lists: the worklist state of tile_worklist.h
 __global__ __launch_bounds__(256) void field_init_kernel(u64 *__restrict__ key, long n, int *__restrict__ ctrl,
                                                          int *__restrict__ flags, int n_tiles)
 {
@@ -95,18 +88,11 @@ __global__ __launch_bounds__(NT) void field_round_kernel(const unsigned char *__
     __shared__ u64 s_key[TH * TH];
     __shared__ unsigned char s_off[TH * TH];          // 1 = the cell is off the mask
     __shared__ int s_dirs;
-    const int tid = threadIdx.x, n_tiles = tiles_x * tiles_y;
-    const int par = round & 1;
-    const int n_cur = min(ctrl[round % 3], n_tiles);
-    if (blockIdx.x == 0 && tid == 0) {
-        ctrl[(round + 2) % 3] = 0;                    // (nobody reads or writes that counter in this round)
-        if (n_cur > 0) ctrl[3] += 1;                  // (launches of a stream run one after the other)
-    }
-    if ((int)blockIdx.x >= n_cur) return;
-    const int t = lists[par * n_tiles + blockIdx.x];
-    if (t < 0 || t >= n_tiles) return;
+    const int tid = threadIdx.x;
+    const int t = axt_worklist_take(round, tiles_x * tiles_y, ctrl, flags, lists);
+    if (t < 0) return;
     const int ty0 = (t / tiles_x) * TS, tx0 = (t % tiles_x) * TS;
-    if (tid == 0) { flags[par * n_tiles + t] = 0; s_dirs = 0; }
+    if (tid == 0) s_dirs = 0;
     for (int e = tid; e < TH * TH; e += NT) {
         const int r = e / TH, c = e - r * TH;
         const int gy = ty0 - 1 + r, gx = tx0 - 1 + c;
@@ -122,7 +108,6 @@ __global__ __launch_bounds__(NT) void field_round_kernel(const unsigned char *__
     }
     __syncthreads();
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     int pos[CPT];
     u64 first[CPT];
     for (int q = 0; q < CPT; ++q) {
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(NT) void field_round_kernel(const unsigned char *__
             const u64 mine = lds_load(&s_key[p]);
             u64 best = mine;
             for (int d = 0; d < nn; ++d) {
-                const int pn = p + dy8[d] * TH + dx8[d];
+                const int pn = p + AXT_NB_DY[d] * TH + AXT_NB_DX[d];
                 const u64 kn = lds_load(&s_key[pn]);
                 if (kn == KEY_INF) continue;
                 const u64 cand = kn + (s_off[pn] ? W_OFF : W_ON);
@@ -164,16 +149,7 @@ __global__ __launch_bounds__(NT) void field_round_kernel(const unsigned char *__
     if (dirs) atomicOr(&s_dirs, dirs);
     __threadfence();                                  // the keys before the marks
     __syncthreads();
-    if (tid < 8 && (s_dirs >> tid & 1)) {
-        const int ny = t / tiles_x + dy8[tid], nx = t % tiles_x + dx8[tid];
-        if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x) {
-            const int nt = ny * tiles_x + nx;
-            if (atomicExch(&flags[(par ^ 1) * n_tiles + nt], 1) == 0) {
-                const int k = atomicAdd(&ctrl[(round + 1) % 3], 1);      // (< n_tiles: a tile enters a worklist once)
-                if (k < n_tiles) lists[(par ^ 1) * n_tiles + k] = nt;
-            }
-        }
-    }
+    axt_worklist_mark(s_dirs, t, tiles_x, tiles_y, round, ctrl, flags, lists);
 }
 
 __global__ __launch_bounds__(256) void field_unpack_kernel(const u64 *__restrict__ key, long n, int *__restrict__ off,
@@ -208,29 +184,10 @@ __global__ __launch_bounds__(256) void sample_kernel(const int *__restrict__ off
     det_moves[s] = m;
 }
 
-// cell_ptr[0..n] = exclusive prefix sum of moves + 1 (0 where moves < 0); one workgroup
-__global__ __launch_bounds__(1024) void path_scan_kernel(const int *__restrict__ det_moves, long n, long long *__restrict__ ptr)
-{
-    __shared__ long long s_part[1024];
-    const int tid = threadIdx.x;
-    const long per = (n + 1023) / 1024;
-    const long a = min(n, tid * per), b = min(n, a + per);
-    long long sum = 0;
-    for (long k = a; k < b; ++k) sum += det_moves[k] < 0 ? 0 : det_moves[k] + 1;
-    s_part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int k = 0; k < 1024; ++k) { const long long v = s_part[k]; s_part[k] = run; run += v; }
-        ptr[n] = run;
-    }
-    __syncthreads();
-    long long run = s_part[tid];
-    for (long k = a; k < b; ++k) {
-        ptr[k] = run;
-        run += det_moves[k] < 0 ? 0 : det_moves[k] + 1;
-    }
-}
+// the cells of a detection's target path: moves + 1, none where moves < 0 (cell_ptr = their exclusive prefix sum)
+struct PathCells {
+    __device__ int operator()(int moves) const { return moves < 0 ? 0 : moves + 1; }
+};
 
 // one thread per detection slot: the walk over the field (see the top); a step that finds no neighbour -- impossible
 // on a field of axt_target_field for this mask -- leaves -1 in the rest of the path
@@ -251,36 +208,26 @@ __global__ __launch_bounds__(64) void path_walk_kernel(const unsigned char *__re
     int cx = x[s], cy = y[s];
     if (cx < 0 || cx >= W || cy < 0 || cy >= H) return;
     const int nn = conn8 ? 8 : 4;
-    const int dy8[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, dx8[8] = {0, 0, -1, 1, -1, 1, -1, 1};
     for (int k = 0; k <= m0; ++k) {
         const long c = (long)cy * W + cx;
         cells[p + k] = (int)c;
         if (k == m0) break;
         const int oc = off[c], mc = moves[c];
-        int found = -1;
-        for (int q = 0; q < nn && found < 0; ++q) {
-            const int ny = cy + dy8[q], nx = cx + dx8[q];
-            if (ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
+        const int found = axt_first_neighbour(cy, cx, H, W, nn, [=](int ny, int nx) {
             const long g = (long)ny * W + nx;
             const int wn = (mask == nullptr || mask[g] == 1) ? 0 : 1;
-            if (off[g] + wn == oc && moves[g] + 1 == mc) found = q;
-        }
+            return off[g] + wn == oc && moves[g] + 1 == mc;
+        });
         if (found < 0) {
             for (int r = k + 1; r <= m0; ++r) cells[p + r] = -1;
             break;
         }
-        cy += dy8[found];
-        cx += dx8[found];
+        cy += AXT_NB_DY[found];
+        cx += AXT_NB_DX[found];
     }
 }
 
-int grid_matches(const axt_grid *grid, int H, int W)
-{
-    if (!grid) return 1;
-    int gh = 0, gw = 0;
-    axt_grid_shape(grid, &gh, &gw);
-    return gh == H && gw == W;
-}
+int grid_matches(const axt_grid *grid, int H, int W) { return !grid || (grid->H == H && grid->W == W); }
 
 }  // namespace
 
@@ -300,11 +247,11 @@ extern "C" int axt_target_field(const axt_grid *grid, int H, int W, int conn8, c
     const long n_tiles_l = (long)tiles_x * tiles_y;
     const int n_tiles = (int)n_tiles_l;
     // scratch: keys u64 [H*W], then i32: ctrl [4], flags [2][n_tiles], lists [2][n_tiles]
-    unsigned char *raw = nullptr;
     const size_t key_bytes = sizeof(u64) * (size_t)n;
-    AXT_CHECK_HIP(hipMallocAsync((void **)&raw, key_bytes + sizeof(int) * (4 + 4 * (size_t)n_tiles), st));
-    u64 *key = reinterpret_cast<u64 *>(raw);
-    int *ctrl = reinterpret_cast<int *>(raw + key_bytes);
+    AxtScratch raw(st, key_bytes + sizeof(int) * (4 + 4 * (size_t)n_tiles));
+    AXT_CHECK_HIP(raw.err);
+    u64 *key = raw.as<u64>();
+    int *ctrl = reinterpret_cast<int *>(raw.as<unsigned char>() + key_bytes);
     int *flags = ctrl + 4, *lists = flags + 2 * (size_t)n_tiles;
     const unsigned nb = (unsigned)((n + 255) / 256);
     long n_init = n > 2 * n_tiles_l ? n : 2 * n_tiles_l;      // (a tiny grid has fewer cells than flags or counters)
@@ -313,35 +260,17 @@ extern "C" int axt_target_field(const axt_grid *grid, int H, int W, int conn8, c
     hipLaunchKernelGGL(field_init_kernel, dim3(nb_init), dim3(256), 0, st, key, n, ctrl, flags, n_tiles);
     hipLaunchKernelGGL(field_seed_kernel, dim3((unsigned)((n_targets + 255) / 256)), dim3(256), 0, st, d_target_cells, n_targets,
                        H, W, tiles_x, key, ctrl, flags, lists);
-    int rc = AXT_OK;
-    hipError_t e = hipGetLastError();
-    // every round with work lets some optimal path cross one more tile border: see the top
-    const long max_rounds = n_tiles_l * 4 * TS + 2;
-    int h_ctrl[4] = {0, 0, 0, 0};
-    bool done = false;
-    long round = 0;
-    while (e == hipSuccess && !done && round < max_rounds) {
-        for (int k = 0; k < CHECK_EVERY; ++k, ++round)
-            hipLaunchKernelGGL(field_round_kernel, dim3(n_tiles), dim3(NT), 0, st, mask, H, W, tiles_x, tiles_y, conn8 ? 1 : 0,
-                               (int)(round % 6), key, ctrl, flags, lists);      // (the kernel needs round % 2 and % 3)
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_ctrl, ctrl, sizeof(h_ctrl), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        done = h_ctrl[round % 3] == 0;                       // the worklist of the round that would come next
-    }
-    if (e != hipSuccess) {
-        axt_set_error("axt_target_field: %s", hipGetErrorString(e));
-        rc = AXT_EHIP;
-    } else if (!done) {
-        axt_set_error("axt_target_field: no fixed point after %ld rounds (bound for %d tiles)", max_rounds, n_tiles);
-        rc = AXT_ERUNTIME;
-    } else {
+    int rounds = 0;
+    int rc = axt_worklist_run("axt_target_field", [&](int r) {
+        hipLaunchKernelGGL(field_round_kernel, dim3(n_tiles), dim3(NT), 0, st, mask, H, W, tiles_x, tiles_y, conn8 ? 1 : 0, r, key,
+                           ctrl, flags, lists);
+    }, ctrl, n_tiles_l, TS, st, &rounds);
+    if (rc == AXT_OK) {
         hipLaunchKernelGGL(field_unpack_kernel, dim3(nb), dim3(256), 0, st, (const u64 *)key, n, d_off, d_moves);
-        e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { axt_set_error("axt_target_field: %s", hipGetErrorString(e)); rc = AXT_EHIP; }
     }
-    (void)hipFreeAsync(raw, st);
-    if (n_rounds) *n_rounds = rc == AXT_OK ? h_ctrl[3] : 0;
+    if (n_rounds) *n_rounds = rc == AXT_OK ? rounds : 0;
     return rc;
 }
 
@@ -372,7 +301,8 @@ extern "C" int axt_target_paths(const axt_grid *grid, const int32_t *d_off, cons
     hipStream_t st = (hipStream_t)stream;
     const long slots = (long)n_frames * cap;
     if (!d_cells) {
-        hipLaunchKernelGGL(path_scan_kernel, dim3(1), dim3(1024), 0, st, d_det_moves, slots, (long long *)d_cell_ptr);
+        hipLaunchKernelGGL((axt_scan_kernel<long long, PathCells>), dim3(1), dim3(1024), 0, st, d_det_moves, slots, (long long *)d_cell_ptr,
+                           PathCells{});
         AXT_LAUNCH_CHECK();
         long long total = 0;
         AXT_CHECK_HIP(hipMemcpyAsync(&total, d_cell_ptr + slots, sizeof(total), hipMemcpyDeviceToHost, st));

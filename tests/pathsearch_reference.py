@@ -101,9 +101,13 @@ class Case:
 
 
 # ------------------------------------------------------------------------------------------------ reference
+# (dy, dx): up, down, left, right, then the diagonals; the first 4 are the 4-connected grid (csrc/grid.h states the same)
+STEPS8 = [(-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (-1, 1), (1, -1), (1, 1)]
+
+
 def _edges(H, W, conn8):
     idx = np.arange(H * W).reshape(H, W)
-    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)] + ([(-1, -1), (-1, 1), (1, -1), (1, 1)] if conn8 else [])
+    steps = STEPS8[:8 if conn8 else 4]
     src, dst = [], []
     for dy, dx in steps:
         ys, xs = np.mgrid[max(0, -dy):H - max(0, dy), max(0, -dx):W - max(0, dx)]
@@ -270,7 +274,7 @@ def model(case):
     x, y, cnt = case.arrays()
     H, W = case.shape
     dm = case.dmax
-    nbr = [(-1, 0), (1, 0), (0, -1), (0, 1)] + ([(-1, -1), (-1, 1), (1, -1), (1, 1)] if case.conn8 else [])
+    nbr = STEPS8[:8 if case.conn8 else 4]
     tight_ok = f.off is not None
     off_mode_ok = tight_ok and lds4(case.max_gap, case.cap) <= LDS_LIMIT and 'AXT_PATH_NO_OFFMODE' not in case.env
     assert (lds4 if off_mode_ok else lds3)(case.max_gap, case.cap) <= LDS_LIMIT

@@ -10,7 +10,7 @@ import numpy as np
 from scipy.sparse import csr_matrix
 from scipy.sparse.csgraph import dijkstra
 
-DY8 = (-1, 1, 0, 0, -1, -1, 1, 1)          # up, down, left, right, then the diagonals in path_bfs.hip's order
+DY8 = (-1, 1, 0, 0, -1, -1, 1, 1)          # up, down, left, right, then the diagonals in csrc/grid.h's order
 DX8 = (0, 0, -1, 1, -1, 1, -1, 1)
 OFF_WEIGHT = 65536
 

@@ -615,3 +615,33 @@ int main()
     subprocess.check_call(['/opt/rocm/bin/hipcc', '-x', 'c++', '-std=c++17', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', f'-I{csrc}', str(src), '-o', str(exe),
                            '-L/opt/rocm/lib', '-lamdhip64', '-Wl,-rpath,/opt/rocm/lib'])
     assert subprocess.run([str(exe)]).returncode == 0
+
+
+def test_the_neighbour_order_is_stated_once_and_is_the_references_order(tmp_path):
+    """Which of several equally cheap paths a search returns is decided by the order in which neighbours are tried, so that
+    order is part of the results. The native code states it once, in csrc/grid.h (AXT_NB_DY / AXT_NB_DX, read by every
+    kernel and by the host code of axt_grid_create): a host program prints it, and it is the order both references walk in
+    (pathsearch_reference.STEPS8, target_reference.DY8 / DX8) -- up, down, left, right, then the diagonals."""
+    import subprocess
+    import pathsearch_reference
+    import target_reference
+    src = tmp_path / 'order.cpp'
+    src.write_text(r'''
+#include "axt_common.h"
+#include "grid.h"
+int main()
+{
+    static_assert(sizeof(AXT_NB_DY) == 8 * sizeof(int) && sizeof(AXT_NB_DX) == 8 * sizeof(int), "eight neighbours");
+    for (int q = 0; q < 8; ++q) printf("%d %d\n", AXT_NB_DY[q], AXT_NB_DX[q]);
+    return 0;
+}
+''')
+    exe = tmp_path / 'order'
+    csrc = os.path.join(ROOT, 'axtrack_amd', 'csrc')
+    subprocess.check_call(['/opt/rocm/bin/hipcc', '-x', 'hip', '--cuda-host-only', '-std=c++17', f'-I{csrc}', str(src), '-o', str(exe)])
+    order = [tuple(int(v) for v in line.split()) for line in subprocess.check_output([str(exe)], text=True).splitlines()]
+    assert order == [tuple(s) for s in pathsearch_reference.STEPS8]
+    assert order == list(zip(target_reference.DY8, target_reference.DX8))
+    stated = [line for name in sorted(os.listdir(csrc)) if name.endswith(('.hip', '.h', '.cpp'))
+              for line in open(os.path.join(csrc, name)) if '{-1, 1, 0, 0, -1, -1, 1, 1}' in line]
+    assert len(stated) == 1, stated
