@@ -947,7 +947,9 @@ def test_detection_metrics_match_the_reference(golden):
 # ----------------------------------------------------------------------------------------- f-1 (next row)
 def test_preprocess_fused_pass_matches_oracle():
     rng = np.random.default_rng(3)
-    T, H, W = 5, 300, 420                                   # W*H not a multiple of 8 per row, odd total tail
+    # H*W = 126 000 (and 124 800 below) is a multiple of 8: both shapes take the 8-pixel vector branch only. The scalar branch,
+    # the tail and the grid-stride loop are run by tests/test_stagekernels_gpu.py::test_preprocess.
+    T, H, W = 5, 300, 420
     raw = rng.integers(0, 5000, (T, H, W)).astype(np.uint16)
     raw[rng.uniform(size=raw.shape) < 0.7] = 0
     mask = synth.corridor_mask(H, W, 40, 128)
