@@ -5,7 +5,8 @@ setup_inference, prepare_input_data, inference -> AxonDetections.IDed_dets_all; 
 visualize_inference exists and says that matplotlib / video plotting is out of scope; render_inference draws the
 annotated frames on the GPU and writes PNG frames or one animated PNG; segment_mask makes the microchannel mask of
 prepare_input_data(mask_fname=...) from a transmission image (data_prep_nbs/00_segment_bg.ipynb); fine_tune_head
-trains the detector's three linear layers on labelled frames with the convolutional trunk frozen (training.py).
+trains the detector's three linear layers on labelled frames with the convolutional trunk frozen (training.py), with the
+reference's translate / flip / rotate augmentation redrawn every epoch if asked (augment.py).
 The compute lives in csrc/libaxtrack_hip.so (C ABI: include/axtrack_hip.h); there is no CPU
 fallback -- importing works anywhere, running needs the GPU and the built library.
 """
@@ -16,10 +17,13 @@ from .hotpath import Detector
 from .render import render_inference
 from .timelapse import Timelapse
 from .training import HeadTrainer, fine_tune_head, yolo_targets
+from .augment import (Transform, transform_from_uniforms, draw_transform, augment_frames, transform_labels,
+                      pos_label_rate)
 from .segment import (segment_microchannels, flood_initial_mask, segment_mask, save_final_mask,
                       otsu_threshold_from_hist)
 
 __all__ = ['setup_inference', 'prepare_input_data', 'inference', 'visualize_inference', 'PKG_DIR', 'DEPLOYED_MODEL_DIR',
            '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse', 'render_inference',
            'HeadTrainer', 'fine_tune_head', 'yolo_targets',
+           'Transform', 'transform_from_uniforms', 'draw_transform', 'augment_frames', 'transform_labels', 'pos_label_rate',
            'segment_microchannels', 'flood_initial_mask', 'segment_mask', 'save_final_mask', 'otsu_threshold_from_hist']

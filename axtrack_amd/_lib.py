@@ -112,6 +112,9 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     'axt_head_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                                       c_double, c_double, c_void_p]),
+    'axt_augment_frame_chunk': (c_int, []),
+    'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                   c_float, c_float, c_void_p, c_void_p, c_void_p]),
     'axt_render_tile_size': (c_int, []),
     'axt_render_frames': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -162,15 +162,23 @@ class Detector:
         return out
 
 
-    def features_frames(self, frames, tile_yx, t0=0, n_frames=None):
+    def features_frames(self, frames, tile_yx, t0=0, n_frames=None, out=None):
         """The frozen trunk of detect_frames: frames f32 [T_all,H,W] on the GPU -> [n_frames * n_tiles, 40960], the input of
         the first linear layer per (frame, tile) item in the flatten order of model.py:50-53 (axt_cnn_features_frames).
-        What training.HeadTrainer trains on."""
+        What training.HeadTrainer trains on. out: a contiguous f32 table of at least that many rows to write into (its
+        first n_frames * n_tiles rows are returned) instead of a new one."""
         T_all, H, W = frames.shape
         if n_frames is None:
             n_frames = T_all - 4 - t0
         tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
-        out = torch.empty((n_frames * len(tile_yx), FEATURES), dtype=torch.float32, device=self.device)
+        n_items = n_frames * len(tile_yx)
+        if out is None:
+            out = torch.empty((n_items, FEATURES), dtype=torch.float32, device=self.device)
+        else:
+            if not (out.is_contiguous() and out.dtype == torch.float32 and out.device == self.device and out.dim() == 2
+                    and out.shape[1] == FEATURES and out.shape[0] >= n_items):
+                raise ValueError(f'out must be a contiguous f32 table [>= {n_items}, {FEATURES}] on {self.device}')
+            out = out[:n_items]
         assert frames.is_contiguous() and frames.dtype == torch.float32 and frames.device == self.device
         with torch.cuda.device(self.device):
             _lib.check(self._lib.axt_cnn_features_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,

@@ -1,11 +1,13 @@
 """Fine-tuning of the detector's linear head on labelled frames.
 
 The convolutional trunk stays frozen: its output per (frame, tile) item -- what the first linear layer reads -- is computed
-once by the inference kernels (Detector.features_frames), and an epoch is nothing but head steps on that table: forward
+by the inference kernels (Detector.features_frames; once, or once per epoch when the frames are augmented), and an epoch is nothing but head steps on that table: forward
 (model.py:105-117), YOLO_AXTrack_loss (loss.py:18-68), backward and torch.optim.Adam with L2 weight decay
 (core_functionality.py:81), all in csrc/train.hip. The epoch loop restates one_epoch / run_epoch
-(core_functionality.py:109-165) without what cached features rule out (augmentation, the prepare_data resampling loop) and
-without the every-tenth-epoch metrics (call get_detection_metrics with a Detector built from the returned state dict)."""
+(core_functionality.py:109-165) without the every-tenth-epoch metrics (call get_detection_metrics with a Detector built
+from the returned state dict). With use_transforms it also restates the reference's augmentation (augment.py): a new
+translate / flip / rotate of frames and labels every epoch, the prepare_data resampling loop, and the feature table
+recomputed from the warped frames, which costs about one trunk pass per epoch."""
 import ctypes
 import os
 
@@ -216,19 +218,61 @@ def save_checkpoint(state_dict, filename):
     torch.save({'state_dict': sd, 'optimizer': None, 'lr_schedular': None}, filename)
 
 
-def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir=None, seed=None):
+def _augmented_epoch(frames, labels, transform, draw, min_pos_rate, max_redraws, warped):
+    """One epoch's draw: warp the frames by `transform`, or by draw() again and again while prepare_data's
+    rate stays below min_pos_rate (one_epoch's loop, core_functionality.py:141, which has no limit: here max_redraws)
+    -> (transform, warped frames, kept tiles, (lx, ly, count))."""
+    from . import augment
+    from .hotpath import tile_list
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    best = -1.0
+    for _ in range(1 + (max_redraws if transform is None else 0)):
+        tf = augment.as_transform(transform) if transform is not None else draw()
+        warped, occ = augment.augment_frames(frames, tf, return_occupancy=True, out=warped)
+        lab = augment.transform_labels(labels, tf, H, W)
+        occ = occ.cpu()
+        if transform is not None:                       # an explicit transform is used as it is
+            break
+        rate = augment.pos_label_rate(occ, *lab)
+        best = max(best, rate)
+        if rate >= min_pos_rate:
+            break
+    else:
+        raise RuntimeError(f'{max_redraws} redraws of the augmentation gave no labels-per-tile rate of {min_pos_rate} or '
+                           f'more (best: {best:.3f}): too few labels for USE_TRANSFORMS, or lower min_pos_rate')
+    tiles = tile_list(occ.amax(0), H, W)                # kept: not empty at some time point (Timelapse.py:551-558)
+    if not tiles:
+        raise ValueError(f'{tf} leaves every frame empty')
+    return tf, warped, tiles, lab
+
+
+def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir=None, seed=None, use_transforms=None,
+                   transforms=None, min_pos_rate=0.65, max_redraws=50):
     """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
     one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
     (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
     reference's five loss components, each the mean over the epoch's batches. dest_dir: E{epoch:04}.pth checkpoints for
-    the epochs in parameters['MODEL_CHECKPOINTS'] (default: the last one)."""
+    the epochs in parameters['MODEL_CHECKPOINTS'] (default: the last one).
+
+    use_transforms: a list of augmentation keys (parameters['USE_TRANSFORMS']: 'vflip', 'hflip', 'rot', 'translateY',
+    'translateX'). Every epoch then draws one transform (augment.draw_transform, from a generator of its own seeded by
+    `seed`), warps the frames and the labels with it, redraws while the labels-per-tile rate (augment.pos_label_rate) is
+    below min_pos_rate -- RuntimeError after max_redraws -- and recomputes the trunk features and the targets of the
+    tiles the warped frames keep. transforms: instead, one explicit transform per epoch (augment.Transform or a dict of
+    its fields), used as given. The transforms used are history.attrs['transforms'], which `transforms=` replays. With
+    neither (None or an empty list) nothing is augmented and the features are computed once."""
     import pandas as pd
-    from .hotpath import Detector
+    from .hotpath import Detector, FEATURES
     if getattr(timelapse, 'frame_sharded', False):
         raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
                                   'process on the whole timelapse')
     if len(labels) != len(timelapse):
         raise ValueError(f'{len(labels)} label frames for {len(timelapse)} detection frames')
+    augmented = bool(use_transforms) or transforms is not None
+    if transforms is not None and use_transforms:
+        raise ValueError('pass use_transforms (drawn every epoch) or transforms (one per epoch), not both')
+    if transforms is not None and len(transforms) != epochs:
+        raise ValueError(f'{len(transforms)} transforms for {epochs} epochs')
     P = dict(TRAIN_DEFAULTS)
     P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
     if isinstance(model, Detector):
@@ -239,15 +283,38 @@ def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir
         sd = model.get('state_dict', model)
         detector = Detector(sd, max_batch=32, device=timelapse.device)
     timelapse.make_resident()
-    tile_yx = timelapse.tile_yx
-    features = detector.features_frames(timelapse.frames, tile_yx)
-    targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
     bs = int(P['BATCH_SIZE'])
-    trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
+    if augmented:
+        from . import augment
+        unknown = [k for k in (use_transforms or []) if k not in augment.TRANSFORM_KEYS]
+        if unknown:
+            raise ValueError(f'unknown augmentation keys {unknown}; known: {augment.TRANSFORM_KEYS}')
+        # the kept tiles change with every draw: one feature table for all tiles, of which an epoch uses the first rows
+        table = torch.empty((len(timelapse) * timelapse.ytiles * timelapse.xtiles, FEATURES), dtype=torch.float32,
+                            device=timelapse.device)
+        warped = torch.empty_like(timelapse.frames)
+        label_xy = augment.label_floats(labels)
+        label_xy = (*label_xy, np.full(len(labels), label_xy[0].shape[1], np.int32))
+        # the draws have a generator of their own, so that replaying them through `transforms` leaves the batch order alone
+        t_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(1)[0])
+        draw = lambda: augment.draw_transform(use_transforms, t_rng)
+        used = []
+        trainer = HeadTrainer(sd, P, max_batch=bs, device=timelapse.device)
+    else:
+        tile_yx = timelapse.tile_yx
+        features = detector.features_frames(timelapse.frames, tile_yx)
+        targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
+        trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
     rng = np.random.default_rng(seed)
     checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
     history = {}
     for epoch in range(epochs):
+        if augmented:
+            tf, warped, tile_yx, lab = _augmented_epoch(timelapse.frames, label_xy, None if transforms is None else
+                                                        transforms[epoch], draw, min_pos_rate, max_redraws, warped)
+            used.append(tf)
+            features = detector.features_frames(warped, tile_yx, out=table)
+            targets = yolo_targets(lab, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         lr = learning_rate(P['LR'], P['LR_DECAYRATE'], epoch)
         rows = []
         for batch in epoch_batches(features.shape[0], bs, P['SHUFFLE'], P['DROP_LAST'], rng):
@@ -259,4 +326,7 @@ def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir
         if dest_dir is not None and epoch in checkpoints:
             os.makedirs(dest_dir, exist_ok=True)
             save_checkpoint(trainer.state_dict(), f'{dest_dir}/E{epoch:04}.pth')
-    return trainer.state_dict(), pd.DataFrame(history, index=list(COMPONENTS))
+    history = pd.DataFrame(history, index=list(COMPONENTS))
+    if augmented:
+        history.attrs['transforms'] = used
+    return trainer.state_dict(), history

@@ -593,6 +593,24 @@ int axt_head_trainer_loss(axt_head_trainer *tr, const float *d_yolo, const float
 int axt_head_trainer_step(axt_head_trainer *tr, const float *d_feat, const int32_t *d_index, int B, const float *d_dy,
                           double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
 
+/* Training augmentation of a whole timelapse in one launch (data_utils.transform_X: translate, then flip, then rotate;
+ * DESIGN.md 6.8e). d_in f32 [T, H, W]; d_out the same shape, not overlapping d_in (AXT_EINVAL: the warp is a gather).
+ * Output pixel (y, x) of every frame reads the source that the inverses give in reverse order:
+ *   rotate != 0: torchvision's TF.rotate(img, angle) for tensors (nearest, no expand, fill 0) = grid_sample(nearest, zeros,
+ *     align_corners=False) on _gen_affine_grid of _get_inverse_affine_matrix([0,0], -angle, [0,0], 1, [0,0]). m00 m01 /
+ *     m10 m11 are that matrix's entries (cos r, sin r / -sin r, cos r with r = radians(-angle)) rounded to f32 by the
+ *     caller. All in f32: base coordinates x - W/2 + 0.5 and y - H/2 + 0.5, the entries divided by 0.5 W (first row) and
+ *     0.5 H (second row), two rounded products and their rounded sum, ((g + 1) * size - 1) / 2, round half to even; a
+ *     source outside the frame gives 0;
+ *   flip_y / flip_x: H-1-y / W-1-x;
+ *   dy, dx (any sign and size): subtracted; a source outside the frame gives 0.
+ * d_occ (may be NULL) u8 [T, ceil(H/512) * ceil(W/512)]: zeroed by the call, then 1 where the OUTPUT frame has a pixel
+ * > 0 in that tile (partial edge tiles count). No atomics: byte-identical from run to run. Asynchronous.
+ * axt_augment_frame_chunk: the frames one workgroup loops over with the source indices it computed once. */
+int axt_augment_frame_chunk(void);
+int axt_augment_frames(const float *d_in, int T, int H, int W, int dy, int dx, int flip_y, int flip_x, int rotate,
+                       float m00, float m01, float m10, float m11, float *d_out, uint8_t *d_occ, void *stream);
+
 /* Integer arc cost used by the flow network (the costs libmot hands its solver at AxonDetections.py:663-690, from
  * observation_model / transition_model, mincostflow_models.py:6-27,67-119): round(cost * 1e6) << 16 | hash16(kind, a, b).
  * kind 0 entry, 1 exit, 2 observation, 3 transition. The low 16 bits make the optimum unique
