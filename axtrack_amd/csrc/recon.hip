@@ -47,6 +47,9 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
+#include <vector>
+
 namespace {
 
 constexpr int LINK_PENDING = -1;      // d_len: the window searches still have to look at this link
@@ -407,6 +410,49 @@ __global__ __launch_bounds__(64) void link_fill_kernel(const int *__restrict__ l
     }
 }
 
+// AXT_PATH_DEBUG only: how many of the selected links each stage of axt_link_paths decided ("none" included), counted on
+// the host from a copy of d_len read back after the stage's launch. A selected link is undecided while its d_len is
+// LINK_PENDING or LINK_EXACT; what a stage decided is by how many the undecided ones fell.
+struct StageCounts {
+    std::vector<char> selected;
+    std::vector<int> len;
+    int n_selected = 0, undecided = 0;
+    int decided[6] = {0, 0, 0, 0, 0, 0};      // gate, bfs31, bfs127, key31, key63, exact
+
+    int init(const int *d_links, int n_links, int cap, const int *d_head_group, int group, hipStream_t st)
+    {
+        std::vector<int> links(3 * (size_t)n_links), head_group;
+        AXT_CHECK_HIP(hipMemcpyAsync(links.data(), d_links, sizeof(int) * links.size(), hipMemcpyDeviceToHost, st));
+        AXT_CHECK_HIP(hipStreamSynchronize(st));
+        if (d_head_group) {
+            int frames = 0;
+            for (int l = 0; l < n_links; ++l) frames = std::max(frames, links[3 * (size_t)l + 1] / cap + 1);
+            head_group.resize(frames);
+            AXT_CHECK_HIP(hipMemcpyAsync(head_group.data(), d_head_group, sizeof(int) * frames, hipMemcpyDeviceToHost, st));
+            AXT_CHECK_HIP(hipStreamSynchronize(st));
+        }
+        selected.resize(n_links);
+        len.resize(n_links);
+        for (int l = 0; l < n_links; ++l) {
+            selected[l] = !d_head_group || head_group[links[3 * (size_t)l + 1] / cap] == group;
+            n_selected += selected[l];
+        }
+        undecided = n_selected;
+        return AXT_OK;
+    }
+
+    int after(int stage, const int *d_len, hipStream_t st)
+    {
+        AXT_CHECK_HIP(hipMemcpyAsync(len.data(), d_len, sizeof(int) * len.size(), hipMemcpyDeviceToHost, st));
+        AXT_CHECK_HIP(hipStreamSynchronize(st));
+        int left = 0;
+        for (size_t l = 0; l < len.size(); ++l) left += selected[l] && len[l] < 0;
+        decided[stage] = undecided - left;
+        undecided = left;
+        return AXT_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" int axt_track_links(const int32_t *d_track, const int32_t *d_count, int n_frames, int cap, int max_gap,
@@ -456,9 +502,15 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
     AxtScratch counters(st, sizeof(int));     // links left for the exact search
     AXT_CHECK_HIP(counters.err);
     AXT_CHECK_HIP(hipMemsetAsync(counters.p, 0, sizeof(int), st));
+    const bool debug = getenv("AXT_PATH_DEBUG") != nullptr;
+    StageCounts stages;
+    if (debug)
+        if (int rc = stages.init(d_links, n_links, cap, d_head_group, group, st)) return rc;
     hipLaunchKernelGGL(link_classify_kernel, dim3(nb), dim3(256), 0, st, d_links, n_links, d_x, d_y, cap, d_head_group, group,
                        mask, label, H, W, max_dist, d_len);
     AXT_LAUNCH_CHECK();
+    if (debug)
+        if (int rc = stages.after(0, d_len, st)) return rc;
     constexpr int R1 = 31, R2 = 127;
     const size_t lds1 = sizeof(unsigned short) * (2 * R1 + 1) * (2 * R1 + 1);
     const size_t lds2 = sizeof(unsigned short) * (2 * R2 + 1) * (2 * R2 + 1);
@@ -467,17 +519,25 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
     hipLaunchKernelGGL((link_bfs_kernel<R1, 256>), dim3(n_links), dim3(256), lds1, st, d_links, d_x, d_y, mask, H, W, max_dist,
                        conn8, 0, d_len, d_stage);
     AXT_LAUNCH_CHECK();
+    if (debug)
+        if (int rc = stages.after(1, d_len, st)) return rc;
     hipLaunchKernelGGL((link_bfs_kernel<R2, 1024>), dim3(n_links), dim3(1024), lds2, st, d_links, d_x, d_y, mask, H, W, max_dist,
                        conn8, 1, d_len, d_stage);
     AXT_LAUNCH_CHECK();
+    if (debug)
+        if (int rc = stages.after(2, d_len, st)) return rc;
     if (off_field && n_comp >= 1) {
         constexpr int K1 = 31, K2 = 63;
         hipLaunchKernelGGL((link_key_kernel<K1, 256>), dim3(n_links), dim3(256), sizeof(unsigned int) * (2 * K1 + 1) * (2 * K1 + 1),
                            st, d_links, d_x, d_y, mask, label, off_field, n_comp, H, W, max_dist, conn8, d_len, d_stage);
         AXT_LAUNCH_CHECK();
+        if (debug)
+            if (int rc = stages.after(3, d_len, st)) return rc;
         hipLaunchKernelGGL((link_key_kernel<K2, 1024>), dim3(n_links), dim3(1024), sizeof(unsigned int) * (2 * K2 + 1) * (2 * K2 + 1),
                            st, d_links, d_x, d_y, mask, label, off_field, n_comp, H, W, max_dist, conn8, d_len, d_stage);
         AXT_LAUNCH_CHECK();
+        if (debug)
+            if (int rc = stages.after(4, d_len, st)) return rc;
     }
     AxtScratch lists(st, sizeof(int) * 5 * (size_t)n_links);
     AXT_CHECK_HIP(lists.err);
@@ -488,7 +548,13 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
     int n_exact = 0;
     AXT_CHECK_HIP(hipMemcpyAsync(&n_exact, counters.p, sizeof(int), hipMemcpyDeviceToHost, st));
     AXT_CHECK_HIP(hipStreamSynchronize(st));
-    if (getenv("AXT_PATH_DEBUG")) fprintf(stderr, "link paths: %d of %d links by the exact search\n", n_exact, n_links);
+    if (debug) {
+        fprintf(stderr, "link paths: %d of %d links by the exact search\n", n_exact, n_links);
+        // (whatever the windows left undecided is the exact search's)
+        fprintf(stderr, "link paths: %d links selected: %d gate, %d bfs31, %d bfs127, %d key31, %d key63, %d exact\n",
+                stages.n_selected, stages.decided[0], stages.decided[1], stages.decided[2], stages.decided[3],
+                stages.decided[4], stages.undecided);
+    }
     if (n_exact == 0) return AXT_OK;
     AxtScratch exact(st, sizeof(int) * ((size_t)n_exact * (max_dist + 1)));
     AXT_CHECK_HIP(exact.err);

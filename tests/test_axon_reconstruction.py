@@ -9,6 +9,7 @@ import pytest
 
 from axtrack_amd import synth, params
 from axtrack_amd.detections import _interp_index, _recon_segments, _recon_frame, _growth_table
+from recon_reference import open_staircase
 
 MAX_DIST = 500
 
@@ -134,20 +135,6 @@ def _expected_links(ad):
     return out
 
 
-def _staircase(xa, ya, xb, yb, W, conn8):
-    sx, sy = (1 if xb >= xa else -1), (1 if yb >= ya else -1)
-    cells = []
-    if conn8:
-        k = min(abs(xb - xa), abs(yb - ya))
-        cells += [(ya + sy * q, xa + sx * q) for q in range(k + 1)]
-        cells += [(ya + sy * k, xa + sx * (k + q)) for q in range(1, abs(xb - xa) - k + 1)]
-        cells += [(ya + sy * (k + q), xb) for q in range(1, abs(yb - ya) - k + 1)]
-    else:
-        cells += [(ya, xa + sx * q) for q in range(abs(xb - xa) + 1)]
-        cells += [(ya + sy * q, xb) for q in range(1, abs(yb - ya) + 1)]
-    return np.array([r * W + c for r, c in cells], np.int64)
-
-
 def _check_open(ad, conn8):
     r = ad.reconstruction_arrays()
     got = set(zip(r['tail_frame'].tolist(), r['tail_slot'].tolist(), r['head_frame'].tolist(), r['head_slot'].tolist(),
@@ -167,7 +154,7 @@ def _check_open(ad, conn8):
             continue
         assert r['len'][l] == coo.getnnz() == len(c)
         assert set(c.tolist()) == set((coo.row * W + coo.col).tolist())
-        assert np.array_equal(c, _staircase(int(x[fa, i]), int(y[fa, i]), int(x[fb, j]), int(y[fb, j]), W, conn8))
+        assert np.array_equal(c, open_staircase(int(x[fa, i]), int(y[fa, i]), int(x[fb, j]), int(y[fb, j]), W, conn8))
     return r
 
 
@@ -228,7 +215,7 @@ def _check_masked(ad, mask_of_link, conn8, oracle=True, sample=None):
         xa, ya, xb, yb = (np.array([v], np.int32) for v in (x[fa, i], y[fa, i], x[fb, j], y[fb, j]))
         c = _path(r, l)
         if m is None:
-            assert np.array_equal(c, _staircase(int(xa[0]), int(ya[0]), int(xb[0]), int(yb[0]), W, conn8))
+            assert np.array_equal(c, open_staircase(int(xa[0]), int(ya[0]), int(xb[0]), int(yb[0]), W, conn8))
             continue
         D, cells = hp.path_cells(*(torch.from_numpy(v).cuda() for v in (xa, ya, xb, yb)), H, W,
                                  torch.from_numpy(m.astype(np.uint8)).cuda(), MAX_DIST, conn8)

@@ -13,6 +13,7 @@ import torch
 
 import hungarian_reference as hr
 import pathsearch_reference as pr
+import recon_reference as rr
 from axtrack_amd import hotpath as hp, params
 
 pytestmark = pytest.mark.gpu
@@ -160,7 +161,9 @@ def test_exact_search_lengths(case):
 @pytest.mark.parametrize('case', pr.battery_x(), ids=repr)
 def test_exact_search_paths(case):
     """hp.path_cells: every path starts at its source, ends at its target, moves between neighbouring cells, visits no cell
-    twice, has the reference's number of cells and costs exactly what the reference's Dijkstra finds."""
+    twice, has the reference's number of cells and costs exactly what the reference's Dijkstra finds; and its cells are
+    the reference walk's (recon_reference.path_cells): among equally cheap paths the one the neighbour order of csrc/grid.h
+    fixes."""
     H, W = case.mask.shape
     D, cells = hp.path_cells(*_xy(case.sources), *_xy(case.targets), H, W, dev(case.mask), case.max_dist, case.conn8)
     D, cells = D.cpu().numpy(), cells.cpu().numpy()
@@ -180,5 +183,7 @@ def test_exact_search_paths(case):
             assert np.all((np.maximum(dr, dq) == 1) if case.conn8 else (dr + dq == 1))
             assert len(set(c.tolist())) == len(c)
             assert wgt[c[1:]].sum() == pr.costs_from(case.mask, case.conn8, sx, sy)[ty, tx]
+            want = rr.path_cells(case.mask, case.conn8, sx, sy, tx, ty, case.max_dist)
+            assert np.array_equal(c, want), f'{case.name}: {(sx, sy)} -> {(tx, ty)}: kernel {c.tolist()}, reference {want.tolist()}'
             checked += 1
     assert checked >= 4
