@@ -74,9 +74,32 @@ class AxonDetections(object):
         self.labelled = False
         self.conn8 = bool(parameters.get('ASTAR_8_CONNECTED', False))
         self.reproduce_label_quirk = bool(parameters.get('REPRODUCE_FRAME_LABEL_QUIRK', True))
-        self._det_tables = None
+        # Every attribute the class reads is created here, at its empty value. The cached ones form two groups with one
+        # reset point each -- whoever adds a cached attribute adds it to one of the two methods, and by that to __init__.
+        self.d_conf = self.d_x = self.d_y = self.d_count = None
+        self._drop_detections()
+        # state that follows neither the detections nor the association: the labels, the target and its fields
+        self._gt = self._gt_ids = self._gt_dev = None
+        self._target_cells, self.reach_px, self.structure_outputchannel_coo, self._target_fields = None, None, None, {}
+
+    def _drop_association(self):
+        """Forget everything that belongs to one association (assign_ids / _set_ided_from_tables)."""
+        self._solved = False
+        self._d_track, self._track_flat_cache = None, None
         self._n_ids, self._n_tracks_dev = None, None
-        self._target_cells, self.structure_outputchannel_coo = None, None
+        self.mcf_total_cost, self.mcf_certificate = None, None
+        self._ided_tables, self.IDed_dets_all, self.IDed_dets_block = None, None, None
+        self._recon = None
+
+    def _drop_detections(self, keep_grids=False):
+        """Forget everything that belongs to one set of detection arrays (d_conf, d_x, d_y, d_count), the association
+        included. keep_grids: the YOLO grids the arrays were decoded from stay (gather_detections: this rank's own)."""
+        self._host, self._det_tables = None, None
+        self._hist, self._shard = None, None
+        self._target_dets, self._target_path_cache = None, None
+        if not keep_grids:
+            self._yolo, self.tile_yx, self._tiled_tables = None, None, None
+        self._drop_association()
 
     @property
     def n_ids(self):
@@ -92,8 +115,7 @@ class AxonDetections(object):
 
     def __len__(self):
         """Number of detection frames (after a multi-GPU gather: of the whole timelapse)."""
-        d_count = getattr(self, 'd_count', None)
-        return int(d_count.shape[0]) if d_count is not None else len(self.timepoint_subset)
+        return int(self.d_count.shape[0]) if self.d_count is not None else len(self.timepoint_subset)
 
     # ------------------------------------------------------------------ caches (AxonDetections.py:141-176)
     def _cache_fname(self, which):
@@ -116,6 +138,7 @@ class AxonDetections(object):
         if hasattr(self.model, 'set_arith'):
             self.model.set_arith(self.P.get('CNN_ARITH', 'f32'))       # read at inference time, like every parameter
         streamed = self._detect_streaming() if getattr(self.dataset, '_pending', False) else None
+        self._drop_detections()
         self.tile_yx = self.dataset.tile_yx
         if not self.tile_yx:
             raise ValueError('the timelapse is empty (no tile has a non-zero pixel)')
@@ -135,7 +158,6 @@ class AxonDetections(object):
         else:
             parts = [self.model.detect_frames(frames, self.tile_yx, t0, n) for t0, n in runs]
             self._yolo = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
-        self._tiled_tables = None
         thr = float(np.float32(self.all_conf_thrs.min()))
         self.d_conf, self.d_x, self.d_y, self.d_count = hp.decode_stitch_nms(
             self._yolo, self.tile_yx, thr, self.nms_min_dist)
@@ -145,8 +167,6 @@ class AxonDetections(object):
             # frame needs (the arc builder's scratch and the frame-to-frame variant scale with the capacity). Frame-sharded
             # ranks agree on a common capacity in gather_detections().
             self._shrink_capacity(int(self.d_count.max().item()))
-        self._det_tables = None
-        self._host = None
         if cache == 'to':
             self.to_cache('_detections', self._detections)
 
@@ -180,6 +200,9 @@ class AxonDetections(object):
     def _shrink_capacity(self, fullest):
         cap = min(-(-max(int(fullest), 1) // 64) * 64, int(self.d_conf.shape[1]))
         self.d_conf, self.d_x, self.d_y = (a[:, :cap].contiguous() for a in (self.d_conf, self.d_x, self.d_y))
+        # gather_detections() can get here with caches filled (tables or histograms read after detect_dataset()): they have
+        # the old capacity. In detect_dataset() everything was dropped a few lines earlier.
+        self._drop_detections(keep_grids=True)
 
     def gather_detections(self, group=None):
         """Frame-sharded runs: every rank has detected its own contiguous block of frames; one
@@ -195,20 +218,22 @@ class AxonDetections(object):
             fullest = self.d_count.max().reshape(1).clone()
             _collective('capacity_allreduce', lambda: dist.all_reduce(fullest, op=dist.ReduceOp.MAX, group=group))
             self._shrink_capacity(int(fullest.item()))
+        gathered_hist = None
         if self.P['MCF_VIS_SIM_WEIGHT'] and dist.is_initialized() and dist.get_world_size(group) > 1:
             # the appearance features need the pixels, which only the owning rank has: they travel with the detections
-            hist, hsum = self._appearance()
+            hist, hsum = self._appearance()               # (of the local arrays: before they are replaced)
             world = dist.get_world_size(group)
             g_hist = torch.empty((world * local,) + tuple(hist.shape[1:]), dtype=hist.dtype, device=hist.device)
             g_hsum = torch.empty((world * local, hsum.shape[1]), dtype=hsum.dtype, device=hsum.device)
             dist.all_gather_into_tensor(g_hist, hist.contiguous(), group=group)
             dist.all_gather_into_tensor(g_hsum, hsum.contiguous(), group=group)
-            self._hist = (g_hist, g_hsum)
+            gathered_hist = (g_hist, g_hsum)
+        self._drop_detections(keep_grids=True)
         self.d_conf, self.d_x, self.d_y, self.d_count = all_gather_detections(
             self.d_conf, self.d_x, self.d_y, self.d_count, group,
             check_shapes=not getattr(self.dataset, '_gather_shapes_agree', False))
         self.dataset._gather_shapes_agree = True          # the shapes follow from the timelapse: checked once
-        self._host, self._det_tables = None, None
+        self._hist = gathered_hist
         if dist.is_initialized() and dist.get_world_size(group) > 1:
             r = dist.get_rank(group)
             self._shard = (r * local, (r + 1) * local, group)       # this rank's frames within the gathered arrays
@@ -217,6 +242,7 @@ class AxonDetections(object):
         """Adopt detection lists that are already arrays (conf f32 [F,cap], x / y i32 [F,cap], count i32 [F], every frame
         in descending confidence): association-only workloads (bench.py --workload assoc-*) and detections produced
         elsewhere. The arrays go to the dataset's device; detect_dataset() is not needed afterwards."""
+        self._drop_detections()
         dev = self.device
         as_dev = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
         self.d_conf, self.d_x, self.d_y, self.d_count = (as_dev(conf, torch.float32), as_dev(x, torch.int32), as_dev(y, torch.int32),
@@ -224,11 +250,10 @@ class AxonDetections(object):
         if self.d_conf.dim() != 2 or self.d_x.shape != self.d_conf.shape or self.d_y.shape != self.d_conf.shape \
                 or self.d_count.shape != (self.d_conf.shape[0],):
             raise ValueError('conf, x, y must be [F, cap] and count [F]')
-        self._host, self._det_tables, self._yolo, self._tiled_tables = None, None, None, None
 
     def _host_dets(self):
         """(count i32 [F], conf f32 [F,cap], x, y) on the host, fetched once."""
-        if getattr(self, '_host', None) is None:
+        if self._host is None:
             self._host = (self.d_count.cpu().numpy(), self.d_conf.cpu().numpy(), self.d_x.cpu().numpy(),
                           self.d_y.cpu().numpy())
         return self._host
@@ -244,8 +269,8 @@ class AxonDetections(object):
             conf[f, :n] = t.conf.to_numpy(dtype=np.float32)
             x[f, :n] = t.anchor_x.to_numpy(dtype=np.int32)
             y[f, :n] = t.anchor_y.to_numpy(dtype=np.int32)
-        dev = self.device
-        self.d_conf, self.d_x, self.d_y, self.d_count = (torch.from_numpy(a).to(dev) for a in (conf, x, y, cnt))
+        self._drop_detections()
+        self.d_conf, self.d_x, self.d_y, self.d_count = (torch.from_numpy(a).to(self.device) for a in (conf, x, y, cnt))
         self._host, self._det_tables = (cnt, conf, x, y), list(tables)
 
     @property
@@ -272,11 +297,10 @@ class AxonDetections(object):
         hot path never needs them (its kernel goes from the YOLO grids to the frame's final list), so they are decoded
         from the grids on the host when first asked for: f32 arithmetic, half-to-even rounding, all-zero cells left
         at zero, exactly as :192-210."""
-        if getattr(self, '_tiled_tables', None) is None:
-            yolo = getattr(self, '_yolo', None)
-            if yolo is None:
+        if self._tiled_tables is None:
+            if self._yolo is None:
                 raise ValueError('the tile tables come from the YOLO grids: run detect_dataset() (not from a cache)')
-            y = yolo.cpu().numpy().astype(np.float32, copy=False)            # [F, n_tiles, Sx, Sy, 3]
+            y = self._yolo.cpu().numpy().astype(np.float32, copy=False)            # [F, n_tiles, Sx, Sy, 3]
             ii = np.arange(self.Sx, dtype=np.float32).reshape(1, 1, self.Sx, 1)
             jj = np.arange(self.Sy, dtype=np.float32).reshape(1, 1, 1, self.Sy)
             ts = np.float32(self.tilesize)
@@ -421,18 +445,15 @@ class AxonDetections(object):
         """AxonDetections.py:505-524. astar_paths_cache: 'from' adopts the path lengths of a
         '{name}_astar_dets_paths.pkl' (the reference's format: per frame pair a nested list of coo matrices / None)
         instead of computing them; 'to' writes such a file (astar_dets_paths)."""
-        self._len_table = _len_table
-        self._recon = None                                  # the reconstructions belong to one association
-        if assigedIDs_cache != 'from':
-            if astar_paths_cache == 'from':
-                self._len_table = self._length_table_from_paths(self.from_cache('astar_dets_paths'))
-            elif astar_paths_cache == 'to':
-                self.to_cache('astar_dets_paths', self.astar_dets_paths())
+        self._drop_association()
         if assigedIDs_cache == 'from':
             self._set_ided_from_tables(self.from_cache('_IDed_detections'))
         else:
-            self._solved = self._assign_IDs_to_detections()
-            self._ided_tables = None
+            if astar_paths_cache == 'from':
+                _len_table = self._length_table_from_paths(self.from_cache('astar_dets_paths'))
+            elif astar_paths_cache == 'to':
+                self.to_cache('astar_dets_paths', self.astar_dets_paths())
+            self._solved = self._assign_IDs_to_detections(_len_table)
             if assigedIDs_cache == 'to' and self._solved:
                 self.to_cache('_IDed_detections', self._IDed_detections)
         self.IDed_dets_all = self._agg_all_IDed_dets() if self._solved else None
@@ -442,7 +463,7 @@ class AxonDetections(object):
         """list of per-frame DataFrames of the IDed detections, rows sorted by ID, index Axon_{id:03}
         (libmot_det2det, AxonDetections.py:786-823); None if the flow problem was infeasible (:691-696).
         Built on first access -- the hot path itself only keeps arrays."""
-        if not getattr(self, '_solved', False):
+        if not self._solved:
             return None
         if self._ided_tables is None:
             cnt, conf, x, y = self._host_dets()
@@ -465,8 +486,9 @@ class AxonDetections(object):
 
     def _set_ided_from_tables(self, tables):
         """Adopt reference-format per-frame IDed tables (the '_IDed_detections' cache)."""
+        self._drop_association()
         cnt, conf, x, y = self._host_dets()
-        offs = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        offs = self._offs
         track = np.full(int(offs[-1]), -1, np.int32)
         for f, t in enumerate(tables):
             if len(t) == 0:
@@ -475,28 +497,32 @@ class AxonDetections(object):
             for name, ax, ay in zip(t.index, tx, ty):
                 k = np.nonzero((x[f, :cnt[f]] == ax) & (y[f, :cnt[f]] == ay))[0][0]   # exact anchor match (:804-808)
                 track[offs[f] + k] = _axon_number(name)
-        self._track_flat_cache, self._d_track = track, None
-        self.n_ids = None                                           # unknown: ids are whatever the cache holds
+        self._track_flat_cache = track                              # (n_ids stays None: ids are whatever the cache holds)
         self._solved, self._ided_tables = True, list(tables)
+
+    def _frame_pairs(self):
+        """(t, t_bef, label) of every frame pair the tracker may link: t_bef = t-1 .. t-(MCF_MAX_NUM_MISSES+1), not before
+        frame 0, in the order and with the labels of the reference's loops (AxonDetections.py:544-556) -- the order of the
+        'astar_dets_paths' cache's dictionary."""
+        gaps = self.P['MCF_MAX_NUM_MISSES'] + 1
+        for t in range(len(self)):
+            for t_bef in range(t - 1, max(t - gaps, 0) - 1, -1):
+                yield t, t_bef, f'{self.dataset.name}_t:{t:0>3}-t:{t_bef:0>3}'
 
     def astar_dists(self):
         """_get_astar_path_distances(_compute_detections_astar_paths()) (AxonDetections.py:526-585,717-752):
         dict '{name}_t:{t:03}-t:{t_bef:03}' -> int array [N_t_bef, N_t], computed on the GPU per pair."""
         cnt = self._host_dets()[0]
         out = {}
-        for t in range(len(self)):
-            mask = self._mask_dev(t)                       # _get_maskweights(t), AxonDetections.py:557
-            for t_bef in range(t - 1, t - (self.P['MCF_MAX_NUM_MISSES'] + 2), -1):
-                if t_bef < 0:
-                    continue
-                na, nb = int(cnt[t_bef]), int(cnt[t])
-                lbl = f'{self.dataset.name}_t:{t:0>3}-t:{t_bef:0>3}'
-                if na == 0:
-                    out[lbl] = np.array([])
-                    continue
-                D = hp.path_cost(self.d_x[t_bef, :na], self.d_y[t_bef, :na], self.d_x[t, :nb], self.d_y[t, :nb],
-                                 self.dataset.sizey, self.dataset.sizex, mask, self.max_px_assoc_dist, self.conn8)
-                out[lbl] = D.cpu().numpy()
+        for t, t_bef, lbl in self._frame_pairs():
+            na, nb = int(cnt[t_bef]), int(cnt[t])
+            if na == 0:
+                out[lbl] = np.array([])
+                continue
+            D = hp.path_cost(self.d_x[t_bef, :na], self.d_y[t_bef, :na], self.d_x[t, :nb], self.d_y[t, :nb],
+                             self.dataset.sizey, self.dataset.sizex, self._mask_dev(t),      # _get_maskweights(t), AxonDetections.py:557
+                             self.max_px_assoc_dist, self.conn8)
+            out[lbl] = D.cpu().numpy()
         return out
 
     def _length_table_from_dists(self, dists):
@@ -504,13 +530,10 @@ class AxonDetections(object):
         the arc builder reads (0 = none)."""
         F, cap, gaps = len(self), self.d_x.shape[1], self.P['MCF_MAX_NUM_MISSES'] + 1
         table = np.zeros((F, cap, gaps, cap), np.int16)
-        for t in range(F):
-            for t_bef in range(t - 1, t - (gaps + 1), -1):
-                if t_bef < 0:
-                    continue
-                D = dists[f'{self.dataset.name}_t:{t:0>3}-t:{t_bef:0>3}']
-                if D.ndim == 2 and D.size:
-                    table[t_bef, :D.shape[0], t - t_bef - 1, :D.shape[1]] = np.where(D >= self.max_px_assoc_dist, 0, D)
+        for t, t_bef, lbl in self._frame_pairs():
+            D = dists[lbl]
+            if D.ndim == 2 and D.size:
+                table[t_bef, :D.shape[0], t - t_bef - 1, :D.shape[1]] = np.where(D >= self.max_px_assoc_dist, 0, D)
         return torch.from_numpy(table).to(self.device)
 
     def _length_table_from_paths(self, paths):
@@ -519,15 +542,12 @@ class AxonDetections(object):
         cnt = self._host_dets()[0]
         F, cap, gaps = len(self), self.d_x.shape[1], self.P['MCF_MAX_NUM_MISSES'] + 1
         table = np.zeros((F, cap, gaps, cap), np.int16)
-        for t in range(F):
-            for t_bef in range(t - 1, t - (gaps + 1), -1):
-                if t_bef < 0:
-                    continue
-                rows = paths[f'{self.dataset.name}_t:{t:0>3}-t:{t_bef:0>3}']
-                if len(rows) != cnt[t_bef] or any(len(r) != cnt[t] for r in rows):
-                    raise ValueError(f'cached paths of t:{t}-t:{t_bef} do not match the detections')
-                for i, row in enumerate(rows):
-                    table[t_bef, i, t - t_bef - 1, :len(row)] = [0 if p is None else min(p.getnnz(), 32767) for p in row]
+        for t, t_bef, lbl in self._frame_pairs():
+            rows = paths[lbl]
+            if len(rows) != cnt[t_bef] or any(len(r) != cnt[t] for r in rows):
+                raise ValueError(f'cached paths of t:{t}-t:{t_bef} do not match the detections')
+            for i, row in enumerate(rows):
+                table[t_bef, i, t - t_bef - 1, :len(row)] = [0 if p is None else min(p.getnnz(), 32767) for p in row]
         return torch.from_numpy(table).to(self.device)
 
     def astar_dets_paths(self):
@@ -539,7 +559,6 @@ class AxonDetections(object):
         of the equally short paths pyastar2d returns is unpinned; lengths are what the tracker
         uses). On a masked grid the GPU search walks back from every target along its distance field
         (axt_path_cells)."""
-        from scipy import sparse
         if self.dataset.masked:
             return self._masked_dets_paths()
         return self._open_dets_paths(self.astar_dists())
@@ -585,36 +604,24 @@ class AxonDetections(object):
         cnt = self._host_dets()[0]
         H, W = self.dataset.sizey, self.dataset.sizex
         out = {}
-        for t in range(len(self)):
+        for t, t_bef, lbl in self._frame_pairs():
             grid = self._mask_dev(t)
-            for t_bef in range(t - 1, t - (self.P['MCF_MAX_NUM_MISSES'] + 2), -1):
-                if t_bef < 0:
-                    continue
-                na, nb = int(cnt[t_bef]), int(cnt[t])
-                lbl = f'{self.dataset.name}_t:{t:0>3}-t:{t_bef:0>3}'
-                if na == 0 or nb == 0:
-                    out[lbl] = [[] for _ in range(na)]
-                    continue
-                if grid is None:
-                    # a frame of a time-varying mask that is all ones: the closed-form staircase of the open grid
-                    D = hp.path_cost(self.d_x[t_bef, :na], self.d_y[t_bef, :na], self.d_x[t, :nb], self.d_y[t, :nb],
-                                     H, W, None, self.max_px_assoc_dist, self.conn8).cpu().numpy()
-                    out.update(self._open_dets_paths({lbl: D}))
-                    continue
-                D, cells = hp.path_cells(self.d_x[t_bef, :na], self.d_y[t_bef, :na], self.d_x[t, :nb], self.d_y[t, :nb],
-                                         H, W, grid, self.max_px_assoc_dist, self.conn8)
-                D, cells = D.cpu().numpy(), cells.cpu().numpy()
-                rows = []
-                for i in range(na):
-                    row = []
-                    for j in range(nb):
-                        if D[i, j] >= self.max_px_assoc_dist:
-                            row.append(None)
-                            continue
-                        c = cells[i, j, :D[i, j]]
-                        row.append(sparse.coo_matrix((np.ones(len(c)), (c // W, c % W)), (H, W), bool))
-                    rows.append(row)
-                out[lbl] = rows
+            na, nb = int(cnt[t_bef]), int(cnt[t])
+            if na == 0 or nb == 0:
+                out[lbl] = [[] for _ in range(na)]
+                continue
+            if grid is None:
+                # a frame of a time-varying mask that is all ones: the closed-form staircase of the open grid
+                D = hp.path_cost(self.d_x[t_bef, :na], self.d_y[t_bef, :na], self.d_x[t, :nb], self.d_y[t, :nb],
+                                 H, W, None, self.max_px_assoc_dist, self.conn8).cpu().numpy()
+                out.update(self._open_dets_paths({lbl: D}))
+                continue
+            D, cells = hp.path_cells(self.d_x[t_bef, :na], self.d_y[t_bef, :na], self.d_x[t, :nb], self.d_y[t, :nb],
+                                     H, W, grid, self.max_px_assoc_dist, self.conn8)
+            D, cells = D.cpu().numpy(), cells.cpu().numpy()
+            coo = lambda c: sparse.coo_matrix((np.ones(len(c)), (c // W, c % W)), (H, W), bool)
+            out[lbl] = [[None if D[i, j] >= self.max_px_assoc_dist else coo(cells[i, j, :D[i, j]]) for j in range(nb)]
+                        for i in range(na)]
         return out
 
     def search_MCF_params(self, edge_cost_thr_values=(.4, .6, .7, .8, .9, 1, 1.2, 3),
@@ -660,11 +667,11 @@ class AxonDetections(object):
     def _appearance(self):
         """feature_model's histograms of every detection (device tensors hist f32 [F,cap,180], sums f64 [F,cap]),
         computed once from the centre frames (AxonDetections.py:682-685)."""
-        if getattr(self, '_hist', None) is None:
+        if self._hist is None:
             if hasattr(self.dataset, 'make_resident'):
                 self.dataset.make_resident()            # (a host-resident timelapse that has not been streamed yet)
             frames, off = self.dataset.frames, 2
-            if not isinstance(self.timepoint_subset, range) and getattr(self, '_shard', None) is None:
+            if not isinstance(self.timepoint_subset, range) and self._shard is None:
                 # the centre frames of the subset. (The reference hands the tracker get_frame_and_truedets(i) with i the POSITION in
                 # the subset, AxonDetections.py:679-685 -- the image of dataset frame i, not of timepoint_subset[i]; only visible
                 # with MCF_VIS_SIM_WEIGHT > 0 under a subset, and not reproduced: the crops here belong to the detections.)
@@ -737,119 +744,126 @@ class AxonDetections(object):
         row_ptr[n_det + 1:] = row_ptr[n_det]
         return row_ptr, col, length, gap_a, cost
 
-    def _assign_IDs_to_detections(self):
+    def _assign_IDs_to_detections(self, len_table=None):
         """AxonDetections.py:631-715 with the tracker replaced by axt_build_arcs + axt_mcf_solve
         (parameters['ASSOCIATION'] = 'mcf', the default and the reference's behaviour) or by the
-        frame-to-frame Hungarian variant of BASELINE config 3 ('hungarian')."""
-        P = self.P
-        vis_w = P['MCF_VIS_SIM_WEIGHT']
-        dmax, units = _cost_units_on_device(P, self.max_px_assoc_dist, self.device)
-        mode = P.get('ASSOCIATION', 'mcf')
-        masked = self.dataset.masked
-        varying = self.dataset.mask3d is not None
-        shard = getattr(self, '_shard', None)           # set by gather_detections(): solve only this rank's frame pairs
+        frame-to-frame Hungarian variant of BASELINE config 3 ('hungarian'). len_table: path lengths that are already
+        known (a path cache, search_MCF_params), read by the flow tracker. True if identities were assigned. The caller has
+        dropped the previous association (_drop_association): only what the variant computes is installed."""
+        dmax, units = _cost_units_on_device(self.P, self.max_px_assoc_dist, self.device)
+        mode = self.P.get('ASSOCIATION', 'mcf')
         if mode == 'hungarian':
-            ctab = None
-            if vis_w or varying:
-                # the appearance term: the link costs are those of the flow tracker's arcs (axt_build_arcs_vis: the same
-                # admission, the same integers), scattered into a dense table per frame pair
-                # (likewise a mask that changes over time: one pass of the arc builder per distinct mask)
-                vis = None
-                if vis_w:
-                    hist, hsum = self._appearance()
-                    vis = dict(hist=hist, hsum=hsum, weight=vis_w, miss_rate=P['MCF_MISS_RATE'], thr=P['MCF_EDGE_COST_THR'])
-                len_table = None
-                if masked and max(dmax) - 1 > 250:       # beyond the hot-path search window: the exact lengths (as for 'mcf')
-                    len_table = self._length_table_from_dists(self.astar_dists())
-                if varying and len_table is None:
-                    row_ptr, col, _, gap, cost = self._build_arcs_time_varying(dmax, units, vis, None)
-                else:
-                    row_ptr, col, _, gap, cost = hp.build_arcs(self.d_x, self.d_y, self.d_count, self.dataset.sizey,
-                                                               self.dataset.sizex, dmax, units,
-                                                               None if varying else self._mask_dev(),
-                                                               self.max_px_assoc_dist, self.conn8, vis, len_table, None)
-                ctab = self._hungarian_cost_table(row_ptr, col, gap, cost, len(dmax))
-            track, n_tracks = hp.hungarian_assoc(self.d_x, self.d_y, self.d_count, self.dataset.sizey,
-                                                 self.dataset.sizex, dmax, units,
-                                                 int(np.rint(P['MCF_EDGE_COST_THR'] * 1e6)),
-                                                 self.max_px_assoc_dist, self.conn8,
-                                                 *(((shard[0], shard[1]), shard[2]) if shard else (None, None)),
-                                                 mask=self._mask_dev() if (masked and ctab is None) else None, ctab=ctab)
-            self._d_track, self._track_flat_cache = track, None       # host copies are made on first use only
-            self._n_ids, self._n_tracks_dev, self.mcf_total_cost = None, n_tracks, None      # (the count stays on the device)
-            return True
+            return self._associate_hungarian(dmax, units)
         if mode != 'mcf':
             raise ValueError(f"parameters['ASSOCIATION'] must be 'mcf' or 'hungarian', got {mode!r}")
-        obs = hp.obs_costs(self.d_conf, self.d_count, P['MCF_CONF_CAPPING_METHOD'], P['MCF_MAX_CONF_COST'])
-        vis = None
-        if vis_w:
-            hist, hsum = self._appearance()
-            vis = dict(hist=hist, hsum=hsum, weight=vis_w, miss_rate=P['MCF_MISS_RATE'], thr=P['MCF_EDGE_COST_THR'])
-        len_table = getattr(self, '_len_table', None)
-        if len_table is None and masked and max(dmax) - 1 > 250:
+        return self._associate_mcf(dmax, units, len_table)
+
+    def _appearance_term(self):
+        """The appearance term of the link costs as the arc builder takes it; None without one (MCF_VIS_SIM_WEIGHT = 0)."""
+        P = self.P
+        if not P['MCF_VIS_SIM_WEIGHT']:
+            return None
+        hist, hsum = self._appearance()
+        return dict(hist=hist, hsum=hsum, weight=P['MCF_VIS_SIM_WEIGHT'], miss_rate=P['MCF_MISS_RATE'], thr=P['MCF_EDGE_COST_THR'])
+
+    def _exact_lengths_if_needed(self, dmax, given=None):
+        """The path-length table the arc builder reads instead of searching: `given`, the exact lengths, or None."""
+        if given is None and self.dataset.masked and max(dmax) - 1 > 250:
             # the hot-path searches of the arc builder cover paths of up to 251 cells (the deployed threshold admits
             # exactly that); wider thresholds take the exact, slower search over the whole range
-            len_table = self._length_table_from_dists(self.astar_dists())
+            return self._length_table_from_dists(self.astar_dists())
+        return given
+
+    def _arcs(self, dmax, units, vis, len_table, src_count):
+        """(row_ptr, col, length, gap, cost) of hotpath.build_arcs for these detections: one pass, or under a mask that
+        changes over time (and without a length table, which already holds every pair's own mask) one pass per mask."""
+        varying = self.dataset.mask3d is not None
+        if varying and len_table is None:
+            return self._build_arcs_time_varying(dmax, units, vis, src_count)
+        mask = None if varying else self._mask_dev()
+        return hp.build_arcs(self.d_x, self.d_y, self.d_count, self.dataset.sizey, self.dataset.sizex, dmax, units, mask,
+                             self.max_px_assoc_dist, self.conn8, vis, len_table, src_count)
+
+    def _associate_hungarian(self, dmax, units):
+        """The frame-to-frame variant: installs the tracks and the identity count, both on the device. Returns True."""
+        vis = self._appearance_term()
+        shard = self._shard                             # set by gather_detections(): solve only this rank's frame pairs
+        ctab = None
+        if vis is not None or self.dataset.mask3d is not None:
+            # the appearance term: the link costs are those of the flow tracker's arcs (axt_build_arcs_vis: the same
+            # admission, the same integers), scattered into a dense table per frame pair
+            # (likewise a mask that changes over time: one pass of the arc builder per distinct mask)
+            row_ptr, col, _, gap, cost = self._arcs(dmax, units, vis, self._exact_lengths_if_needed(dmax), None)
+            ctab = self._hungarian_cost_table(row_ptr, col, gap, cost, len(dmax))
+        mask = self._mask_dev() if (self.dataset.masked and ctab is None) else None
+        # (host copies of the tracks are made on first use only, and the count stays on the device)
+        self._d_track, self._n_tracks_dev = hp.hungarian_assoc(
+            self.d_x, self.d_y, self.d_count, self.dataset.sizey, self.dataset.sizex, dmax, units,
+            int(np.rint(self.P['MCF_EDGE_COST_THR'] * 1e6)), self.max_px_assoc_dist, self.conn8,
+            *(((shard[0], shard[1]), shard[2]) if shard else (None, None)), mask=mask, ctab=ctab)
+        return True
+
+    def _node_costs_int(self, obs, n_det):
+        """The integer node costs (axt_arc_cost_int: round(cost * 1e6) << 16 | identity hash): the observation costs on the
+        device, beside the arcs' (the numpy version of the same arithmetic took 57 ms for config 4's 319 k detections);
+        entry / exit depend on the count and the price only and are kept, read-only: solves and certificates share them."""
+        valid = torch.arange(self.d_conf.shape[1], device=self.device)[None, :] < self.d_count[:, None]
+        k = torch.arange(n_det, dtype=torch.int64, device=self.device)
+        obs_int = _arc_cost_int_torch(torch.round(obs[valid] * 1e6).to(torch.int64), 2, k, 0)
+        ee = float(self.P['MCF_ENTRY_EXIT_COST'])
+        key = (n_det, ee, str(self.device))
+        if _ENTRY_EXIT_CACHE.get('key') != key:
+            units = torch.full((n_det,), int(np.rint(ee * 1e6)), dtype=torch.int64, device=self.device)
+            entry, exit_ = (_arc_cost_int_torch(units, kind, k, 0).cpu().numpy() for kind in (0, 1))
+            entry.setflags(write=False)
+            exit_.setflags(write=False)
+            _ENTRY_EXIT_CACHE.update(key=key, entry=entry, exit=exit_)
+        return obs_int, _ENTRY_EXIT_CACHE['entry'], _ENTRY_EXIT_CACHE['exit']
+
+    def _associate_mcf(self, dmax, units, len_table):
+        """The global min-cost flow: installs the tracks (host), the identity count, the total cost and, if asked for, the
+        certificate. Returns False, installing nothing, when the flow problem is infeasible."""
+        P = self.P
+        shard = self._shard                             # set by gather_detections(): build only this rank's arc rows
+        obs = hp.obs_costs(self.d_conf, self.d_count, P['MCF_CONF_CAPPING_METHOD'], P['MCF_MAX_CONF_COST'])
+        vis = self._appearance_term()
+        len_table = self._exact_lengths_if_needed(dmax, len_table)
         src_count = None
-        if shard is not None and (masked or vis is not None or len_table is not None):
+        if shard is not None and (self.dataset.masked or vis is not None or len_table is not None):
             # frame-sharded: this rank builds the arc rows of its own frames, one all-gather joins them (the path
             # searches of a masked grid / the appearance distances are the expensive part of the association and shard
             # with the frames). On an all-ones mask the arcs are closed-form and cheaper to rebuild on every rank than to
             # exchange: the all-gather of the detections is then the ONLY collective before the replicated flow solve.
             src_count = torch.zeros_like(self.d_count)
             src_count[shard[0]:shard[1]] = self.d_count[shard[0]:shard[1]]
-        if varying and len_table is None:
-            row_ptr, col, length, gap, cost = self._build_arcs_time_varying(dmax, units, vis, src_count)
-        else:
-            row_ptr, col, length, gap, cost = hp.build_arcs(self.d_x, self.d_y, self.d_count, self.dataset.sizey,
-                                                            self.dataset.sizex, dmax, units,
-                                                            None if varying else self._mask_dev(),
-                                                            self.max_px_assoc_dist, self.conn8, vis, len_table, src_count)
-        cnt, conf, x, y = self._host_dets()
+        row_ptr, col, length, gap, cost = self._arcs(dmax, units, vis, len_table, src_count)
+        n_det = int(self._offs[-1])
         if src_count is not None:
             from . import sharded
-            row_ptr, col, length, gap, cost = sharded.all_gather_arcs(row_ptr, col, length, gap, cost, int(cnt.sum()),
-                                                                      shard[2])
-        offs = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        n_det = int(offs[-1])
-        # the integer node costs (axt_arc_cost_int: round(cost * 1e6) << 16 | identity hash) on the device, beside the arcs' (the
-        # numpy version of the same arithmetic took 57 ms for config 4's 319 k detections); entry / exit depend on the count
-        # and the price only and are kept
-        valid = torch.arange(conf.shape[1], device=self.device)[None, :] < self.d_count[:, None]
-        k = torch.arange(n_det, dtype=torch.int64, device=self.device)
-        obs_int = _arc_cost_int_torch(torch.round(obs[valid] * 1e6).to(torch.int64), 2, k, 0)
-        ee = float(P['MCF_ENTRY_EXIT_COST'])
-        key = (n_det, ee, str(self.device))
-        if _ENTRY_EXIT_CACHE.get('key') != key:
-            units = torch.full((n_det,), int(np.rint(ee * 1e6)), dtype=torch.int64, device=self.device)
-            _ENTRY_EXIT_CACHE.update(key=key, entry=_arc_cost_int_torch(units, 0, k, 0).cpu().numpy(),
-                                     exit=_arc_cost_int_torch(units, 1, k, 0).cpu().numpy())
-        entry_int, exit_int = _ENTRY_EXIT_CACHE['entry'], _ENTRY_EXIT_CACHE['exit']
+            row_ptr, col, length, gap, cost = sharded.all_gather_arcs(row_ptr, col, length, gap, cost, n_det, shard[2])
+        obs_int, entry_int, exit_int = self._node_costs_int(obs, n_det)
         obs_int, row_ptr_h, col_h, cost_h = hp.to_host(obs_int, row_ptr[:n_det + 1], col, cost)       # (pinned staging: 120 MB at config 4)
         net = (obs_int, entry_int, exit_int, row_ptr_h, col_h, cost_h)
         # parameters['MCF_CERTIFICATE'] (not a key of the reference): also return the node potentials that prove the optimum
         # (axt_mcf_solve_duals) and keep them, with the network they refer to, in self.mcf_certificate
         want_cert = bool(P.get('MCF_CERTIFICATE', False))
-        self.mcf_certificate = None
         if shard is not None and P.get('MCF_SHARDED_SOLVE', True):
             # frame-sharded: every rank solves its run of time blocks, one all-gather joins the runs (sharded.solve_flow)
             from . import sharded
             res = sharded.solve_flow(*net, P['MCF_MIN_FLOW'], P['MCF_MAX_FLOW'], shard[2], self.device, duals=want_cert)
         else:
             res = hp.mcf_solve(*net, P['MCF_MIN_FLOW'], P['MCF_MAX_FLOW'], duals=want_cert)
-        if res is not None and want_cert:
-            self.mcf_certificate = dict(obs=net[0].copy(), entry=net[1], exit=net[2], row_ptr=net[3].copy(), col=net[4].copy(),
-                                        cost=net[5].copy(), next=res[0], track=res[1], total_cost=res[3], potentials=res[4],
-                                        min_flow=P['MCF_MIN_FLOW'], max_flow=P['MCF_MAX_FLOW'])
-            res = res[:4]
         if res is None:
             print('Could not solve the graph for identity association; -> no IDed detections. Try narrowing '
                   'expected identities by updating parameters[`MCF_MIN_FLOW`, `MCF_MAX_FLOW`]. '
                   f"Currently: {P['MCF_MIN_FLOW']} to {P['MCF_MAX_FLOW']}.")
             return False
-        nxt, track, n_tracks, total = res
-        self.mcf_total_cost, self.n_ids = total, n_tracks
-        self._track_flat_cache, self._d_track = track, None
+        if want_cert:
+            self.mcf_certificate = dict(obs=net[0].copy(), entry=net[1], exit=net[2], row_ptr=net[3].copy(), col=net[4].copy(),
+                                        cost=net[5].copy(), next=res[0], track=res[1], total_cost=res[3], potentials=res[4],
+                                        min_flow=P['MCF_MIN_FLOW'], max_flow=P['MCF_MAX_FLOW'])
+        _, track, n_tracks, total = res[:4]
+        self._track_flat_cache, self.n_ids, self.mcf_total_cost = track, n_tracks, total
         return True
 
     def _hungarian_cost_table(self, row_ptr, col, gap, cost, gaps):
@@ -880,7 +894,7 @@ class AxonDetections(object):
     @property
     def _track_flat(self):
         """Trajectory id of every detection in flat numbering on the host, i32 [n_det] (-1: none)."""
-        if getattr(self, '_track_flat_cache', None) is None:
+        if self._track_flat_cache is None:
             cnt = self._host_dets()[0]
             track_h = self._d_track.cpu().numpy()
             self._track_flat_cache = track_h[np.arange(track_h.shape[1])[None, :] < cnt[:, None]]
@@ -905,9 +919,8 @@ class AxonDetections(object):
         frames x ids, so it is filled on the GPU (axt_ided_table) and copied once into pinned host memory,
         which the DataFrame then wraps without another copy."""
         track = self._track_dev()                                   # i32 [F,cap], -1 = no ID / empty slot
-        shard = getattr(self, '_shard', None)
-        if shard is not None:
-            return self._ided_block(track, shard[0], shard[1])
+        if self._shard is not None:
+            return self._ided_block(track, self._shard[0], self._shard[1])
         key = (int(track.shape[0]), int(track.shape[1]))
         if self._n_ids is None and self._n_tracks_dev is not None and key in _IDS_GUESS:
             # The number of identities is still on the device, and fetching it first would hold the host -- and with it the
@@ -967,12 +980,12 @@ class AxonDetections(object):
         interpolate_missing=False): 'interp_axon_id', 'interp_frame', 'interp_x', 'interp_y', 'interp_link' and
         'interp_index' (position along the link's path, _interp_index). The GPU work (hotpath.track_links +
         hotpath.link_paths) runs once per assign_ids() and is cached."""
-        if getattr(self, '_shard', None) is not None:
+        if self._shard is not None:
             raise NotImplementedError('axon reconstructions of a frame-sharded run are not implemented: reconstruct in a '
                                       'single process (AxonDetections without gather_detections)')
-        if not getattr(self, '_solved', False):
+        if not self._solved:
             raise ValueError('no identities: run assign_ids() first (or the association was infeasible)')
-        if getattr(self, '_recon', None) is None:
+        if self._recon is None:
             self._recon = self._trace_links()
         r = dict(self._recon)
         if not interpolate_missing:
@@ -1023,8 +1036,7 @@ class AxonDetections(object):
         columns (REPRODUCE_FRAME_LABEL_QUIRK)."""
         r = self.reconstruction_arrays(interpolate_missing)
         seg = _recon_segments(r, interpolate_missing)
-        names = None if axon_name is None else ([axon_name] if isinstance(axon_name, str) else list(axon_name))
-        return _recon_frame(seg, r['cells'], r['shape'], t, names, include_history, ymin, ymax, xmin, xmax)
+        return _recon_frame(seg, r['cells'], r['shape'], t, _name_list(axon_name), include_history, ymin, ymax, xmin, xmax)
 
     def _reconstruct_axons(self):
         """AxonDetections.py:924-928: the reconstructions of the whole timelapse."""
@@ -1045,12 +1057,12 @@ class AxonDetections(object):
 
     # ------------------------------------------------------------------ target screens (video_plotting.py:170-177,308-309)
     def _require_target(self, ids=False):
-        if getattr(self, '_shard', None) is not None:
+        if self._shard is not None:
             raise NotImplementedError('target screens of a frame-sharded run are not implemented: screen in a single '
                                       'process (AxonDetections without gather_detections)')
-        if getattr(self, '_target_cells', None) is None:
+        if self._target_cells is None:
             raise ValueError('no target: call set_target() first')
-        if ids and not getattr(self, '_solved', False):
+        if ids and not self._solved:
             raise ValueError('no identities: run assign_ids() first (or the association was infeasible)')
 
     def set_target(self, target, reach_px=None):
@@ -1099,8 +1111,7 @@ class AxonDetections(object):
         """(off, moves) of every detection slot on the device, i32 [F, cap] (-1: empty slot or outside the grid), with the
         fields, grids and per-frame field index they were read from."""
         self._require_target()
-        key = (self.d_x.data_ptr(), self.d_count.data_ptr(), self.conn8)
-        if self._target_dets is None or self._target_dets[0] != key:
+        if self._target_dets is None:                               # (valid until the detections or the target change)
             grids, index = self._target_groups()
             fields = [self._target_field_of_group(g, grid) for g, grid in enumerate(grids)]
             if index is None:
@@ -1109,9 +1120,8 @@ class AxonDetections(object):
                 off, moves = torch.stack([f[0] for f in fields]), torch.stack([f[1] for f in fields])
                 d_index = torch.from_numpy(index).to(self.device)
             d_off, d_moves = hp.target_sample(off, moves, self.d_x, self.d_y, self.d_count, d_index)
-            self._target_dets = (key, d_off, d_moves, fields, grids, d_index)
-            self._target_path_cache = None
-        return self._target_dets[1:]
+            self._target_dets = (d_off, d_moves, fields, grids, d_index)
+        return self._target_dets
 
     def target_arrays(self):
         """(frame, axon_id, x, y, off, moves) of every IDed detection, frame-major like ided_arrays(): off / moves = the
@@ -1170,9 +1180,8 @@ class AxonDetections(object):
             raise ValueError(f'frame {t} lies outside the timelapse [0, {len(self)})')
         ptr, cells = self._target_paths()
         ids, slots = self._target_path_slots(int(t))
-        names = None if axon_name is None else ([axon_name] if isinstance(axon_name, str) else list(axon_name))
         H, W = self.dataset.sizey, self.dataset.sizex
-        return _trg_path_dict(ids, slots, ptr, cells, (H, W), names, ymin, ymax, xmin, xmax)
+        return _trg_path_dict(ids, slots, ptr, cells, (H, W), _name_list(axon_name), ymin, ymax, xmin, xmax)
 
     # ------------------------------------------------------------------ rendering (video_plotting.py:17-320)
     def render_frames(self, which_dets='IDed', t_y_x_slice=(None, None, None), draw_grid=True, draw_scalebar=False,
@@ -1193,15 +1202,19 @@ class AxonDetections(object):
 
     def _track_dev(self):
         """Trajectory id of every detection slot on the device, i32 [F,cap] (-1: none)."""
-        t = getattr(self, '_d_track', None)
-        if t is None:
+        if self._d_track is None:
             cnt = self._host_dets()[0]
             cap = self.d_conf.shape[1]
             full = np.full((len(cnt), cap), -1, np.int32)
             valid = np.arange(cap)[None, :] < cnt[:, None]
             full[valid] = self._track_flat_cache
-            t = self._d_track = torch.from_numpy(full).to(self.device)
-        return t
+            self._d_track = torch.from_numpy(full).to(self.device)
+        return self._d_track
+
+
+def _name_list(axon_name):
+    """axon_name of the accessors (None, a name, or a list of names) -> None or a list."""
+    return None if axon_name is None else ([axon_name] if isinstance(axon_name, str) else list(axon_name))
 
 
 _COLUMNS_CACHE = {}

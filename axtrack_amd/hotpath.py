@@ -306,13 +306,19 @@ class Grid:
             self._lib.axt_grid_destroy(h)
 
 
+def _as_grid(mask, conn8, device):
+    """A mask argument (None = all ones, a Grid, or an array / tensor [H, W]) -> None or a Grid on `device`."""
+    if mask is None or isinstance(mask, Grid):
+        return mask
+    return Grid(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask, conn8, device)
+
+
 def path_cost(xa, ya, xb, yb, H, W, mask=None, max_dist=MAX_PX_ASSOC_DIST, conn8=False):
     """A* path-length matrix of one frame pair (AxonDetections.py:526-629,717-752)."""
     na, nb = xa.numel(), xb.numel()
     D = torch.empty((na, nb), dtype=torch.int32, device=xa.device)
     lib = _lib.load()
-    if mask is not None and not isinstance(mask, Grid):
-        mask = Grid(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask, conn8, xa.device)
+    mask = _as_grid(mask, conn8, xa.device)
     with torch.cuda.device(xa.device):
         _lib.check(lib.axt_path_cost(xa.data_ptr(), ya.data_ptr(), na, xb.data_ptr(), yb.data_ptr(), nb,
                                      mask._h if mask is not None else None, H, W, int(max_dist), int(bool(conn8)),
@@ -326,8 +332,7 @@ def path_cells(xa, ya, xb, yb, H, W, mask, max_dist=MAX_PX_ASSOC_DIST, conn8=Fal
     na, nb = xa.numel(), xb.numel()
     D = torch.empty((na, nb), dtype=torch.int32, device=xa.device)
     cells = torch.full((na, nb, int(max_dist)), -1, dtype=torch.int32, device=xa.device)
-    if not isinstance(mask, Grid):
-        mask = Grid(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask, conn8, xa.device)
+    mask = _as_grid(mask, conn8, xa.device)
     with torch.cuda.device(xa.device):
         _lib.check(_lib.load().axt_path_cells(xa.data_ptr(), ya.data_ptr(), na, xb.data_ptr(), yb.data_ptr(), nb, mask._h,
                                               H, W, int(max_dist), int(bool(conn8)), D.data_ptr(), cells.data_ptr(),
@@ -369,9 +374,8 @@ def build_arcs(x, y, count, H, W, dmax, cost_units=None, mask=None, max_dist=MAX
     if length_table is not None:
         assert tuple(length_table.shape) == (n_frames, cap, max_gap, cap) and length_table.dtype == torch.int16
         mask = None
+    mask = _as_grid(mask, conn8, dev)
     if mask is not None:
-        if not isinstance(mask, Grid):
-            mask = Grid(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask, conn8, dev)
         n_work += (n_frames * cap * max_gap * cap + 1) // 2
     work = torch.empty((n_work,), dtype=torch.int32, device=dev)
     n_arcs = ctypes.c_int64(0)
@@ -541,8 +545,7 @@ def target_field(target_cells, H, W, mask=None, conn8=False, return_rounds=False
     _require_gpu()
     dev = target_cells.device
     cells = target_cells.to(torch.int32).contiguous()
-    if mask is not None and not isinstance(mask, Grid):
-        mask = Grid(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask, conn8, dev)
+    mask = _as_grid(mask, conn8, dev)
     off = torch.empty((int(H), int(W)), dtype=torch.int32, device=dev)
     moves = torch.empty((int(H), int(W)), dtype=torch.int32, device=dev)
     rounds = ctypes.c_int(0)
@@ -725,27 +728,23 @@ def mcf_solve(obs_int, entry_int, exit_int, row_ptr, col, cost_int, min_flow, ma
     (pot_u i64 [n], pot_v i64 [n], pot_t): the node potentials that certify the optimum (axt_mcf_solve_duals)."""
     n = len(obs_int)
     arrs = [np.ascontiguousarray(a, np.int64) for a in (obs_int, entry_int, exit_int, row_ptr)]
-    col = np.ascontiguousarray(col, np.int32)
-    cost_int = np.ascontiguousarray(cost_int, np.int64)
-    nxt = np.empty(n, np.int32)
-    track = np.empty(n, np.int32)
-    n_tracks, total = ctypes.c_int(0), ctypes.c_int64(0)
-    lib = _lib.load()
+    arrs += [np.ascontiguousarray(col, np.int32), np.ascontiguousarray(cost_int, np.int64)]
+    return _flow_solve('axt_mcf_solve', (n, *(a.ctypes.data for a in arrs), int(min_flow), int(max_flow)), n, duals)
+
+
+def _flow_solve(what, head, n, duals):
+    """Call the flow-solve entry point `what` over n detections (head: its arguments before the outputs), with duals its
+    `_duals` symbol, and return what mcf_solve returns."""
+    what += '_duals' if duals else ''
+    nxt, track, n_tracks, total = np.empty(n, np.int32), np.empty(n, np.int32), ctypes.c_int(0), ctypes.c_int64(0)
+    out = [nxt.ctypes.data, track.ctypes.data, ctypes.byref(n_tracks), ctypes.byref(total)]
     if duals:
         pu, pv, pt = np.zeros(n, np.int64), np.zeros(n, np.int64), ctypes.c_int64(0)
-        rc = _lib.check(lib.axt_mcf_solve_duals(n, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
-                                                arrs[3].ctypes.data, col.ctypes.data, cost_int.ctypes.data, int(min_flow),
-                                                int(max_flow), nxt.ctypes.data, track.ctypes.data, ctypes.byref(n_tracks),
-                                                ctypes.byref(total), pu.ctypes.data, pv.ctypes.data, ctypes.byref(pt)),
-                        'axt_mcf_solve_duals')
-        return None if rc == 1 else (nxt, track, int(n_tracks.value), int(total.value), (pu, pv, int(pt.value)))
-    rc = _lib.check(lib.axt_mcf_solve(n, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
-                                      arrs[3].ctypes.data, col.ctypes.data, cost_int.ctypes.data, int(min_flow),
-                                      int(max_flow), nxt.ctypes.data, track.ctypes.data, ctypes.byref(n_tracks),
-                                      ctypes.byref(total)), 'axt_mcf_solve')
-    if rc == 1:
+        out += [pu.ctypes.data, pv.ctypes.data, ctypes.byref(pt)]
+    if _lib.check(getattr(_lib.load(), what)(*head, *out), what) == 1:
         return None
-    return nxt, track, int(n_tracks.value), int(total.value)
+    res = (nxt, track, int(n_tracks.value), int(total.value))
+    return res + ((pu, pv, int(pt.value)),) if duals else res
 
 
 class McfShard:
@@ -772,19 +771,7 @@ class McfShard:
         states = [np.ascontiguousarray(s, np.uint8) for s in states]
         ptrs = (ctypes.c_void_p * self.world)(*[s.ctypes.data if len(s) else None for s in states])
         sizes = np.array([len(s) for s in states], np.int64)
-        nxt, track = np.empty(self.n, np.int32), np.empty(self.n, np.int32)
-        n_tracks, total = ctypes.c_int(0), ctypes.c_int64(0)
-        if duals:
-            pu, pv, pt = np.zeros(self.n, np.int64), np.zeros(self.n, np.int64), ctypes.c_int64(0)
-            rc = _lib.check(self._lib.axt_mcf_shard_finish_duals(self._h, ptrs, sizes.ctypes.data, int(min_flow), int(max_flow),
-                                                                 nxt.ctypes.data, track.ctypes.data, ctypes.byref(n_tracks),
-                                                                 ctypes.byref(total), pu.ctypes.data, pv.ctypes.data,
-                                                                 ctypes.byref(pt)), 'axt_mcf_shard_finish_duals')
-            return None if rc == 1 else (nxt, track, int(n_tracks.value), int(total.value), (pu, pv, int(pt.value)))
-        rc = _lib.check(self._lib.axt_mcf_shard_finish(self._h, ptrs, sizes.ctypes.data, int(min_flow), int(max_flow),
-                                                       nxt.ctypes.data, track.ctypes.data, ctypes.byref(n_tracks),
-                                                       ctypes.byref(total)), 'axt_mcf_shard_finish')
-        return None if rc == 1 else (nxt, track, int(n_tracks.value), int(total.value))
+        return _flow_solve('axt_mcf_shard_finish', (self._h, ptrs, sizes.ctypes.data, int(min_flow), int(max_flow)), self.n, duals)
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None

@@ -244,7 +244,7 @@ def render_frames(dets, which_dets='IDed', t_y_x_slice=(None, None, None), draw_
                   description='', annotate=True, draw_target_paths=False, _frames=None):
     """AxonDetections.render_frames (see there). _frames: the detection frames to draw (render_inference's chunks)."""
     ds = dets.dataset
-    if getattr(dets, '_shard', None) is not None:
+    if dets._shard is not None:
         raise NotImplementedError('rendering a frame-sharded run is not implemented: render in a single process '
                                   '(AxonDetections without gather_detections)')
     if which_dets not in ('IDed', 'confident', 'all', 'groundtruth'):
@@ -261,7 +261,7 @@ def render_frames(dets, which_dets='IDed', t_y_x_slice=(None, None, None), draw_
         raise ValueError("draw_axon_reconstructions goes with which_dets='IDed' (the reconstructions are the IDed tracks')")
     if draw_target_paths and which_dets != 'IDed':
         raise ValueError("draw_target_paths goes with which_dets='IDed' (the paths start at the IDed detections)")
-    if which_dets == 'IDed' and not getattr(dets, '_solved', False):
+    if which_dets == 'IDed' and not dets._solved:
         raise ValueError('no identities: run assign_ids() first (or the association was infeasible)')
     if draw_target_paths:
         dets._require_target(ids=True)

@@ -25,10 +25,9 @@ for it in range(6):
     d = T('decode_nms', lambda: hp.decode_stitch_nms(yolo, tiles, float(np.float32(0.55)), 23), acc)
     ad.tile_yx, ad._yolo = tiles, yolo
     ad.d_conf, ad.d_x, ad.d_y, ad.d_count = d
-    ad._host = None; ad._det_tables = None
     T('host_dets (D2H)', ad._host_dets, acc)
     T('assign (solve)', ad._assign_IDs_to_detections, acc)
-    ad._solved = True; ad._ided_tables = None
+    ad._solved = True
     T('IDed_dets_all', ad._agg_all_IDed_dets, acc)
     T('whole inference()', lambda: axtrack_amd.inference(tl, model, None, P, None, None, None), acc)
 for k, v in acc.items():

@@ -322,9 +322,12 @@ def test_unstitched_tile_tables_equal_the_references(golden, name):
     """get_frame_dets(unstitched=True) / _pandas_tiled_dets (AxonDetections.py:178-248,322-331) decoded on the host from
     the YOLO grids: on the reference's golden grids the tables equal the reference's own (values and order)."""
     import torch
+    from axtrack_amd import params
     from axtrack_amd.detections import AxonDetections
     g = golden(name)
-    ad = object.__new__(AxonDetections)
+
+    dataset = type('Dataset', (), dict(name='golden', sizet=g['yolo'].shape[0], device='cpu'))()       # (a stub: no frames needed)
+    ad = AxonDetections(None, dataset, params.load_parameters(), None)
     ad.Sx = ad.Sy = 12
     ad.tilesize = 512
     ad.conf_thr = 0.7
