@@ -34,6 +34,10 @@ SIGNATURES = {
     'axt_cnn_kernel_flops_per_tile': (c_double, [c_int]),
     'axt_preprocess_u16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_void_p,
                                    c_void_p]),
+    'axt_preprocess_stats_u16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p,
+                                         ctypes.POINTER(c_size_t), c_void_p]),
+    'axt_preprocess_u16_framewise': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p,
+                                             c_void_p, c_void_p]),
     'axt_tile_occupancy': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'axt_decode_stitch_nms': (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),

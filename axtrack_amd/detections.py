@@ -81,6 +81,8 @@ class AxonDetections(object):
         # state that follows neither the detections nor the association: the labels, the target and its fields
         self._gt = self._gt_ids = self._gt_dev = None
         self._target_cells, self.reach_px, self.structure_outputchannel_coo, self._target_fields = None, None, None, {}
+        if getattr(dataset, 'labelled', False):            # a labelled dataset brings its ground truth (AxonDetections.py:57)
+            self.set_groundtruth([dataset.labels[t] for t in self.timepoint_subset])
 
     def _drop_association(self):
         """Forget everything that belongs to one association (assign_ids / _set_ided_from_tables)."""
@@ -354,6 +356,12 @@ class AxonDetections(object):
                                 'anchor_x': pd.array(np.asarray(gx, np.int64), dtype='Int64'),
                                 'anchor_y': pd.array(np.asarray(gy, np.int64), dtype='Int64')},
                                index=[f'Axon_{i:0>3}' for i in self._gt_ids[t]])
+        elif which_dets == 'FP_FN':
+            # AxonDetections.py:341-349: the confident detections that match no label, the labels no detection matches
+            if not self.labelled:
+                raise ValueError("no labels: call set_groundtruth() first")
+            FP_mask, FN_mask = self.compute_TP_FP_FN('confident', t, return_FP_FN_mask=True)
+            return self.get_frame_dets('confident', t)[FP_mask], self.get_frame_dets('groundtruth', t)[FN_mask]
         else:
             raise NotImplementedError(f"which_dets={which_dets!r} is a plotting selection (out of scope)")
         if libmot:
@@ -377,7 +385,7 @@ class AxonDetections(object):
         """labels: per detection frame (x, y) or (x, y, ids) -- integer anchor arrays and, for the tracking scores of
         search_MCF_params, the axons' identities (the numbers of the labels' Axon_### names; default: position in
         the frame). The reference reads them from the labelled dataset's YOLO targets (get_frame_and_truedets,
-        :355-376); the dataset side is out of scope here."""
+        :355-376); here a labelled Timelapse (prepare_training_data) hands its labels over in __init__."""
         if len(labels) != len(self):
             raise ValueError(f'{len(labels)} label frames for {len(self)} detection frames')
         self._gt = [(np.asarray(l[0], np.int64), np.asarray(l[1], np.int64)) for l in labels]

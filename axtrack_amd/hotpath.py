@@ -223,6 +223,57 @@ def preprocess_u16(raw, mask=None, offset=0.0, clip_lower=0.0, log_correct=True,
     return out
 
 
+# axt_frame_stats (include/axtrack_hip.h): one 32-byte record per frame
+FRAME_STATS_DTYPE = np.dtype([('n', np.int64), ('sum', np.float64), ('sumsq', np.float64), ('max', np.float32),
+                              ('reserved', np.float32)])
+
+
+def preprocess_stats_u16(raw, mask=None, offset=0.0, clip_lower=0.0, log_correct=True):
+    """Per-frame (n, sum, sumsq, max) of the values preprocess_u16 would write with scale=1, without writing them: what
+    Timelapse._standardize measures before it scales (Timelapse.py:286-302). raw, mask as in preprocess_u16.
+    -> numpy record array [T] of FRAME_STATS_DTYPE on the host (the call waits for the result)."""
+    T, H, W = raw.shape
+    assert raw.is_contiguous() and raw.element_size() == 2
+    if mask is not None:
+        mask = mask.to(device=raw.device, dtype=torch.uint8).contiguous()
+    lib = _lib.load()
+    args = (T, H, W, ctypes.c_float(offset), ctypes.c_float(clip_lower), int(bool(log_correct)))
+    need = ctypes.c_size_t(0)
+    _lib.check(lib.axt_preprocess_stats_u16(None, None, *args, None, None, ctypes.byref(need), None),
+               'axt_preprocess_stats_u16 (scratch size)')
+    scratch = torch.empty(need.value, dtype=torch.uint8, device=raw.device)
+    stats = torch.empty(T * FRAME_STATS_DTYPE.itemsize, dtype=torch.uint8, device=raw.device)
+    with torch.cuda.device(raw.device):
+        _lib.check(lib.axt_preprocess_stats_u16(raw.data_ptr(), _lib.dptr(mask), *args, stats.data_ptr(),
+                                                scratch.data_ptr(), ctypes.byref(need), _stream()),
+                   'axt_preprocess_stats_u16')
+    return stats.cpu().numpy().view(FRAME_STATS_DTYPE)
+
+
+def preprocess_u16_framewise(raw, scale, mask=None, offset=0.0, clip_lower=0.0, log_correct=True, out=None):
+    """preprocess_u16 with one scale per frame (STANDARDIZE_FRAMEWISE, Timelapse.py:309-312). scale: T positive finite
+    numbers (host array or tensor); a scale that is not would put inf / NaN into a frame and is refused here."""
+    T, H, W = raw.shape
+    assert raw.is_contiguous() and raw.element_size() == 2
+    sc = np.ascontiguousarray(scale.detach().cpu().numpy() if isinstance(scale, torch.Tensor) else scale, np.float32)
+    if sc.shape != (T,):
+        raise ValueError(f'{T} frames need {T} scales, got an array of shape {sc.shape}')
+    if not (np.isfinite(sc) & (sc > 0)).all():
+        raise ValueError(f'frame scales must be finite and > 0; frames {np.flatnonzero(~(np.isfinite(sc) & (sc > 0))).tolist()} are not')
+    if out is None:
+        out = torch.empty((T, H, W), dtype=torch.float32, device=raw.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (T, H, W) and out.device == raw.device
+    if mask is not None:
+        mask = mask.to(device=raw.device, dtype=torch.uint8).contiguous()
+    d_scale = torch.from_numpy(sc).to(raw.device)
+    lib = _lib.load()
+    with torch.cuda.device(raw.device):
+        _lib.check(lib.axt_preprocess_u16_framewise(raw.data_ptr(), _lib.dptr(mask), T, H, W, ctypes.c_float(offset),
+                                                    ctypes.c_float(clip_lower), int(bool(log_correct)), d_scale.data_ptr(),
+                                                    out.data_ptr(), _stream()), 'axt_preprocess_u16_framewise')
+    return out
+
+
 def tile_occupancy_bytes(frames):
     """Per-tile occupancy of this block of frames as a device u8 tensor [tile_rows * tile_cols] (1 = some pixel of
     the tile is non-zero at some time point)."""

@@ -21,7 +21,8 @@ import torch
 from . import params as _params
 from .detections import AxonDetections
 from .hotpath import Detector
-from .timelapse import Timelapse, preprocess, pad_mask
+from .timelapse import (Timelapse, preprocess, pad_mask, estimate_stnd_scaler, frame_scales, load_labels_csv,
+                        contiguous_runs)
 
 # config.py:5,8 -- the directory that holds examples/ and deployed_model/ (the reference's package root)
 PKG_DIR = os.path.abspath(os.path.join(os.path.dirname(__file__), '..')) + '/'
@@ -123,6 +124,90 @@ def prepare_input_data(imseq_fname, parameters, dest_dir, inference_data_dir, st
         warnings.warn(f'check_preproc: the preprocessing statistics are in {fname}; the comparison plot against the training '
                       f'data (ml_plotting.plot_preprocessed_input_data, train_preproc_data.csv) is out of scope of axtrack_amd')
     return timelapse
+
+
+def _read_stack(source, what):
+    """A .npy file, a .tif file where tifffile exists, or the array itself."""
+    if not isinstance(source, str):
+        return np.asarray(source)
+    if source.endswith('.npy'):
+        return np.load(source)
+    try:
+        from tifffile import imread
+    except ImportError as e:
+        raise ImportError(f'reading {what} {source} needs tifffile; pass a numpy array or a .npy file instead') from e
+    return imread(source)
+
+
+def prepare_training_data(parameters, skip_test=False, **overrides):
+    """core_functionality.setup_data (:15-59): the labelled train and test timelapses of one recording -> (train, test), test
+    None with skip_test. Keys read from `parameters` (each can be overridden by keyword): TIMELAPSE_FILE (.npy, a uint16
+    array [T,H,W], or .tif where tifffile exists), LABELS_FILE (the reference's axon_anchor_labels.csv), MASK_FILE (.npy, an
+    array, None or a name ending in 'None'), TRAIN_TIMEPOINTS, TEST_TIMEPOINTS (input frame numbers), OFFSET, CLIP_LOWERLIM,
+    PAD (top, right, bottom, left), LOG_CORRECT, STANDARDIZE, STANDARDIZE_FRAMEWISE, TEMPORAL_CONTEXT, TILESIZE, CACHE, DEVICE.
+
+    With STANDARDIZE[1] None the train scaler is estimated from ALL frames of the file (estimate_stnd_scaler, as
+    Timelapse._standardize runs before the time points are sliced), else the passed scaler is used; the test set gets
+    train.stnd_scaler (:58). Frame-wise, that is (name, None) and every frame is divided by its own std / max. Each set is
+    the block of input frames [min(tp) - context, max(tp) + context] with its labels at the time points; this package's
+    Timelapse is one dense contiguous stack, so a time-point list with a gap raises ValueError naming the runs (call once
+    per run). CACHE: a directory that receives train_stnd_scaler.pkl (Timelapse.py:320-323), the file setup_inference
+    looks for next to the weights."""
+    P = dict(parameters)
+    P.update(overrides)
+    device, context = P.get('DEVICE', 'cuda:0'), int(P.get('TEMPORAL_CONTEXT', 2))
+    imseq = _read_stack(P['TIMELAPSE_FILE'], 'the timelapse')
+    if imseq.ndim != 3:
+        raise ValueError(f'the timelapse must be [T,H,W], got {imseq.shape}')
+    T = imseq.shape[0]
+    mask = P.get('MASK_FILE')
+    mask = None if mask is None or (isinstance(mask, str) and mask.endswith('None')) else _read_stack(mask, 'the mask')
+    pad = P.get('PAD')
+    pad = [int(v) for v in pad] if pad is not None and any(pad) else None
+    H = imseq.shape[1] + (pad[0] + pad[2] if pad else 0)
+    W = imseq.shape[2] + (pad[1] + pad[3] if pad else 0)
+    labels = load_labels_csv(P['LABELS_FILE'], pad=pad, shape=(H, W))
+    name, passed = P.get('STANDARDIZE', ('zscore', None))
+    framewise = bool(P.get('STANDARDIZE_FRAMEWISE', False))
+    if not name:
+        raise ValueError('STANDARDIZE[0] must be \'zscore\' or \'0to1\': the detector reads standardised frames')
+    if framewise and passed is not None:
+        raise ValueError('a passed scaler applies to timelapse-wide standardisation only: with STANDARDIZE_FRAMEWISE pass '
+                         '(name, None)')
+    pre = dict(offset=P.get('OFFSET'), clip=P.get('CLIP_LOWERLIM'), log_correct=P.get('LOG_CORRECT', True), device=device)
+    per_frame = None
+    if passed is None:
+        stnd_scaler, per_frame = estimate_stnd_scaler(imseq, mask, standardize=name, framewise=framewise, **pre)
+    else:
+        stnd_scaler = (name, (float(passed[0]), float(passed[1])))
+    scales = frame_scales(stnd_scaler, per_frame)
+
+    def one_set(which, timepoints):
+        runs = contiguous_runs(timepoints)
+        if not runs:
+            raise ValueError(f'{which}_TIMEPOINTS is empty')
+        if len(runs) > 1:
+            raise ValueError(f'{which}_TIMEPOINTS has gaps: a Timelapse is one contiguous block of frames. Call once per run: '
+                             f'{[f"{a}..{b}" for a, b in runs]}')
+        a, b = runs[0][0] - context, runs[0][1] + context + 1
+        if a < 0 or b > T:
+            raise ValueError(f'{which}_TIMEPOINTS {runs[0][0]}..{runs[0][1]} need the input frames {a}..{b - 1}; the file has 0..{T - 1}')
+        if b - context > len(labels):
+            raise ValueError(f'{P["LABELS_FILE"]} has {len(labels)} rows; {which}_TIMEPOINTS reach frame {b - context - 1}')
+        m = mask[a:b] if mask is not None and np.ndim(mask) == 3 else mask
+        frames = preprocess(imseq[a:b], m, scale=scales if np.ndim(scales) == 0 else scales[a:b], pad=pad, **pre)
+        if pad:
+            m = pad_mask(m, pad, imseq[a:b].shape)
+        return Timelapse(frames, name=which.lower(), mask=m, temporal_context=context, tilesize=P.get('TILESIZE', 512),
+                         device=device, labels=labels[a + context:b - context], stnd_scaler=stnd_scaler)
+
+    train = one_set('TRAIN', P['TRAIN_TIMEPOINTS'])
+    if P.get('CACHE'):
+        os.makedirs(P['CACHE'], exist_ok=True)
+        with open(f"{P['CACHE']}/train_stnd_scaler.pkl", 'wb') as f:
+            pickle.dump(train.stnd_scaler, f)
+    test = None if skip_test else one_set('TEST', P['TEST_TIMEPOINTS'])
+    return train, test
 
 
 def save_preproc_metrics(dest_dir, name, imseq, mask, input_metadata, parameters, stnd_scaler, n_samples=int(1e6)):

@@ -13,8 +13,11 @@ import torch
 
 class Timelapse:
     def __init__(self, frames, name='timelapse', mask=None, temporal_context=2, tilesize=512,
-                 device='cuda:0', pixelsize=None, dt=None, incubation_time=None):
-        """frames: preprocessed f32 [T_all,H,W] (numpy or torch); mask: bool [H,W] or None (all ones)."""
+                 device='cuda:0', pixelsize=None, dt=None, incubation_time=None, labels=None, stnd_scaler=None):
+        """frames: preprocessed f32 [T_all,H,W] (numpy or torch); mask: bool [H,W] or None (all ones).
+        labels: None, or one entry per DETECTION frame, (x, y) or (x, y, ids) integer arrays as load_labels_csv returns
+        them and AxonDetections.set_groundtruth / fine_tune_head take them. stnd_scaler: the scaler the frames were
+        standardised with, (name, (var_scalar, mean_scalar)) or (name, None) for frame-wise scales (Timelapse.py:300-302)."""
         if temporal_context != 2:
             raise ValueError('the deployed detector has 5 input channels: temporal_context must be 2')
         f = torch.as_tensor(frames)
@@ -50,6 +53,15 @@ class Timelapse:
                 raise ValueError('mask must be [H,W] or [T_all,H,W]')
         self.pixelsize, self.dt, self.incubation_time = pixelsize, dt, incubation_time
         self.timepoints = np.arange(temporal_context, temporal_context + self.sizet)
+        if labels is not None:
+            labels = [tuple(np.asarray(a, np.int64) for a in l) for l in labels]
+            if len(labels) != self.sizet:
+                raise ValueError(f'{len(labels)} label frames for {self.sizet} detection frames')
+        self.labels, self.stnd_scaler = labels, stnd_scaler
+
+    @property
+    def labelled(self):
+        return self.labels is not None
 
     def __len__(self):
         return self.sizet
@@ -77,14 +89,15 @@ class Timelapse:
     def to_cache(self, directory):
         """'{name}_dataset_cached.pkl' (Timelapse._caching, Timelapse.py:435-449): the reference pickles its whole
         __dict__ (sparse tensors of all three channels); this writes the same file name with what the hot path keeps --
-        the preprocessed frames, the mask and the metadata."""
+        the preprocessed frames, the mask, the metadata and, of a labelled dataset, the labels and the scaler."""
         import os
         import pickle
         os.makedirs(directory, exist_ok=True)
         self.make_resident()
         d = dict(_axtrack_amd_cache=1, name=self.name, frames=self.frames.cpu().numpy(),
                  mask=self.mask3d if self.mask3d is not None else self.mask2d, temporal_context=self.temporal_context,
-                 tilesize=self.tilesize, pixelsize=self.pixelsize, dt=self.dt, incubation_time=self.incubation_time)
+                 tilesize=self.tilesize, pixelsize=self.pixelsize, dt=self.dt, incubation_time=self.incubation_time,
+                 labels=self.labels, stnd_scaler=self.stnd_scaler)
         with open(f'{directory}/{self.name}_dataset_cached.pkl', 'wb') as file:
             pickle.dump(d, file, protocol=4)
 
@@ -101,7 +114,7 @@ class Timelapse:
         if d.get('_axtrack_amd_cache'):
             return cls(d['frames'], name=d['name'], mask=d['mask'], temporal_context=d['temporal_context'],
                        tilesize=d['tilesize'], device=device, pixelsize=d['pixelsize'], dt=d['dt'],
-                       incubation_time=d['incubation_time'])
+                       incubation_time=d['incubation_time'], labels=d.get('labels'), stnd_scaler=d.get('stnd_scaler'))
         X = d['X']
         X = X.to_dense() if X.is_sparse else X
         mask = np.stack([np.asarray(m.todense()) if hasattr(m, 'todense') else np.asarray(m) for m in d['mask']]).astype(bool)
@@ -264,20 +277,14 @@ def _pinned_bytes(n):
     return _PINNED[n]
 
 
-def preprocess(imseq, mask=None, offset=121, clip=55, log_correct=True, scale=0.015176106, device='cuda:0', pad=None):
-    """Dense preprocessing of a raw uint16 timelapse as Timelapse._read_tiff / _clip_image_values /
-    _log_adjust_image / _standardize do it (Timelapse.py:205-326), as one fused HIP pass
-    (axt_preprocess_u16): u16 -> f32 in [0,1], mask, subtract offset/2^16 and clamp at 0, zero below
-    clip/2^16, log2(1+x), divide by the train-set std. `img_as_float32` and `adjust_log` are skimage
-    functions that are absent here: their arithmetic (x * (1/65535), log2(1+x)) is restated from the
-    published skimage 0.18 behaviour, PARITY UNPINNED (SURVEY.md 8f-1, a "next" row).
-    mask: [H,W] or one per frame [T,H,W] (Timelapse.py:210-217). pad: None or (top, right, bottom, left) -- zero
-    margins added after masking and offsetting (Timelapse.py:224-234); zero stays zero through the clip, the log and
-    the scaling, so the margins are added to the finished frames. Returns f32 [T, H + top + bottom, W + left + right]."""
-    from . import hotpath as hp
+def _raw_on_device(imseq, mask, offset, clip, device):
+    """What preprocess and estimate_stnd_scaler hand to the kernels: (raw counts on the device as int16 bits [T,H,W], the
+    static mask as a u8 tensor or None, offset and clip in [0,1] units). A mask per frame zeroes the raw counts."""
     a = np.asarray(imseq)
     if a.dtype != np.uint16:
         raise TypeError(f'raw timelapses are uint16 (got {a.dtype}); pass preprocessed float32 frames to Timelapse directly')
+    if a.ndim != 3:
+        raise ValueError(f'raw timelapses are [T,H,W], got {a.shape}')
     raw = torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(device)
     off = 0.0 if not offset else (offset / 2 ** 16 if isinstance(offset, int) else float(offset))
     lo = 0.0 if not clip else (clip / 2 ** 16 if isinstance(clip, int) else float(clip))
@@ -290,11 +297,142 @@ def preprocess(imseq, mask=None, offset=121, clip=55, log_correct=True, scale=0.
             raw = raw * torch.from_numpy(mk).to(device=device, dtype=torch.int16)
         else:
             m = torch.from_numpy(np.ascontiguousarray(mk.astype(np.uint8)))
-    out = hp.preprocess_u16(raw.contiguous(), m, off, lo, bool(log_correct), float(scale))
+    return raw.contiguous(), m, off, lo
+
+
+def preprocess(imseq, mask=None, offset=121, clip=55, log_correct=True, scale=0.015176106, device='cuda:0', pad=None):
+    """Dense preprocessing of a raw uint16 timelapse as Timelapse._read_tiff / _clip_image_values /
+    _log_adjust_image / _standardize do it (Timelapse.py:205-326), as one fused HIP pass
+    (axt_preprocess_u16): u16 -> f32 in [0,1], mask, subtract offset/2^16 and clamp at 0, zero below
+    clip/2^16, log2(1+x), divide by the train-set std. `img_as_float32` and `adjust_log` are skimage
+    functions that are absent here: their arithmetic (x * (1/65535), log2(1+x)) is restated from the
+    published skimage 0.18 behaviour, PARITY UNPINNED (SURVEY.md 8f-1, a "next" row).
+    mask: [H,W] or one per frame [T,H,W] (Timelapse.py:210-217). pad: None or (top, right, bottom, left) -- zero
+    margins added after masking and offsetting (Timelapse.py:224-234); zero stays zero through the clip, the log and
+    the scaling, so the margins are added to the finished frames. Returns f32 [T, H + top + bottom, W + left + right].
+    scale: one number, or one per frame (STANDARDIZE_FRAMEWISE, Timelapse.py:309-312: axt_preprocess_u16_framewise)."""
+    from . import hotpath as hp
+    raw, m, off, lo = _raw_on_device(imseq, mask, offset, clip, device)
+    if np.ndim(scale) == 0:
+        out = hp.preprocess_u16(raw, m, off, lo, bool(log_correct), float(scale))
+    else:
+        out = hp.preprocess_u16_framewise(raw, scale, m, off, lo, bool(log_correct))
     if pad is not None and any(pad):
         top, right, bottom, left = (int(v) for v in pad)
         out = torch.nn.functional.pad(out, (left, right, top, bottom)).contiguous()
     return out
+
+
+STANDARDIZE_MODES = ('zscore', '0to1')
+
+
+def scaler_from_stats(n, sum_, sumsq, max_, standardize='zscore', framewise=False):
+    """Timelapse._standardize's scaler (Timelapse.py:286-302) from the per-frame statistics of the preprocessed, not yet
+    scaled frames -- n non-zero values, their sum, their sum of squares, the frame's maximum -- in f64 on the host:
+    mean = sum / n, std = sqrt(sumsq / n - mean^2), the population std np.std(frame.data) takes of the non-zero values.
+    -> (stnd_scaler, per_frame DataFrame (n, mean, std, max), frame scales f64 [T] for framewise or None).
+    'zscore': var_scalar = mean of the stds, mean_scalar = mean of the means; '0to1': var_scalar = max of the maxima,
+    mean_scalar = 0. Not framewise: (name, (var_scalar, mean_scalar)); framewise: (name, None) and the per-frame std /
+    max are the scales. Where the reference would divide by NaN or 0 -- 'zscore' with a frame without a non-zero pixel, a
+    scale of 0 -- this raises ValueError naming the frames."""
+    import pandas as pd
+    if standardize not in STANDARDIZE_MODES:
+        raise ValueError(f'standardize must be one of {STANDARDIZE_MODES}, got {standardize!r}')
+    n = np.asarray(n, np.int64)
+    s, q, mx = (np.asarray(v, np.float64) for v in (sum_, sumsq, max_))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = s / n
+        # sumsq / n - mean^2 cancels: what it leaves of a frame of equal values is summation error, at most a few
+        # n * 2^-53 of sumsq / n. A variance down there is 0 (and then refused as a frame scale), not a tiny scale.
+        var = q / n - mean * mean
+        std = np.sqrt(np.where(var <= 4.0 * n * 2.0 ** -53 * (q / n), 0.0, var))
+    per_frame = pd.DataFrame({'n': n, 'mean': mean, 'std': std, 'max': mx})
+    if standardize == 'zscore' and (n == 0).any():
+        raise ValueError(f"'zscore' needs a non-zero pixel in every frame; frames {np.flatnonzero(n == 0).tolist()} have none "
+                         f'(the reference would scale by NaN)')
+    frame_scale = std if standardize == 'zscore' else mx
+    if framewise:
+        bad = ~(np.isfinite(frame_scale) & (frame_scale > 0))
+        if bad.any():
+            raise ValueError(f'frame-wise {standardize!r}: the scale of frames {np.flatnonzero(bad).tolist()} would be 0')
+        return (standardize, None), per_frame, frame_scale.copy()
+    if standardize == 'zscore':
+        var_scalar, mean_scalar = float(np.mean(std)), float(np.mean(mean))
+    else:
+        var_scalar, mean_scalar = float(np.max(mx)), 0.0
+    if not (np.isfinite(var_scalar) and var_scalar > 0):
+        raise ValueError(f'{standardize!r}: the scale of the timelapse would be {var_scalar} (frames without contrast)')
+    return (standardize, (var_scalar, mean_scalar)), per_frame, None
+
+
+def estimate_stnd_scaler(imseq, mask=None, offset=None, clip=None, log_correct=True, standardize='zscore', framewise=False,
+                         device='cuda:0'):
+    """The standardisation scaler of a raw uint16 timelapse [T,H,W], as Timelapse._standardize computes it from the
+    training data (Timelapse.py:277-302) -> (stnd_scaler, per_frame). One pass over the raw counts
+    (axt_preprocess_stats_u16: the preprocessing arithmetic of `preprocess` at scale 1, reduced per frame to n, sum,
+    sumsq, max without writing a frame); the rest is scaler_from_stats on the host. All frames take part. per_frame:
+    DataFrame (n, mean, std, max), one row per input frame; with framewise=True its 'std' ('zscore') or 'max' ('0to1')
+    column is what `preprocess(scale=...)` takes as the frames' scales."""
+    from . import hotpath as hp
+    if standardize not in STANDARDIZE_MODES:
+        raise ValueError(f'standardize must be one of {STANDARDIZE_MODES}, got {standardize!r}')
+    raw, m, off, lo = _raw_on_device(imseq, mask, offset, clip, device)
+    st = hp.preprocess_stats_u16(raw, m, off, lo, bool(log_correct))
+    scaler, per_frame, _ = scaler_from_stats(st['n'], st['sum'], st['sumsq'], st['max'], standardize, framewise)
+    return scaler, per_frame
+
+
+def frame_scales(stnd_scaler, per_frame):
+    """What `preprocess(scale=...)` takes for a scaler: the one number, or for (name, None) the per-frame column."""
+    if stnd_scaler[1] is not None:
+        return float(stnd_scaler[1][0])
+    return per_frame['std' if stnd_scaler[0] == 'zscore' else 'max'].to_numpy(np.float64)
+
+
+def load_labels_csv(fname, pad=None, shape=None):
+    """The reference's axon_anchor_labels.csv as Timelapse._load_bboxes reads it (Timelapse.py:377-383): two header rows
+    (axon name, property), the frame number as index; the (axon, 'anchor_x' | 'anchor_y') columns are kept, the rows sorted
+    by index and renumbered, pad[0] added to y and pad[3] to x (pad: top, right, bottom, left).
+    -> per input frame (x, y, ids), int64 arrays. NaN means the axon is absent in that frame; values are truncated toward
+    zero (construct_tiles' fillna(-1).astype(int), :514). A label left of or above the frame is dropped, and with
+    shape=(H, W) of the padded frame so is one right of or below it: construct_tiles assigns those to no tile (:532-534).
+    ids: the trailing integer of the axon's column name when every name has one and they are distinct, else the column
+    position."""
+    import re
+    import pandas as pd
+    bboxes = pd.read_csv(fname, index_col=0, header=[0, 1])
+    bboxes = bboxes.loc[:, (slice(None), ['anchor_x', 'anchor_y'])].sort_index().reset_index(drop=True)
+    names = list(dict.fromkeys(bboxes.columns.get_level_values(0)))
+    lone = [a for a in names if not {(a, 'anchor_x'), (a, 'anchor_y')} <= set(bboxes.columns)]
+    if lone:
+        raise ValueError(f'{fname}: axons {lone} lack anchor_x or anchor_y')
+    tails = [re.search(r'(\d+)$', str(a)) for a in names]
+    ids = np.array([int(m.group(1)) for m in tails], np.int64) if all(tails) else None
+    if ids is None or len(set(ids.tolist())) != len(ids):
+        ids = np.arange(len(names), dtype=np.int64)
+    x = np.stack([bboxes[(a, 'anchor_x')].to_numpy(np.float64) for a in names], 1) if names else np.zeros((len(bboxes), 0))
+    y = np.stack([bboxes[(a, 'anchor_y')].to_numpy(np.float64) for a in names], 1) if names else np.zeros((len(bboxes), 0))
+    if pad is not None and (pad[0] or pad[3]):
+        y, x = y + int(pad[0]), x + int(pad[3])
+    present = ~(np.isnan(x) | np.isnan(y))
+    xi = np.where(present, np.trunc(np.nan_to_num(x)), -1).astype(np.int64)
+    yi = np.where(present, np.trunc(np.nan_to_num(y)), -1).astype(np.int64)
+    keep = present & (xi >= 0) & (yi >= 0)
+    if shape is not None:
+        keep &= (xi < int(shape[1])) & (yi < int(shape[0]))
+    return [(xi[t, keep[t]], yi[t, keep[t]], ids[keep[t]]) for t in range(len(bboxes))]
+
+
+def contiguous_runs(timepoints):
+    """Sorted distinct time points -> list of (first, last) of their runs of consecutive numbers."""
+    tp = sorted({int(t) for t in timepoints})
+    runs = []
+    for t in tp:
+        if runs and t == runs[-1][1] + 1:
+            runs[-1][1] = t
+        else:
+            runs.append([t, t])
+    return [tuple(r) for r in runs]
 
 
 def pad_mask(mask, pad, shape):

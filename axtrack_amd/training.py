@@ -4,8 +4,8 @@ The convolutional trunk stays frozen: its output per (frame, tile) item -- what 
 by the inference kernels (Detector.features_frames; once, or once per epoch when the frames are augmented), and an epoch is nothing but head steps on that table: forward
 (model.py:105-117), YOLO_AXTrack_loss (loss.py:18-68), backward and torch.optim.Adam with L2 weight decay
 (core_functionality.py:81), all in csrc/train.hip. The epoch loop restates one_epoch / run_epoch
-(core_functionality.py:109-165) without the every-tenth-epoch metrics (call get_detection_metrics with a Detector built
-from the returned state dict). With use_transforms it also restates the reference's augmentation (augment.py): a new
+(core_functionality.py:109-165); its every-tenth-epoch metrics run when a labelled test timelapse is given
+(fine_tune_head(test_timelapse=...)). With use_transforms it also restates the reference's augmentation (augment.py): a new
 translate / flip / rotate of frames and labels every epoch, the prepare_data resampling loop, and the feature table
 recomputed from the warped frames, which costs about one trunk pass per epoch."""
 import ctypes
@@ -246,8 +246,26 @@ def _augmented_epoch(frames, labels, transform, draw, min_pos_rate, max_redraws,
     return tf, warped, tiles, lab
 
 
-def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir=None, seed=None, use_transforms=None,
-                   transforms=None, min_pos_rate=0.65, max_redraws=50):
+def _epoch_metrics(sd, timelapse, labels, parameters, subset):
+    """one_epoch's every-tenth-epoch evaluation (core_functionality.py:150-161) of the detector with state dict `sd` on the
+    detection frames `subset` of a labelled timelapse: detect, sum compute_TP_FP_FN('all', t) over the frames (one launch:
+    detection_confusion), precision / recall / F1 at the 13 thresholds as compute_prc_rcl_F1's Series."""
+    from . import params as _params
+    from .detections import AxonDetections
+    from .hotpath import Detector
+    P = _params.load_parameters()
+    P.update(parameters or {})
+    detector = Detector(sd, max_batch=32, device=timelapse.device)
+    dets = AxonDetections(detector, timelapse, P, None, timepoint_subset=subset)
+    if labels is not None:
+        dets.set_groundtruth([labels[t] for t in subset])
+    dets.detect_dataset()
+    return dets.compute_prc_rcl_F1(dets.detection_confusion().sum(axis=0), return_dataframe=True)
+
+
+def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
+                   use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
+                   metrics_every=10):
     """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
     one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
     (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
@@ -260,12 +278,32 @@ def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir
     below min_pos_rate -- RuntimeError after max_redraws -- and recomputes the trunk features and the targets of the
     tiles the warped frames keep. transforms: instead, one explicit transform per epoch (augment.Transform or a dict of
     its fields), used as given. The transforms used are history.attrs['transforms'], which `transforms=` replays. With
-    neither (None or an empty list) nothing is augmented and the features are computed once."""
+    neither (None or an empty list) nothing is augmented and the features are computed once.
+
+    labels=None takes the labels of a labelled timelapse (prepare_training_data). test_timelapse: a labelled timelapse to
+    validate on. Then every epoch with epoch % metrics_every == 0 ends with one_epoch's evaluation
+    (core_functionality.py:150-161): a Detector built from the trainer's weights of that moment (one host round trip)
+    detects every 10th frame of the train set, from a start in 0..9 drawn from a generator of its own seeded by `seed`
+    (taken modulo the number of frames where the set has fewer than ten), and all frames of the test set; the confusion
+    counts are summed over the frames and turned into precision / recall / F1 at the 13 thresholds. The result is
+    history.attrs['metrics']: a DataFrame, rows (metric, threshold), columns (epoch, 'train' | 'test'). The evaluation
+    reads the weights only: history and the returned state dict are what they are without it."""
     import pandas as pd
     from .hotpath import Detector, FEATURES
-    if getattr(timelapse, 'frame_sharded', False):
-        raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
-                                  'process on the whole timelapse')
+    for tl in (timelapse, test_timelapse):
+        if getattr(tl, 'frame_sharded', False):
+            raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
+                                      'process on the whole timelapse')
+    if model is None:
+        raise ValueError('fine_tune_head needs the model to start from: a Detector or a state dict')
+    explicit_labels = labels is not None
+    if labels is None:
+        labels = getattr(timelapse, 'labels', None)
+        if labels is None:
+            raise ValueError('no labels: pass them, or a labelled timelapse (prepare_training_data)')
+    with_metrics = test_timelapse is not None and bool(metrics_every)
+    if with_metrics and not getattr(test_timelapse, 'labelled', False):
+        raise ValueError('test_timelapse carries no labels (prepare_training_data makes labelled timelapses)')
     if len(labels) != len(timelapse):
         raise ValueError(f'{len(labels)} label frames for {len(timelapse)} detection frames')
     augmented = bool(use_transforms) or transforms is not None
@@ -307,7 +345,8 @@ def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir
         trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
     rng = np.random.default_rng(seed)
     checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
-    history = {}
+    history, metrics = {}, {}
+    m_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(2)[1])      # the evaluation's own draws
     for epoch in range(epochs):
         if augmented:
             tf, warped, tile_yx, lab = _augmented_epoch(timelapse.frames, label_xy, None if transforms is None else
@@ -326,7 +365,16 @@ def fine_tune_head(timelapse, labels, model, parameters=None, epochs=1, dest_dir
         if dest_dir is not None and epoch in checkpoints:
             os.makedirs(dest_dir, exist_ok=True)
             save_checkpoint(trainer.state_dict(), f'{dest_dir}/E{epoch:04}.pth')
+        if with_metrics and epoch % int(metrics_every) == 0:
+            now = trainer.state_dict()
+            tstart = int(m_rng.integers(0, 10)) % len(timelapse)
+            metrics[(epoch, 'train')] = _epoch_metrics(now, timelapse, labels if explicit_labels else None, parameters,
+                                                       list(range(tstart, len(timelapse), 10)))
+            metrics[(epoch, 'test')] = _epoch_metrics(now, test_timelapse, None, parameters,
+                                                      list(range(len(test_timelapse))))
     history = pd.DataFrame(history, index=list(COMPONENTS))
+    if with_metrics:
+        history.attrs['metrics'] = pd.DataFrame(metrics)
     if augmented:
         history.attrs['transforms'] = used
     return trainer.state_dict(), history

@@ -142,6 +142,27 @@ double axt_cnn_kernel_flops_per_tile(int kernel);
 int axt_preprocess_u16(const uint16_t *d_raw, const uint8_t *d_mask, int T, int H, int W, float offset,
                        float clip_lower, int log_correct, float scale, float *d_out, void *stream);
 
+/* The statistics Timelapse._standardize takes of the preprocessed frames before it scales them (Timelapse.py:286-302), per
+ * frame, over the values axt_preprocess_u16 would write with scale = 1 -- no frame is written, 2 B of traffic per pixel:
+ * n = how many values are != 0, sum and sumsq of the values (each f32 widened to f64 first), max of the values (0 for an
+ * empty frame). Deterministic: per-block partials go to d_scratch and a second launch adds them in a fixed order; no
+ * atomics, two calls give identical bits. *scratch_bytes: in, the size of d_scratch; out, the size needed. With
+ * d_scratch == NULL the call only answers that size (d_raw, d_stats may be NULL then). d_stats [T] on the device. */
+typedef struct {
+    int64_t n;
+    double sum, sumsq;
+    float max, reserved;
+} axt_frame_stats;
+int axt_preprocess_stats_u16(const uint16_t *d_raw, const uint8_t *d_mask, int T, int H, int W, float offset,
+                             float clip_lower, int log_correct, axt_frame_stats *d_stats, void *d_scratch,
+                             size_t *scratch_bytes, void *stream);
+
+/* axt_preprocess_u16 with one scale per frame (STANDARDIZE_FRAMEWISE, Timelapse.py:309-312): d_scale f32 [T] on the device,
+ * each > 0 (the caller's promise: the values are not read back here). Bit-equal to axt_preprocess_u16 on each frame alone
+ * with that frame's scale. */
+int axt_preprocess_u16_framewise(const uint16_t *d_raw, const uint8_t *d_mask, int T, int H, int W, float offset,
+                                 float clip_lower, int log_correct, const float *d_scale, float *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Tiling: which 512x512 tiles the reference keeps (Timelapse.py:551-558): a tile is kept if
  * any pixel of it is > 0 at any t. d_occ u8 [ceil(H/512)*ceil(W/512)] row-major, 1 = keep.
