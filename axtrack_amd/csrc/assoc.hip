@@ -289,28 +289,40 @@ int axt_path_cells(const int32_t *d_xa, const int32_t *d_ya, int na, const int32
                                 (hipStream_t)stream, d_cells);
 }
 
-static int build_arcs_impl(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                           const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                           int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
-                           const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, const VisParams *vis,
-                           const int16_t *d_ext_table, void *stream, const int32_t *d_src_count = nullptr)
+int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, const int32_t *d_src_count, int n_frames,
+                   int cap, const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
+                   const float *d_hist, const double *d_hist_sum, double vis_weight, double miss_rate, double edge_cost_thr,
+                   int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
+                   const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, const int16_t *d_len_table, void *stream)
 {
-    const int32_t *src_count = d_src_count ? d_src_count : d_count;
     AXT_REQUIRE(d_x && d_y && d_count && h_dmax && d_row_ptr && d_work && n_arcs, "null argument");
     AXT_REQUIRE(n_frames >= 1 && cap >= 1 && max_gap >= 1 && max_gap <= 8, "bad argument");
+    const bool vis = d_hist != nullptr;
+    VisParams vp{};
+    if (vis) {
+        AXT_REQUIRE(d_hist_sum, "axt_build_arcs: null histogram sums");
+        AXT_REQUIRE(vis_weight > 0.0 && vis_weight <= 1.0, "axt_build_arcs: weight %g outside (0,1]", vis_weight);
+        vp.hist = d_hist;
+        vp.hsum = d_hist_sum;
+        vp.w = vis_weight;
+        vp.thr = edge_cost_thr;
+        for (int g = 0; g < 8; ++g) vp.mp[g] = pow(miss_rate, (double)g);          // miss_rate ** (gap - 1), as Python computes it
+        d_cost_units = nullptr;
+    }
+    if (d_len_table) grid = nullptr;
+    const int32_t *src_count = d_src_count ? d_src_count : d_count;
     hipStream_t st = (hipStream_t)stream;
     // d_work layout: cnt [n_frames*cap*max_gap] | frame_off [n_frames+1] | dmax [max_gap] | pad |
     //                masked grids only: Dtmp i16 [n_frames*cap*max_gap*cap]
     int *cnt = d_work;
     int *frame_off = d_work + (size_t)n_frames * cap * max_gap;
     int *dmax = frame_off + n_frames + 1;
-    // path lengths from a table: the caller's (d_ext_table) or the one the masked-grid search fills in d_work
-    const short *Dtmp = d_ext_table ? d_ext_table
+    // path lengths from a table: the caller's (d_len_table) or the one the masked-grid search fills in d_work
+    const short *Dtmp = d_len_table ? d_len_table
                                     : reinterpret_cast<short *>(d_work + (((size_t)n_frames * cap * max_gap + n_frames + 1 + max_gap + 3) & ~(size_t)3));
-    const bool table = grid != nullptr || d_ext_table != nullptr;
+    const bool table = grid != nullptr || d_len_table != nullptr;
     const dim3 grid_dim(n_frames, 8), block(256);
     const bool fill = d_col != nullptr;
-    const VisParams vp = vis ? *vis : VisParams{};
     // the four (table, appearance) variants of one pass
     auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, grid_dim, block, 0, st, d_x, d_y, d_count, src_count, frame_off, n_frames, cap, H, W, max_dist, conn8,
@@ -323,7 +335,7 @@ static int build_arcs_impl(const int32_t *d_x, const int32_t *d_y, const int32_t
         AXT_CHECK_HIP(hipMemcpyAsync(dmax, h_dmax, sizeof(int) * max_gap, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(frame_offsets_kernel, dim3(1), dim3(1024), 0, st, d_count, n_frames, cap, frame_off);
         AXT_LAUNCH_CHECK();
-        if (grid && !d_ext_table) {
+        if (grid) {
             const int rc = axt_masked_distance_table(grid, d_x, d_y, d_count, src_count, n_frames, cap, max_dist, max_gap, h_dmax,
                                                      dmax, const_cast<short *>(Dtmp), st);
             if (rc) return rc;
@@ -355,66 +367,6 @@ static int build_arcs_impl(const int32_t *d_x, const int32_t *d_y, const int32_t
     else launch(arcs_open_kernel<true, false, false>);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
-}
-
-int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                   const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                   int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
-                   const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, void *stream)
-{
-    return build_arcs_impl(d_x, d_y, d_count, n_frames, cap, grid, H, W, max_dist, conn8, max_gap, h_dmax, d_row_ptr, d_work,
-                           d_col, d_len, d_gap, d_cost_units, d_cost, n_arcs, nullptr, nullptr, stream);
-}
-
-int axt_build_arcs_from_lengths(const int16_t *d_len_table, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
-                                int n_frames, int cap, int max_dist, int max_gap, const int32_t *h_dmax,
-                                int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
-                                const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, void *stream)
-{
-    AXT_REQUIRE(d_len_table, "axt_build_arcs_from_lengths: null table");
-    return build_arcs_impl(d_x, d_y, d_count, n_frames, cap, nullptr, 0, 0, max_dist, 0, max_gap, h_dmax, d_row_ptr, d_work,
-                           d_col, d_len, d_gap, d_cost_units, d_cost, n_arcs, nullptr, d_len_table, stream);
-}
-
-int axt_build_arcs_vis(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                       const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                       const float *d_hist, const double *d_hist_sum, double vis_weight, double miss_rate,
-                       double edge_cost_thr, int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len,
-                       uint8_t *d_gap, int64_t *d_cost, int64_t *n_arcs, void *stream)
-{
-    AXT_REQUIRE(d_hist && d_hist_sum, "axt_build_arcs_vis: null histogram argument");
-    AXT_REQUIRE(vis_weight > 0.0 && vis_weight <= 1.0, "axt_build_arcs_vis: weight %g outside (0,1]", vis_weight);
-    VisParams vp;
-    vp.hist = d_hist;
-    vp.hsum = d_hist_sum;
-    vp.w = vis_weight;
-    vp.thr = edge_cost_thr;
-    for (int g = 0; g < 8; ++g) vp.mp[g] = pow(miss_rate, (double)g);          // miss_rate ** (gap - 1), as Python computes it
-    return build_arcs_impl(d_x, d_y, d_count, n_frames, cap, grid, H, W, max_dist, conn8, max_gap, h_dmax, d_row_ptr, d_work,
-                           d_col, d_len, d_gap, nullptr, d_cost, n_arcs, &vp, nullptr, stream);
-}
-
-int axt_build_arcs_rows(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, const int32_t *d_src_count,
-                        int n_frames, int cap, const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
-                        const int32_t *h_dmax, const float *d_hist, const double *d_hist_sum, double vis_weight,
-                        double miss_rate, double edge_cost_thr, int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col,
-                        int16_t *d_len, uint8_t *d_gap, const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs,
-                        const int16_t *d_len_table, void *stream)
-{
-    if (!d_hist)
-        return build_arcs_impl(d_x, d_y, d_count, n_frames, cap, d_len_table ? nullptr : grid, H, W, max_dist, conn8, max_gap,
-                               h_dmax, d_row_ptr, d_work, d_col, d_len, d_gap, d_cost_units, d_cost, n_arcs, nullptr, d_len_table,
-                               stream, d_src_count);
-    AXT_REQUIRE(d_hist_sum, "axt_build_arcs_rows: null histogram sums");
-    AXT_REQUIRE(vis_weight > 0.0 && vis_weight <= 1.0, "axt_build_arcs_rows: weight %g outside (0,1]", vis_weight);
-    VisParams vp;
-    vp.hist = d_hist;
-    vp.hsum = d_hist_sum;
-    vp.w = vis_weight;
-    vp.thr = edge_cost_thr;
-    for (int g = 0; g < 8; ++g) vp.mp[g] = pow(miss_rate, (double)g);
-    return build_arcs_impl(d_x, d_y, d_count, n_frames, cap, d_len_table ? nullptr : grid, H, W, max_dist, conn8, max_gap, h_dmax,
-                           d_row_ptr, d_work, d_col, d_len, d_gap, nullptr, d_cost, n_arcs, &vp, d_len_table, stream, d_src_count);
 }
 
 }  // extern "C"

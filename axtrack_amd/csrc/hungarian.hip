@@ -143,7 +143,7 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
     // cost of linking row i to column j (HINF: not admitted)
     auto link_cost = [&](int i, int j) -> long {
         if (!col_ok[j]) return HINF;
-        if (ctab)                            // link costs given per pair (the appearance term: axt_hungarian_pairs_costs)
+        if (ctab)                            // link costs given per pair (the appearance term: d_ctab of axt_hungarian_pairs)
             return ctab[(((long)t * cap + i) * tab_gaps + (GAP - 1)) * cap + j];
         int d;
         if (dtab) {                          // masked grid: path lengths from the arc builder's searches (<= 0: none)
@@ -567,6 +567,10 @@ __global__ void fill2_int_kernel(int *p, int *q, long n, int v)
 // (predecessor index in frame t-1 / t-2, or -1). Frame-sharded runs give every rank its own range and combine the
 // arrays with one element-wise MAX all-reduce (entries not owned stay -1; the one redundant boundary pair is
 // deterministic, so equal on both ranks). d_work i32 [2*n_frames*cap + n_frames + 1].
+// d_ctab != NULL: the link costs are GIVEN, i64 [n_frames][cap][max_gap][cap], entry (t, i, g-1, j) = the integer cost
+// (axt_arc_cost_int, kind 3, global detection indices) of linking detection i of frame t to detection j of frame t+g, or
+// 0x3fffffffffffffff where the link is not admitted. Used for cost models the closed form does not cover (the appearance
+// term: the costs of axt_build_arcs with d_hist scattered into the table).
 namespace {
 __global__ void range_count_kernel(const int *__restrict__ count, int *__restrict__ out, int n, int a, int b)
 {
@@ -575,15 +579,27 @@ __global__ void range_count_kernel(const int *__restrict__ count, int *__restric
 }
 }  // namespace
 
-static int hungarian_pairs_impl(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                                const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
-                                const int32_t *h_dmax, const int64_t *d_cost_units, int64_t thr_units, int t_begin,
-                                int t_end, int32_t *d_pred, int32_t *d_work, void *stream, const int64_t *d_ctab)
+extern "C" int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
+                                   const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
+                                   const int32_t *h_dmax, const int64_t *d_cost_units, int64_t thr_units, int t_begin,
+                                   int t_end, int32_t *d_pred, int32_t *d_work, void *stream, const int64_t *d_ctab)
 {
-    AXT_REQUIRE(d_x && d_y && d_count && h_dmax && d_cost_units && d_work && d_pred, "null argument");
+    AXT_REQUIRE(d_x && d_y && d_count && (d_ctab || (h_dmax && d_cost_units)) && d_work && d_pred, "null argument");
     AXT_REQUIRE(n_frames >= 1 && cap >= 1 && cap <= 2048, "axt_hungarian_pairs: cap %d out of range [1,2048]", cap);
     AXT_REQUIRE(max_gap == 1 || max_gap == 2, "axt_hungarian_pairs: max_gap must be 1 or 2");
     AXT_REQUIRE(t_begin >= 0 && t_begin <= t_end && t_end <= n_frames, "axt_hungarian_pairs: bad frame range [%d,%d)", t_begin, t_end);
+    int dmax[2] = {0, 0};                          // the admission limits per gap (h_dmax may be NULL, or hold one entry)
+    if (d_ctab) {
+        // Link costs given: the kernels use neither path lengths nor limits nor units (they stage units[0 .. limit] in LDS,
+        // so the pointer must be readable: the table itself). What they still take as arguments is fixed here, because
+        // lds_base below depends on max_dist (tests/hungarian_reference.dispatch restates it).
+        H = W = 1 << 20;
+        max_dist = 1;
+        conn8 = 0;
+        d_cost_units = d_ctab;
+    } else {
+        for (int g = 0; g < max_gap; ++g) dmax[g] = h_dmax[g];
+    }
     hipStream_t st = (hipStream_t)stream;
     const long slots = (long)n_frames * cap;
     int *pred1 = d_pred, *pred2 = d_pred + slots;
@@ -629,7 +645,7 @@ static int hungarian_pairs_impl(const int32_t *d_x, const int32_t *d_y, const in
     }
     if (e1 > t_begin) {
         hipLaunchKernelGGL((cap <= 192 ? hungarian_pair_kernel<1, 3> : cap <= 576 ? hungarian_pair_kernel<1, 9> : hungarian_pair_kernel<1, 0>), dim3(e1 - t_begin), dim3(cap <= 576 ? 256 : 64), lds, st, d_x, d_y, d_count, frame_off,
-                           n_frames, cap, H, W, max_dist, conn8, h_dmax[0], (const long *)d_cost_units, (long)thr_units,
+                           n_frames, cap, H, W, max_dist, conn8, dmax[0], (const long *)d_cost_units, (long)thr_units,
                            (const int *)nullptr, (const int *)nullptr, succ1, pred1, cdim, t_begin, dtab, max_gap,
                            (const long *)d_ctab);
         AXT_LAUNCH_CHECK();
@@ -637,44 +653,12 @@ static int hungarian_pairs_impl(const int32_t *d_x, const int32_t *d_y, const in
     const int e2 = t_end < n_frames - 2 ? t_end : n_frames - 2;
     if (max_gap == 2 && e2 > t_begin) {
         hipLaunchKernelGGL((cap <= 192 ? hungarian_pair_kernel<2, 3> : cap <= 576 ? hungarian_pair_kernel<2, 9> : hungarian_pair_kernel<2, 0>), dim3(e2 - t_begin), dim3(cap <= 576 ? 256 : 64), lds, st, d_x, d_y, d_count, frame_off,
-                           n_frames, cap, H, W, max_dist, conn8, h_dmax[1],
+                           n_frames, cap, H, W, max_dist, conn8, dmax[1],
                            (const long *)d_cost_units + (max_dist + 1), (long)thr_units, (const int *)succ1,
                            (const int *)pred1, succ2, pred2, cdim, t_begin, dtab, max_gap, (const long *)d_ctab);
         AXT_LAUNCH_CHECK();
     }
     return AXT_OK;
-}
-
-extern "C" int axt_hungarian_pairs_grid(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                                        const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
-                                        const int32_t *h_dmax, const int64_t *d_cost_units, int64_t thr_units, int t_begin,
-                                        int t_end, int32_t *d_pred, int32_t *d_work, void *stream)
-{
-    return hungarian_pairs_impl(d_x, d_y, d_count, n_frames, cap, grid, H, W, max_dist, conn8, max_gap, h_dmax, d_cost_units,
-                                thr_units, t_begin, t_end, d_pred, d_work, stream, nullptr);
-}
-
-// The same passes with the link costs GIVEN: d_ctab i64 [n_frames][cap][max_gap][cap], entry (t, i, g-1, j) = the integer cost
-// (axt_arc_cost_int, kind 3, global detection indices) of linking detection i of frame t to detection j of frame t+g, or
-// 0x3fffffffffffffff where the link is not admitted. Used for cost models the closed form does not cover (the appearance
-// term: the costs of axt_build_arcs_vis scattered into the table).
-extern "C" int axt_hungarian_pairs_costs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                                         int max_gap, const int64_t *d_ctab, int64_t thr_units, int t_begin, int t_end,
-                                         int32_t *d_pred, int32_t *d_work, void *stream)
-{
-    AXT_REQUIRE(d_ctab != nullptr, "axt_hungarian_pairs_costs: null cost table");
-    const int32_t dmax0[2] = {0, 0};
-    return hungarian_pairs_impl(d_x, d_y, d_count, n_frames, cap, nullptr, 1 << 20, 1 << 20, 1, 0, max_gap, dmax0,
-                                (const int64_t *)d_ctab, thr_units, t_begin, t_end, d_pred, d_work, stream, d_ctab);
-}
-
-extern "C" int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                                   int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                                   const int64_t *d_cost_units, int64_t thr_units, int t_begin, int t_end,
-                                   int32_t *d_pred, int32_t *d_work, void *stream)
-{
-    return axt_hungarian_pairs_grid(d_x, d_y, d_count, n_frames, cap, nullptr, H, W, max_dist, conn8, max_gap, h_dmax,
-                                    d_cost_units, thr_units, t_begin, t_end, d_pred, d_work, stream);
 }
 
 // Chains of links -> trajectory ids numbered by (first frame, index). d_pred as written by axt_hungarian_pairs
@@ -706,21 +690,6 @@ extern "C" int axt_chain_tracks(const int32_t *d_count, int n_frames, int cap, c
     hipLaunchKernelGGL(chain_assign_kernel, dim3(nb), dim3(256), 0, st, (const int *)ra, (const int *)rb, d_track, slots);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
-}
-
-// Both steps for a whole timelapse on one GPU. d_work i32 [4*n_frames*cap + n_frames + 1].
-extern "C" int axt_hungarian_assoc(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                                   int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                                   const int64_t *d_cost_units, int64_t thr_units, int32_t *d_work, int32_t *d_track,
-                                   int32_t *d_n_tracks, void *stream)
-{
-    AXT_REQUIRE(d_work && n_frames >= 1 && cap >= 1, "bad argument");
-    const long slots = (long)n_frames * cap;
-    int32_t *pred = d_work, *work = d_work + 2 * slots;
-    int rc = axt_hungarian_pairs(d_x, d_y, d_count, n_frames, cap, H, W, max_dist, conn8, max_gap, h_dmax, d_cost_units,
-                                 thr_units, 0, n_frames, pred, work, stream);
-    if (rc) return rc;
-    return axt_chain_tracks(d_count, n_frames, cap, pred, work, d_track, d_n_tracks, stream);
 }
 
 #ifdef AXT_HUNG_STATS

@@ -26,7 +26,7 @@ def transition_cost_table(P, max_px=hp.MAX_PX_ASSOC_DIST, vis_sim=0.0):
     D = 0..max_px and gap = 1..MCF_MAX_NUM_MISSES+1, numpy f64 exactly as the reference computes
     it, for one value of the visual similarity. Returns (cost f64 [gaps, max_px+1], dmax i32 [gaps]) with
     dmax = largest D whose cost < MCF_EDGE_COST_THR. With MCF_VIS_SIM_WEIGHT = 0 the table IS the cost model; with
-    a weight the costs are computed per pair on the GPU (axt_build_arcs_vis) and the table for vis_sim = 1 only
+    a weight the costs are computed per pair on the GPU (axt_build_arcs with d_hist) and the table for vis_sim = 1 only
     bounds the candidate pairs."""
     w = P['MCF_VIS_SIM_WEIGHT']
     gaps = P['MCF_MAX_NUM_MISSES'] + 1
@@ -546,7 +546,7 @@ class AxonDetections(object):
 
     def _length_table_from_paths(self, paths):
         """_get_astar_path_distances (AxonDetections.py:717-752) of a cached path dictionary, as the i16 table
-        [F, cap, gaps, cap] axt_build_arcs_from_lengths reads: getnnz() of a path, 0 (= none) for None."""
+        [F, cap, gaps, cap] axt_build_arcs reads as d_len_table: getnnz() of a path, 0 (= none) for None."""
         cnt = self._host_dets()[0]
         F, cap, gaps = len(self), self.d_x.shape[1], self.P['MCF_MAX_NUM_MISSES'] + 1
         table = np.zeros((F, cap, gaps, cap), np.int16)
@@ -798,7 +798,7 @@ class AxonDetections(object):
         shard = self._shard                             # set by gather_detections(): solve only this rank's frame pairs
         ctab = None
         if vis is not None or self.dataset.mask3d is not None:
-            # the appearance term: the link costs are those of the flow tracker's arcs (axt_build_arcs_vis: the same
+            # the appearance term: the link costs are those of the flow tracker's arcs (axt_build_arcs with d_hist: the same
             # admission, the same integers), scattered into a dense table per frame pair
             # (likewise a mask that changes over time: one pass of the arc builder per distinct mask)
             row_ptr, col, _, gap, cost = self._arcs(dmax, units, vis, self._exact_lengths_if_needed(dmax), None)
@@ -876,7 +876,7 @@ class AxonDetections(object):
 
     def _hungarian_cost_table(self, row_ptr, col, gap, cost, gaps):
         """Arcs (CSR by global tail index, global head indices, integer costs) -> i64 [F, cap, gaps, cap] with
-        hp.HUNGARIAN_NO_LINK where there is no arc: what axt_hungarian_pairs_costs reads. All on the device."""
+        hp.HUNGARIAN_NO_LINK where there is no arc: what axt_hungarian_pairs reads as d_ctab. All on the device."""
         F, cap = self.d_x.shape
         if F * cap * gaps * cap * 8 > 4 << 30:
             raise NotImplementedError(f'the cost table of {F} frames x {cap} detection slots would take '

@@ -431,33 +431,15 @@ def build_arcs(x, y, count, H, W, dmax, cost_units=None, mask=None, max_dist=MAX
     work = torch.empty((n_work,), dtype=torch.int32, device=dev)
     n_arcs = ctypes.c_int64(0)
     lib = _lib.load()
-    head = (x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames, cap, mask._h if mask is not None else None, H, W, int(max_dist),
-            int(bool(conn8)), max_gap, h_dmax.ctypes.data)
-    if vis is not None:
-        head += (vis['hist'].data_ptr(), vis['hsum'].data_ptr(), float(vis['weight']), float(vis['miss_rate']), float(vis['thr']))
-    head += (row_ptr.data_ptr(), work.data_ptr())
+    hist, hsum, weight, miss_rate, thr = (None, None, 0.0, 0.0, 0.0) if vis is None else (
+        vis['hist'], vis['hsum'], vis['weight'], vis['miss_rate'], vis['thr'])
 
     def call(col, length, gap, cu, cost, what):
-        if src_count is not None or (length_table is not None and vis is not None):
-            v = vis or {}
-            rc = lib.axt_build_arcs_rows(x.data_ptr(), y.data_ptr(), count.data_ptr(), _lib.dptr(src_count), n_frames, cap,
-                                         mask._h if mask is not None else None, H, W, int(max_dist), int(bool(conn8)), max_gap,
-                                         h_dmax.ctypes.data, v['hist'].data_ptr() if vis else None,
-                                         v['hsum'].data_ptr() if vis else None, float(v.get('weight', 0.0)),
-                                         float(v.get('miss_rate', 0.0)), float(v.get('thr', 0.0)), row_ptr.data_ptr(),
-                                         work.data_ptr(), _lib.dptr(col), _lib.dptr(length), _lib.dptr(gap), _lib.dptr(cu),
-                                         _lib.dptr(cost), ctypes.byref(n_arcs), _lib.dptr(length_table), _stream())
-        elif length_table is not None:
-            rc = lib.axt_build_arcs_from_lengths(length_table.data_ptr(), x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames,
-                                                 cap, int(max_dist), max_gap, h_dmax.ctypes.data, row_ptr.data_ptr(),
-                                                 work.data_ptr(), _lib.dptr(col), _lib.dptr(length), _lib.dptr(gap),
-                                                 _lib.dptr(cu), _lib.dptr(cost), ctypes.byref(n_arcs), _stream())
-        elif vis is None:
-            rc = lib.axt_build_arcs(*head, _lib.dptr(col), _lib.dptr(length), _lib.dptr(gap), _lib.dptr(cu), _lib.dptr(cost),
-                                    ctypes.byref(n_arcs), _stream())
-        else:
-            rc = lib.axt_build_arcs_vis(*head, _lib.dptr(col), _lib.dptr(length), _lib.dptr(gap), _lib.dptr(cost),
-                                        ctypes.byref(n_arcs), _stream())
+        rc = lib.axt_build_arcs(x.data_ptr(), y.data_ptr(), count.data_ptr(), _lib.dptr(src_count), n_frames, cap,
+                                mask._h if mask is not None else None, H, W, int(max_dist), int(bool(conn8)), max_gap,
+                                h_dmax.ctypes.data, _lib.dptr(hist), _lib.dptr(hsum), float(weight), float(miss_rate),
+                                float(thr), row_ptr.data_ptr(), work.data_ptr(), _lib.dptr(col), _lib.dptr(length), _lib.dptr(gap),
+                                _lib.dptr(cu), _lib.dptr(cost), ctypes.byref(n_arcs), _lib.dptr(length_table), _stream())
         _lib.check(rc, f'axt_build_arcs({what})')
 
     with torch.cuda.device(dev):
@@ -488,7 +470,7 @@ def hungarian_assoc(x, y, count, H, W, dmax, cost_units, thr_units, max_dist=MAX
     combined over `group` with one MAX all-reduce and every rank numbers the chains (frame-sharded runs).
     mask: None (all-ones) or a Grid: path lengths then come from the masked-grid searches of the arc builder.
     ctab: optional i64 device tensor [F, cap, len(dmax), cap] of link costs (HUNGARIAN_NO_LINK where not admitted), used
-    instead of the costs derived from the path lengths (axt_hungarian_pairs_costs; the appearance term).
+    instead of the costs derived from the path lengths (d_ctab of axt_hungarian_pairs; the appearance term).
     Returns (track i32 [F,cap] device tensor, n_tracks device tensor [1])."""
     n_frames, cap = x.shape
     max_gap = len(dmax)
@@ -503,18 +485,13 @@ def hungarian_assoc(x, y, count, H, W, dmax, cost_units, thr_units, max_dist=MAX
     a, b = (0, n_frames) if frame_range is None else frame_range
     lib = _lib.load()
     with torch.cuda.device(dev):
-        if ctab is not None:
-            if ctab.dtype != torch.int64 or tuple(ctab.shape) != (n_frames, cap, max_gap, cap) or not ctab.is_contiguous():
-                raise ValueError(f'ctab must be a contiguous int64 tensor [{n_frames}, {cap}, {max_gap}, {cap}]')
-            _lib.check(lib.axt_hungarian_pairs_costs(x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames, cap, max_gap,
-                                                     ctab.data_ptr(), int(thr_units), int(a), int(b), pred.data_ptr(),
-                                                     work.data_ptr(), _stream()), 'axt_hungarian_pairs_costs')
-        else:
-            _lib.check(lib.axt_hungarian_pairs_grid(x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames, cap,
-                                                    mask._h if mask is not None else None, H, W,
-                                                    int(max_dist), int(bool(conn8)), max_gap, h_dmax.ctypes.data,
-                                                    cu.data_ptr(), int(thr_units), int(a), int(b), pred.data_ptr(),
-                                                    work.data_ptr(), _stream()), 'axt_hungarian_pairs_grid')
+        if ctab is not None and (ctab.dtype != torch.int64 or tuple(ctab.shape) != (n_frames, cap, max_gap, cap)
+                                 or not ctab.is_contiguous()):
+            raise ValueError(f'ctab must be a contiguous int64 tensor [{n_frames}, {cap}, {max_gap}, {cap}]')
+        _lib.check(lib.axt_hungarian_pairs(x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames, cap,
+                                           mask._h if mask is not None else None, H, W, int(max_dist), int(bool(conn8)),
+                                           max_gap, h_dmax.ctypes.data, cu.data_ptr(), int(thr_units), int(a), int(b),
+                                           pred.data_ptr(), work.data_ptr(), _stream(), _lib.dptr(ctab)), 'axt_hungarian_pairs')
         if frame_range is not None:
             import torch.distributed as dist
             from . import sharded

@@ -242,22 +242,30 @@ int axt_path_cells(const int32_t *d_xa, const int32_t *d_ya, int na,
  * A detection on the mask gets all its path lengths from one bit-parallel breadth-first search (depth h_dmax-1 <= 250
  * moves) over the steps that keep that count minimal; a detection off the mask from a label-correcting search on
  * (off-mask cells, moves) inside the window paths of <= dmax cells cannot leave, checked against the same counts
- * (masks with more than 64 components: on-mask search within the component + the exact search of axt_path_cost). */
-int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                   const axt_grid *grid, int H, int W, int max_dist, int conn8,
+ * (masks with more than 64 components: on-mask search within the component + the exact search of axt_path_cost).
+ * Optional inputs, each a nullable pointer:
+ *   d_src_count (i32 [n_frames]) -- NULL: every row. Otherwise rows are built only for the first d_src_count[t] detections
+ *     of frame t: a rank of a frame-sharded run (one process per GPU after the all-gather of the detections, SURVEY.md
+ *     section 8e) passes its own frames' counts and zeros elsewhere, while targets, numbering and integer costs stay those
+ *     of the whole timelapse (d_count), so that the ranks' arc lists, concatenated in rank order, are exactly the
+ *     single-process list. row_ptr covers all detections; rows outside the source frames are empty.
+ *   d_len_table (i16 [n_frames, cap, max_gap, cap]) -- NULL: the path lengths are computed. Otherwise entry [t][i][g-1][j] =
+ *     number of cells of the path between detection i of frame t and detection j of frame t+g, <= 0 = none; grid, H, W
+ *     and conn8 are not read. This is how path lengths cached by the reference ('{name}_astar_dets_paths.pkl': coo
+ *     matrices, length = getnnz(), AxonDetections.py:717-752) re-enter the pipeline. d_x / d_y are not read for lengths
+ *     but must be valid [n_frames, cap] arrays.
+ *   d_hist, d_hist_sum (axt_box_histograms below) with vis_weight in (0,1], miss_rate, edge_cost_thr -- d_hist NULL: costs
+ *     from d_cost_units, the three numbers are not read. Otherwise the appearance term: the cost is computed per pair,
+ *     d_cost_units is ignored and d_cost may be NULL. With d_len_table this is the combination the reference's parameter
+ *     search runs (assign_ids(astar_paths_cache='from') with MCF_VIS_SIM_WEIGHT > 0, AxonDetections.py:882,911-912). */
+int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, const int32_t *d_src_count,
+                   int n_frames, int cap, const axt_grid *grid, int H, int W, int max_dist, int conn8,
                    int max_gap, const int32_t *h_dmax,
+                   const float *d_hist, const double *d_hist_sum, double vis_weight, double miss_rate,
+                   double edge_cost_thr,
                    int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
-                   const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, void *stream);
-
-/* axt_build_arcs with the path lengths supplied by the caller instead of computed: d_len_table i16
- * [n_frames, cap, max_gap, cap], entry [t][i][g-1][j] = number of cells of the path between detection i of
- * frame t and detection j of frame t+g, <= 0 = none. This is how path lengths cached by the reference
- * ('{name}_astar_dets_paths.pkl': coo matrices, length = getnnz(), AxonDetections.py:717-752) re-enter the
- * pipeline. d_x / d_y are not read for lengths but must be valid [n_frames, cap] arrays. */
-int axt_build_arcs_from_lengths(const int16_t *d_len_table, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
-                                int n_frames, int cap, int max_dist, int max_gap, const int32_t *h_dmax,
-                                int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
-                                const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, void *stream);
+                   const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs,
+                   const int16_t *d_len_table, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Appearance term of the transition cost, MCF_VIS_SIM_WEIGHT > 0.
@@ -268,41 +276,16 @@ int axt_build_arcs_from_lengths(const int16_t *d_len_table, const int32_t *d_x, 
  * normalised. The crop starts at (max(y - box/2, 0), max(x - box/2, 0)) and is clipped at the far edges.
  * d_hist f32 [n_frames, cap, 180], d_hist_sum f64 [n_frames, cap] (bin sums, used by the distance).
  *
- * axt_build_arcs_vis = axt_build_arcs with the cost of transition_model (:100-118) computed per pair:
+ * axt_build_arcs with d_hist = these histograms computes the cost of transition_model (:100-118) per pair:
  *   cost = -log((1-w) * (1 - D/max_dist) * miss_rate^(gap-1) + w * (1 - d_B(hist_a, hist_b)) + 1e-6)
  * d_B = cv2.compareHist(.., HISTCMP_BHATTACHARYYA); an arc is kept iff cost < edge_cost_thr, and
  * d_cost (may be NULL) receives round(cost * 1e6) << 16 | hash16(3, a, b). h_dmax[g-1] only bounds the
- * candidates: pass the largest D whose cost with similarity 1 is still below the threshold. Same two
- * phases and scratch as axt_build_arcs. cv2 is absent from the reference tree: parity unpinned.
+ * candidates: pass the largest D whose cost with similarity 1 is still below the threshold.
+ * cv2 is absent from the reference tree: parity unpinned.
  * ------------------------------------------------------------------------------------------ */
 int axt_box_histograms(const float *d_frames, int T_all, int H, int W, int t_offset, const int32_t *d_x,
                        const int32_t *d_y, const int32_t *d_count, int n_frames, int cap, int box,
                        float *d_hist, double *d_hist_sum, void *stream);
-int axt_build_arcs_vis(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                       const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                       const float *d_hist, const double *d_hist_sum, double vis_weight, double miss_rate,
-                       double edge_cost_thr, int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len,
-                       uint8_t *d_gap, int64_t *d_cost, int64_t *n_arcs, void *stream);
-
-/* The same arc builder (_compute_detections_astar_paths + transition_model + the tracker's edge admission,
- * AxonDetections.py:526-629,663-690, mincostflow_models.py:67-119) for a frame-sharded run (one process per GPU after
- * the all-gather of the detections): rows are built only for the first d_src_count[t] detections of every frame t -- a rank passes
- * its own frames' counts and zeros elsewhere -- while targets, detection numbering and integer costs are those of the
- * whole timelapse (d_count), so that the ranks' arc lists, concatenated in rank order, are exactly the single-process
- * list. d_hist == NULL: costs from d_cost_units as in axt_build_arcs; otherwise the appearance term as in
- * axt_build_arcs_vis (d_cost_units ignored). row_ptr covers all detections; rows outside the source frames are empty.
- * This is the general entry point: d_src_count == NULL builds every row; d_len_table != NULL (i16
- * [n_frames, cap, max_gap, cap], as for axt_build_arcs_from_lengths) takes the path lengths from a cache instead of
- * computing them (grid ignored) -- the combination the reference's parameter search runs with the appearance term
- * (assign_ids(astar_paths_cache='from') with MCF_VIS_SIM_WEIGHT > 0, AxonDetections.py:882,911-912). */
-int axt_build_arcs_rows(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, const int32_t *d_src_count,
-                        int n_frames, int cap, const axt_grid *grid, int H, int W, int max_dist, int conn8,
-                        int max_gap, const int32_t *h_dmax,
-                        const float *d_hist, const double *d_hist_sum, double vis_weight, double miss_rate,
-                        double edge_cost_thr,
-                        int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
-                        const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs,
-                        const int16_t *d_len_table, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Global data association. Replaces libmot's MinCostFlowTracker as driven by
@@ -367,42 +350,31 @@ void axt_mcf_shard_free(axt_mcf_shard *shard);
  * to b (frame t+g) costs transition_model(D(a,b), g) (mincostflow_models.py:67-119) and is admitted for D <= h_dmax[g-1]; leaving a detection
  * without successor costs thr_units (= round(MCF_EDGE_COST_THR * 1e6)). Every frame pair
  * (t,t+1) is solved exactly and independently (one wavefront each), then (t,t+2) among the
- * detections left unlinked, then chains are numbered by (first frame, index).
- * d_cost_units i64 [max_gap, max_dist+1]; d_work i32 [4*n_frames*cap + n_frames + 1] scratch;
- * d_track i32 [n_frames, cap]: trajectory id of every detection slot (-1 beyond count);
- * d_n_tracks i32 [1]. All-ones mask only (closed-form path lengths). Asynchronous.
+ * detections left unlinked, then chains are numbered by (first frame, index). Asynchronous.
+ *
+ * axt_hungarian_pairs solves the frame pairs of the source frames [t_begin, t_end) into d_pred = pred1 | pred2 (i32
+ * [2, n_frames*cap], predecessor index in frame t-1 / t-2 or -1; entries of other frames stay -1). A frame-sharded rank
+ * passes its own range, and the ranks combine d_pred with one element-wise MAX all-reduce. max_gap is 1 or 2, cap at most
+ * 2048; d_cost_units i64 [max_gap, max_dist+1]; d_work i32 [2*n_frames*cap + n_frames + 1] scratch.
+ * Optional inputs, each a nullable pointer:
+ *   grid -- NULL: all-ones mask, closed-form path lengths. Otherwise the path lengths of the pairs come from the
+ *     masked-grid searches of the arc builder (_compute_detections_astar_paths on weights {1 on mask, 65536 off},
+ *     AxonDetections.py:526-629).
+ *   d_ctab (i64 [n_frames][cap][max_gap][cap]) -- NULL: costs from the path lengths and d_cost_units. Otherwise the link
+ *     costs are GIVEN: entry (t, i, g-1, j) = the integer cost (axt_arc_cost_int, kind 3, global detection indices) of
+ *     linking detection i of frame t to detection j of frame t+g, or 0x3fffffffffffffff where the link is not admitted;
+ *     grid, H, W, max_dist, conn8, h_dmax and d_cost_units are not read and may be NULL or 0. For cost models the closed
+ *     form does not cover -- the appearance term of transition_model (mincostflow_models.py:107-113,
+ *     MCF_VIS_SIM_WEIGHT > 0): the costs of axt_build_arcs with d_hist scattered into the table.
+ *
+ * axt_chain_tracks numbers the chains of d_pred (after the all-reduce in sharded runs): d_track i32 [n_frames, cap] =
+ * trajectory id of every detection slot (-1 beyond count), d_n_tracks i32 [1]; d_work i32 [2*n_frames*cap] scratch.
  * ------------------------------------------------------------------------------------------ */
-int axt_hungarian_assoc(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                        int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                        const int64_t *d_cost_units, int64_t thr_units, int32_t *d_work,
-                        int32_t *d_track, int32_t *d_n_tracks, void *stream);
-
-/* The two halves of axt_hungarian_assoc (same cost model, mincostflow_models.py:67-119; stands where the reference
- * runs its tracker, AxonDetections.py:663-690), for frame-sharded runs: every rank solves the frame pairs of its own
- * source frames [t_begin, t_end) into d_pred = pred1 | pred2 (i32 [2, n_frames*cap], predecessor index in frame
- * t-1 / t-2 or -1; entries of other ranks' frames stay -1), the ranks combine d_pred with one element-wise MAX
- * all-reduce, then each numbers the chains. d_work: i32 [2*n_frames*cap + n_frames + 1] for the pairs,
- * i32 [2*n_frames*cap] for the chains. */
 int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                        int H, int W, int max_dist, int conn8, int max_gap, const int32_t *h_dmax,
-                        const int64_t *d_cost_units, int64_t thr_units, int t_begin, int t_end,
-                        int32_t *d_pred, int32_t *d_work, void *stream);
-/* axt_hungarian_pairs on a masked grid (grid = NULL: identical to it): the path lengths of the pairs come from the
- * masked-grid searches of the arc builder (_compute_detections_astar_paths on weights {1 on mask, 65536 off},
- * AxonDetections.py:526-629) instead of the closed form. */
-int axt_hungarian_pairs_grid(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                             const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
-                             const int32_t *h_dmax, const int64_t *d_cost_units, int64_t thr_units,
-                             int t_begin, int t_end, int32_t *d_pred, int32_t *d_work, void *stream);
-/* The same two passes with the link costs GIVEN instead of derived from the path lengths: d_ctab i64
- * [n_frames][cap][max_gap][cap], entry (t, i, g-1, j) = the integer cost (axt_arc_cost_int, kind 3, global detection
- * indices) of linking detection i of frame t to detection j of frame t+g, or 0x3fffffffffffffff where the link is not
- * admitted. For cost models the closed form does not cover -- the appearance term of transition_model
- * (mincostflow_models.py:107-113, MCF_VIS_SIM_WEIGHT > 0): the costs of axt_build_arcs_vis scattered into the table.
- * Build-side variant like axt_hungarian_pairs itself (the reference runs only the flow tracker). */
-int axt_hungarian_pairs_costs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
-                              int max_gap, const int64_t *d_ctab, int64_t thr_units, int t_begin, int t_end,
-                              int32_t *d_pred, int32_t *d_work, void *stream);
+                        const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
+                        const int32_t *h_dmax, const int64_t *d_cost_units, int64_t thr_units,
+                        int t_begin, int t_end, int32_t *d_pred, int32_t *d_work, void *stream,
+                        const int64_t *d_ctab);
 int axt_chain_tracks(const int32_t *d_count, int n_frames, int cap, const int32_t *d_pred, int32_t *d_work,
                      int32_t *d_track, int32_t *d_n_tracks, void *stream);
 

@@ -66,7 +66,7 @@ def geometric_costs(dets, H, W, mask=None, conn8=False, P=orc.DEFAULTS):
 
 
 def costs_to_table(costs, counts, cap, gaps=2):
-    """The dense table axt_hungarian_pairs_costs reads: i64 [F, cap, gaps, cap], NO_LINK where nothing is given."""
+    """The dense table axt_hungarian_pairs reads as d_ctab: i64 [F, cap, gaps, cap], NO_LINK where nothing is given."""
     F = len(counts)
     tab = np.full((F, cap, gaps, cap), NO_LINK, np.int64)
     for (t, g), c in costs.items():
@@ -268,7 +268,7 @@ def track_table(trajs, counts, cap):
 
 # ------------------------------------------------------------------------------------------------ dispatch (restated)
 def dispatch(cap, max_dist=500):
-    """(NC, cdim) of hungarian_pairs_impl for a slot count, restated from its formulas in axtrack_amd/csrc/hungarian.hip:
+    """(NC, cdim) of axt_hungarian_pairs for a slot count, restated from its formulas in axtrack_amd/csrc/hungarian.hip:
     `lds_base` (the two lines of `const size_t lds_base = ...`), `int cdim = cap < 96 ? cap : 96; if (lds_base + cdim*cdim*8 >
     160 KiB) cdim = 0;`, and the launches' `cap <= 192 ? <.,3> : cap <= 576 ? <.,9> : <.,0>`."""
     lds_base = cap * (3 * 8 + 8 * 4 + 2) + 8 + (max_dist + 2) * 8 + 8 + cap * 8 + (cap * 48 if cap <= 576 else 0)

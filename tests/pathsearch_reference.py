@@ -38,7 +38,7 @@ def lds3(max_gap, cap):
 class Case:
     """mask u8 [H, W]; frames: per frame a list of (x, y); cap slots per frame (fill: every free slot holds an
     out-of-grid anchor (-1, 0) and count == cap); misses = MCF_MAX_NUM_MISSES (max_gap - 1); env: overrides for the run;
-    src_count: rows built per frame (axt_build_arcs_rows) or None; routes: the deciding routes the case is there for;
+    src_count: rows built per frame (d_src_count of axt_build_arcs) or None; routes: the deciding routes the case is there for;
     named: {name: (tail (t, i), head (t, j), reference length or None for no arc)}."""
     name: str
     mask: np.ndarray

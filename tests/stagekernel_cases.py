@@ -15,8 +15,8 @@ from oracle import oracle as orc
 FRAME_CHUNK = 1024          # assoc.hip frame_offsets_kernel (`base += 1024`), ided.hip ided_slot_kernel (`f0 += 1024`)
 DET_CHUNK = 1024            # assoc.hip row_ptr_kernel (`base += 1024` over detections)
 TARGET_STEP = 64            # assoc.hip arcs_open_kernel (`j0 += 64`: one wave scans 64 targets per step)
-ARC_WAVES_PER_FRAME = 8 * 4  # assoc.hip build_arcs_impl `grid_dim(n_frames, 8)` x 256 threads = 4 waves
-MAX_GAP_LIMIT = 8           # assoc.hip build_arcs_impl (`max_gap <= 8`, VisParams::mp[8])
+ARC_WAVES_PER_FRAME = 8 * 4  # assoc.hip axt_build_arcs `grid_dim(n_frames, 8)` x 256 threads = 4 waves
+MAX_GAP_LIMIT = 8           # assoc.hip axt_build_arcs (`max_gap <= 8`, VisParams::mp[8])
 OBS_THREADS = 64            # assoc.hip axt_obs_costs launches conf_max_kernel / obs_cost_kernel with 64 threads
 PREP_BLOCK_CAP, PREP_THREADS, PREP_VEC = 2048, 256, 8       # preproc.hip axt_preprocess_u16 (`blocks > 256 * 8`), 8 px per lane
 PREP_GRID_PIXELS = PREP_BLOCK_CAP * PREP_THREADS * PREP_VEC  # 4 194 304: more pixels than this need the grid-stride loop
@@ -588,14 +588,14 @@ def vis_cases():
     facts = ['appearance term', 'max_gap > 2', 'nb > 64', 'two identical histograms']
     out = []
     for rows in (False, True):
-        c = _vis_base('vis_open' + ('_rows' if rows else ''), facts + (['src_count given (axt_build_arcs_rows)'] if rows else ['axt_build_arcs_vis']),
+        c = _vis_base('vis_open' + ('_rows' if rows else ''), facts + (['src_count given'] if rows else ['appearance term, all rows, computed lengths']),
                       31, False)
         if rows:
             c.src_count = c.count.copy()
         out.append(c)
     for rows in (False, True):
         c = _vis_base('vis_table' + ('_rows' if rows else ''), facts + ['length table', 'empty crop: histogram and sum 0', 'table entries <= 0',
-                                                                       'axt_build_arcs_rows']
+                                                                       'appearance term with a length table or src_count']
                       + (['src_count below the count of a frame'] if rows else []), 32, True)
         if rows:
             c.src_count = c.count.copy()
@@ -671,12 +671,12 @@ def _arc_facts(c):
         'src_count: own frames, zeros elsewhere': c.src_count is not None and bool(((c.src_count == 0) | (c.src_count == c.count)).all()
                                                                                      and (c.src_count == 0).any() and (c.src_count > 0).any()),
         'src_count below the count of a frame': c.src_count is not None and bool(((c.src_count > 0) & (c.src_count < c.count)).any()),
-        'src_count given (axt_build_arcs_rows)': c.src_count is not None,
+        'src_count given': c.src_count is not None,
         'length table': c.length_table is not None,
         'max_dist not above a limit': bool((c.max_dist <= np.asarray(c.dmax)).any()),
         'appearance term': c.vis is not None,
-        'axt_build_arcs_vis': c.vis is not None and c.src_count is None and c.length_table is None,
-        'axt_build_arcs_rows': c.src_count is not None or (c.vis is not None and c.length_table is not None),
+        'appearance term, all rows, computed lengths': c.vis is not None and c.src_count is None and c.length_table is None,
+        'appearance term with a length table or src_count': c.src_count is not None or (c.vis is not None and c.length_table is not None),
         'nb > 64': bool((cnt[1:] > TARGET_STEP).any()),
     }
     if c.length_table is not None:

@@ -379,8 +379,8 @@ def test_inference_hungarian_mode_end_to_end(weights):
 
 
 def test_inference_hungarian_mode_with_the_appearance_term(weights):
-    """ASSOCIATION='hungarian' with MCF_VIS_SIM_WEIGHT > 0 (axt_hungarian_pairs_costs): the link costs are the flow
-    tracker's arc costs with the appearance term (axt_build_arcs_vis), handed to the pair kernels as a table. Same
+    """ASSOCIATION='hungarian' with MCF_VIS_SIM_WEIGHT > 0 (d_ctab of axt_hungarian_pairs): the link costs are the flow
+    tracker's arc costs with the appearance term (axt_build_arcs with d_hist), handed to the pair kernels as a table. Same
     trajectories and IDed_dets_all as the oracle (SciPy LSAP on transition_cost(..., vis_w, vis_sim)), on the all-ones mask
     and on a masked grid; and a different association from the one without the term."""
     import axtrack_amd
@@ -400,7 +400,7 @@ def test_inference_hungarian_mode_with_the_appearance_term(weights):
 
 
 def test_inference_hungarian_mode_on_a_masked_grid(weights):
-    """The frame-to-frame variant with path lengths from the masked-grid searches (axt_hungarian_pairs_grid): the
+    """The frame-to-frame variant with path lengths from the masked-grid searches (axt_hungarian_pairs with a grid): the
     oracle's trajectories, which differ from those on the all-ones mask."""
     import axtrack_amd
     frames = synth.synth_frames(9, 512, 512, seed=27)
@@ -761,7 +761,7 @@ def test_two_rank_sharding_with_a_tile_that_is_empty_on_one_rank(weights):
 # ----------------------------------------------------------------------------------------- f-2 (next row)
 def test_path_cache_round_trip_in_the_references_format(weights, tmp_path):
     """'{name}_astar_dets_paths.pkl': written ('to') in the reference's format -- nested lists of scipy coo matrices /
-    None per frame pair -- read back ('from') through axt_build_arcs_from_lengths, and consumed by the oracle's
+    None per frame pair -- read back ('from') through d_len_table of axt_build_arcs, and consumed by the oracle's
     restatement of _get_astar_path_distances: the same path lengths, arcs and trajectories every way."""
     import pickle
     from scipy import sparse

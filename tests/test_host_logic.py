@@ -27,7 +27,42 @@ def test_library_exports_every_declared_symbol():
     for n in sorted(names):
         assert hasattr(lib, n), f'libaxtrack_hip.so does not export {n}'
         assert n in _lib.SIGNATURES, f'{n} has no ctypes signature in axtrack_amd/_lib.py'
+    for n in sorted(_lib.SIGNATURES):
+        assert n in names, f'axtrack_amd/_lib.py has a signature for {n}, which no header declares'
     assert lib.axt_abi_version() == 1
+
+
+def test_association_entry_points_check_arguments_without_a_gpu():
+    """axt_build_arcs and axt_hungarian_pairs refuse bad arguments before they touch the device (invalid calls only:
+    a valid one would reach a launch)."""
+    lib = _lib.load()
+    EINVAL = -22
+    buf = np.zeros(64, np.int64)
+    p = buf.ctypes.data                                               # (never dereferenced: the checks come first)
+    n = ctypes.c_int64(0)
+
+    def arcs(d_x=p, max_gap=2, hist=None, hsum=None, weight=0.0, col=None, length=None, gap=None, units=None, cost=None):
+        return lib.axt_build_arcs(d_x, p, p, None, 4, 8, None, 64, 64, 500, 0, max_gap, p, hist, hsum, weight, 0.5, 4.6, p, p,
+                                  col, length, gap, units, cost, ctypes.byref(n), None, None)
+
+    assert arcs(d_x=None) == EINVAL
+    assert b'null argument' in lib.axt_last_error()
+    assert arcs(max_gap=9) == EINVAL
+    assert arcs(hist=p, hsum=None, weight=0.5) == EINVAL                                  # histograms without their sums
+    assert arcs(hist=p, hsum=p, weight=0.0) == EINVAL
+    assert arcs(hist=p, hsum=p, weight=1.5) == EINVAL
+    assert b'1.5' in lib.axt_last_error()
+    assert arcs(col=p, length=p, gap=p, cost=p, units=None) == EINVAL                     # phase 2: costs wanted, no units
+    assert b'go together' in lib.axt_last_error()
+
+    def pairs(cap=8, max_gap=2, a=0, b=4, units=p, ctab=None):
+        return lib.axt_hungarian_pairs(p, p, p, 4, cap, None, 64, 64, 500, 0, max_gap, p, units, 4600000, a, b, p, p, None, ctab)
+
+    assert pairs(cap=2049) == EINVAL
+    assert b'2049' in lib.axt_last_error()
+    assert pairs(max_gap=3) == EINVAL
+    assert pairs(a=3, b=2) == EINVAL
+    assert pairs(units=None, ctab=None) == EINVAL                                         # neither a cost table nor units
 
 
 def test_product_has_no_oracle_import():

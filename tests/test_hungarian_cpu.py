@@ -36,7 +36,7 @@ def test_vector_costs_equal_the_oracles():
 
 
 def test_dispatch_bounds():
-    """The thresholds of hungarian_pairs_impl, derived from its lds_base expression (restated in hr.dispatch)."""
+    """The thresholds of axt_hungarian_pairs, derived from its lds_base expression (restated in hr.dispatch)."""
     assert [hr.dispatch(c) for c in (64, 192, 193, 576, 577)] == [(3, 64), (3, 96), (9, 96), (9, 96), (0, 96)]
     c0 = hr.first_cap_without_cache()
     assert hr.dispatch(c0 - 1) == (0, 96) and hr.dispatch(c0) == (0, 0) and hr.dispatch(2048) == (0, 0)

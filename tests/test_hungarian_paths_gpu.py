@@ -64,14 +64,14 @@ def test_open_grid(case):
 
 @pytest.mark.parametrize('case', hr.battery_b(), ids=repr)
 def test_given_cost_table(case):
-    """Battery B: link costs handed over as a table (axt_hungarian_pairs_costs): dense random, Machol-Wien, equal units,
+    """Battery B: link costs handed over as a table (d_ctab of axt_hungarian_pairs): dense random, Machol-Wien, equal units,
     nothing admitted, one row per column -- and admitted links dearer than leaving the row unlinked."""
     _judge(case, *_run(case))
 
 
 @pytest.mark.parametrize('case', hr.battery_c(), ids=repr)
 def test_masked_grid(case):
-    """Battery C: path lengths from the masked-grid searches (axt_hungarian_pairs_grid), crowded."""
+    """Battery C: path lengths from the masked-grid searches (axt_hungarian_pairs with a grid), crowded."""
     _judge(case, *_run(case))
 
 
@@ -84,9 +84,10 @@ def _pairs_call(case, a, b, pred, work, cap=None):
         x, y = torch.cat([x, pad], 1).contiguous(), torch.cat([y, pad], 1).contiguous()
     h_dmax = np.ascontiguousarray(dmax, np.int32)
     d_units = dev(units)
-    rc = _lib.load().axt_hungarian_pairs(x.data_ptr(), y.data_ptr(), cnt.data_ptr(), len(case.counts), cap or case.cap, case.H,
-                                         case.W, hp.MAX_PX_ASSOC_DIST, int(case.conn8), 2, h_dmax.ctypes.data,
-                                         d_units.data_ptr(), case.thr_units, a, b, pred.data_ptr(), work.data_ptr(), hp._stream())
+    rc = _lib.load().axt_hungarian_pairs(x.data_ptr(), y.data_ptr(), cnt.data_ptr(), len(case.counts), cap or case.cap, None,
+                                         case.H, case.W, hp.MAX_PX_ASSOC_DIST, int(case.conn8), 2, h_dmax.ctypes.data,
+                                         d_units.data_ptr(), case.thr_units, a, b, pred.data_ptr(), work.data_ptr(), hp._stream(),
+                                         None)
     torch.cuda.synchronize()
     return rc
 

@@ -130,7 +130,7 @@ def _link_costs(case):
 
 @pytest.mark.parametrize('case', [c for c in pr.battery() if c.group in 'ADF'], ids=repr)
 def test_hungarian_on_the_same_table(case, monkeypatch):
-    """hp.hungarian_assoc fills the same path-length table (axt_hungarian_pairs_grid): judged by hungarian_reference.judge
+    """hp.hungarian_assoc fills the same path-length table (axt_hungarian_pairs with a grid): judged by hungarian_reference.judge
     on costs taken from the reference lengths."""
     from axtrack_amd.detections import transition_cost_table
     _environment(case, monkeypatch)
