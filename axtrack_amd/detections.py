@@ -79,7 +79,8 @@ class AxonDetections(object):
         self.d_conf = self.d_x = self.d_y = self.d_count = None
         self._drop_detections()
         # state that follows neither the detections nor the association: the labels, the target and its fields
-        self._gt = self._gt_ids = self._gt_dev = None
+        self._gt = self._gt_ids = self._gt_dev = self._gt_gid_dev = None
+        self._gt_no = 0
         self._target_cells, self.reach_px, self.structure_outputchannel_coo, self._target_fields = None, None, None, {}
         if getattr(dataset, 'labelled', False):            # a labelled dataset brings its ground truth (AxonDetections.py:57)
             self.set_groundtruth([dataset.labels[t] for t in self.timepoint_subset])
@@ -399,6 +400,12 @@ class AxonDetections(object):
         dev = self.device
         self._gt_dev = (torch.from_numpy(gx).to(dev), torch.from_numpy(gy).to(dev),
                         torch.tensor([len(x) for x, _ in self._gt], dtype=torch.int32, device=dev))
+        # the dense label identities (rank among all identities of the labels) for the tracking scores on the device
+        every = np.unique(np.concatenate(self._gt_ids + [np.zeros(0, np.int64)]))
+        gid = np.zeros((len(self), gcap), np.int32)
+        for t, ids in enumerate(self._gt_ids):
+            gid[t, :len(ids)] = np.searchsorted(every, ids)
+        self._gt_gid_dev, self._gt_no = torch.from_numpy(gid).to(dev), len(every)
         self.labelled = True
 
     def detection_confusion(self):
@@ -634,17 +641,26 @@ class AxonDetections(object):
 
     def search_MCF_params(self, edge_cost_thr_values=(.4, .6, .7, .8, .9, 1, 1.2, 3),
                           entry_exit_cost_values=(.2, .8, .9, 1, 1.1, 2), miss_rate_values=(0.9, 0.6),
-                          vis_sim_weight_values=(0, 0.1), conf_capping_method_values=('ceil', 'scale_to_max')):
+                          vis_sim_weight_values=(0, 0.1), conf_capping_method_values=('ceil', 'scale_to_max'),
+                          scoring='host', score_batch=64):
         """AxonDetections.py:845-922: re-solve the association for every combination of the five tracker parameters
         (same nesting order) and score each against the labelled identities; one row per combination -- the five
         parameters, then mot_metrics.MOTCHALLENGE_METRICS -- written to '{dir}/MCF_params_results.csv' and returned.
         Every solve is the GPU arc build + flow solve of assign_ids (the detections and their appearance
         histograms stay on the device between combinations); the parameters are restored afterwards. On a masked
         grid the path lengths are computed once, exactly and up to max_px_assoc_dist (astar_dists), and reused by every
-        combination -- as the reference reuses its path cache."""
+        combination -- as the reference reuses its path cache.
+        scoring: 'host' scores every combination with mot_metrics on the libmot tables; 'gpu' keeps every combination's
+        track table on the device and scores score_batch of them per call of score_associations --
+        same rows, columns and CSV."""
         from . import mot_metrics
         if not self.labelled:
             raise ValueError("no labels: call set_groundtruth() first")
+        if scoring not in ('host', 'gpu'):
+            raise ValueError(f"scoring={scoring!r}: 'host' or 'gpu'")
+        if scoring == 'gpu':
+            return self._search_MCF_params_gpu(edge_cost_thr_values, entry_exit_cost_values, miss_rate_values,
+                                               vis_sim_weight_values, conf_capping_method_values, int(score_batch))
         target = self.get_frame_dets('groundtruth', None, libmot=True)
         names = ('edge_cost_thr', 'entry_exit_cost', 'miss_rate', 'vis_sim_weight', 'conf_capping_method')
         keys = ('MCF_EDGE_COST_THR', 'MCF_ENTRY_EXIT_COST', 'MCF_MISS_RATE', 'MCF_VIS_SIM_WEIGHT', 'MCF_CONF_CAPPING_METHOD')
@@ -671,6 +687,105 @@ class AxonDetections(object):
         os.makedirs(self.dir, exist_ok=True)
         results.to_csv(f'{self.dir}/MCF_params_results.csv')
         return results
+
+    def _search_MCF_params_gpu(self, ecs, eecs, mrs, vsws, ccms, score_batch):
+        """search_MCF_params with the scores taken on the device: the same loop, but every combination leaves a clone of
+        its track table (all -1 where nothing was solved: the host path's pred = None) and the tables are scored
+        score_batch at a time."""
+        if score_batch < 1:
+            raise ValueError(f'score_batch={score_batch} must be positive')
+        self._require_scorable()
+        names = ('edge_cost_thr', 'entry_exit_cost', 'miss_rate', 'vis_sim_weight', 'conf_capping_method')
+        keys = ('MCF_EDGE_COST_THR', 'MCF_ENTRY_EXIT_COST', 'MCF_MISS_RATE', 'MCF_VIS_SIM_WEIGHT', 'MCF_CONF_CAPPING_METHOD')
+        before = {k: self.P[k] for k in keys}
+        results, combos, tracks = [], [], []
+        lengths = self._length_table_from_dists(self.astar_dists()) if self.dataset.masked else None
+
+        def flush():
+            for combo, scores in zip(combos, self._score_series(torch.stack(tracks))):
+                results.append(pd.concat([pd.Series(combo, names, dtype=object), scores]))
+            combos.clear(); tracks.clear()
+        try:
+            for ec in ecs:
+                for eec in eecs:
+                    for mr in mrs:
+                        for vsw in vsws:
+                            for ccm in ccms:
+                                self.P.update(dict(zip(keys, (ec, eec, mr, vsw, ccm))))
+                                self.assign_ids(_len_table=lengths)
+                                combos.append((ec, eec, mr, vsw, ccm))
+                                tracks.append(self._track_dev().clone() if self._solved
+                                              else torch.full_like(self.d_x, -1, dtype=torch.int32))
+                                if len(tracks) == score_batch:
+                                    flush()
+            if tracks:
+                flush()
+        finally:
+            self.P.update(before)
+        results = pd.concat(results, axis=1).T
+        os.makedirs(self.dir, exist_ok=True)
+        results.to_csv(f'{self.dir}/MCF_params_results.csv')
+        return results
+
+    # ------------------------------------------------------------------ tracking scores on the device (DESIGN.md 6.8g)
+    def _require_scorable(self):
+        if not self.labelled:
+            raise ValueError("no labels: call set_groundtruth() first")
+        if self._shard is not None:
+            raise NotImplementedError('tracking scores of a frame-sharded run are not implemented: score in a single '
+                                      'process after gather_detections()')
+        cap, gcap = int(self.d_x.shape[1]), int(self._gt_dev[0].shape[1])
+        if cap > hp.MOT_MAX_SIDE or gcap > hp.MOT_MAX_SIDE:
+            raise ValueError(f'{gcap} labels / {cap} detection slots in a frame: the device scorer takes at most '
+                             f'{hp.MOT_MAX_SIDE} per frame')
+        d = self.nms_min_dist
+        if d is None or int(d) != d or not 0 <= d <= hp.MOT_MAX_DIST:
+            raise ValueError(f'NON_MAX_SUPRESSION_DIST={d!r}: the device scorer takes an integer in [0, {hp.MOT_MAX_DIST}]')
+
+    def _score_series(self, tracks, events=False):
+        """The scores of the associations tracks (i32 [K,F,cap] on the device) as a list of K pd.Series; with events
+        (K == 1 at a time is enough for that) also the event log as numpy arrays."""
+        from . import mot_metrics
+        self._require_scorable()
+        F, cap = self.d_x.shape
+        if tracks.dim() != 3 or tuple(tracks.shape[1:]) != (F, cap):
+            raise ValueError(f'tracks of shape {tuple(tracks.shape)}: expected [K, {F}, {cap}]')
+        tracks = tracks.to(device=self.device, dtype=torch.int32).contiguous()
+        K = int(tracks.shape[0])
+        gx, gy, gc = self._gt_dev
+        no, nh = max(self._gt_no, 1), max(int(tracks.max().item()) + 1, 1) if K else 1
+        one = hp.mot_scores_scratch_bytes(1, F, cap, gx.shape[1], no, nh, int(self.nms_min_dist))
+        if one > 1 << 30:
+            raise ValueError(f'scoring one association of {no} label identities x {nh} track identities would take '
+                             f'{one / 2 ** 30:.1f} GiB of scratch (limit 1 GiB)')
+        chunk = max(1, (1 << 30) // max(one, 1))
+        out, log = [], None
+        for a in range(0, K, chunk):
+            res = hp.mot_scores(tracks[a:a + chunk], self.d_x, self.d_y, self.d_count, self._gt_gid_dev, gx, gy, gc, no, nh,
+                                int(self.nms_min_dist), events=events)
+            counts, tallies = res[0].cpu().numpy(), res[1].cpu().numpy()
+            out += [mot_metrics.scores_from_counts(c, t) for c, t in zip(counts, tallies)]
+            if events:
+                log = dict(zip(('kind', 'partner', 'fp'), (v.cpu().numpy() for v in res[2:])))
+        return (out, log) if events else out
+
+    def get_tracking_metrics(self, events=False):
+        """The fifteen MOTChallenge scores (pd.Series, mot_metrics.MOTCHALLENGE_METRICS) of the current association
+        against the labels, counted on the device (axt_mot_scores). events=True: also the event log as numpy arrays --
+        'kind' u8 [F,gcap] per label slot (0 none, 1 MATCH, 2 SWITCH, 3 MISS), 'partner' i32 [F,gcap] (detection slot,
+        -1 none), 'fp' u8 [F,cap] per detection slot."""
+        if not self.labelled:
+            raise ValueError("no labels: call set_groundtruth() first")
+        assert self._solved, "Run .assign_IDs() first!"
+        res = self._score_series(self._track_dev()[None], events=events)
+        if events:
+            return res[0][0], {k: v[0] for k, v in res[1].items()}
+        return res[0]
+
+    def score_associations(self, tracks):
+        """Scores of K associations of the current detections, i32 tensor [K,F,cap] of track identities (-1 = none):
+        DataFrame of K rows, columns mot_metrics.MOTCHALLENGE_METRICS. K is chunked so that the scratch stays under 1 GiB."""
+        return pd.DataFrame(self._score_series(tracks))
 
     def _appearance(self):
         """feature_model's histograms of every detection (device tensors hist f32 [F,cap,180], sums f64 [F,cap]),

@@ -704,6 +704,45 @@ def detection_confusion(conf, x, y, count, gx, gy, gcount, thrs, min_dist=23, k_
     return (out, fp, fn) if k_mask >= 0 else out
 
 
+MOT_MAX_SIDE, MOT_MAX_DIST = 1024, 255       # axt_mot_scores: labels / detections per frame, max_dist
+
+
+def mot_scores_scratch_bytes(n_assoc, n_frames, cap, gcap, no, nh, max_dist=23):
+    """Bytes of scratch axt_mot_scores needs for n_assoc associations (the size query; no GPU work)."""
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().axt_mot_scores(None, int(n_assoc), None, None, None, int(n_frames), int(cap), None, None, None,
+                                          None, int(gcap), int(no), int(nh), int(max_dist), None, None, None, None, None,
+                                          None, ctypes.byref(need), None), 'axt_mot_scores (scratch size)')
+    return int(need.value)
+
+
+def mot_scores(tracks, x, y, count, gid, gx, gy, gcount, no, nh, max_dist=23, events=False):
+    """The counts behind mot_metrics.summarize(mot_metrics.accumulate(...)) for K associations of the same detections
+    (axt_mot_scores). tracks i32 [K,F,cap] (-1 = no identity, identities < nh); labels gid (dense, < no),
+    gx, gy i32 [F,gcap], gcount i32 [F]. -> (counts i64 [K,10], tallies i32 [K,no,2]) on the device; with events also
+    (kind u8 [K,F,gcap], partner slot i32 [K,F,gcap], fp u8 [K,F,cap])."""
+    K, n_frames, cap = tracks.shape
+    gcap = gx.shape[1]
+    dev = x.device
+    assert tracks.dtype == torch.int32 and tracks.is_contiguous() and tuple(x.shape) == (n_frames, cap)
+    need = ctypes.c_size_t(mot_scores_scratch_bytes(K, n_frames, cap, gcap, no, nh, max_dist))
+    scratch = torch.empty(max(need.value, 8), dtype=torch.uint8, device=dev)
+    counts = torch.empty((K, 10), dtype=torch.int64, device=dev)
+    tallies = torch.empty((K, int(no), 2), dtype=torch.int32, device=dev)
+    kind = part = fp = None
+    if events:
+        kind = torch.empty((K, n_frames, gcap), dtype=torch.uint8, device=dev)
+        part = torch.empty((K, n_frames, gcap), dtype=torch.int32, device=dev)
+        fp = torch.empty((K, n_frames, cap), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().axt_mot_scores(tracks.data_ptr(), K, x.data_ptr(), y.data_ptr(), count.data_ptr(), n_frames,
+                                              cap, gid.data_ptr(), gx.data_ptr(), gy.data_ptr(), gcount.data_ptr(), gcap,
+                                              int(no), int(nh), int(max_dist), counts.data_ptr(), tallies.data_ptr(),
+                                              _lib.dptr(kind), _lib.dptr(part), _lib.dptr(fp), scratch.data_ptr(),
+                                              ctypes.byref(need), _stream()), 'axt_mot_scores')
+    return (counts, tallies, kind, part, fp) if events else (counts, tallies)
+
+
 _HOST_STAGING = {}
 
 

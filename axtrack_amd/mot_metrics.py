@@ -135,6 +135,47 @@ def summarize(ev):
     return pd.Series([vals[k] for k in MOTCHALLENGE_METRICS], index=MOTCHALLENGE_METRICS)
 
 
+def pair_cost_int(d2, label, track):
+    """Host twin of the device scorer's pair cost (csrc/mot.hip): (d2 << 26) | hash16(kind 4, dense label identity,
+    track identity), the splitmix hash of axt_arc_cost_int. int64 arrays (broadcast)."""
+    with np.errstate(over='ignore'):
+        x = (np.uint64(4) << np.uint64(60)) ^ (np.asarray(label, np.uint64) << np.uint64(30)) ^ np.asarray(track, np.uint64)
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x = x ^ (x >> np.uint64(31))
+    return (np.asarray(d2, np.int64) << 26) | (x & np.uint64(0xFFFF)).astype(np.int64)
+
+
+# the ten counts of axt_mot_scores, in its order
+MOT_COUNTS = ['n_match', 'n_switch', 'n_miss', 'n_fp', 'sum_d2', 'n_obj', 'n_pred', 'n_unique_objects',
+              'n_fragmentations', 'idtp']
+
+
+def scores_from_counts(counts, tallies):
+    """The fifteen MOTChallenge scores (pd.Series, index MOTCHALLENGE_METRICS) from the device scorer's output for one
+    association: counts int [10] (MOT_COUNTS), tallies int [no, 2] (frames present, frames not missed) per label
+    identity. The f64 formulae and NaN conventions of summarize."""
+    c = dict(zip(MOT_COUNTS, (int(v) for v in np.asarray(counts).reshape(-1))))
+    tallies = np.asarray(tallies, np.int64).reshape(-1, 2)
+    seen = tallies[:, 0] > 0
+    ratio = tallies[seen, 1].astype(np.float64) / np.maximum(tallies[seen, 0], 1)
+    n_det, n_obj, n_pred = c['n_match'] + c['n_switch'], c['n_obj'], c['n_pred']
+    idtp = float(c['idtp'])
+    idfp, idfn = float(n_pred) - idtp, float(n_obj) - idtp
+
+    def div(a, b):
+        return a / b if b else np.nan
+    vals = dict(idf1=div(2 * idtp, n_obj + n_pred), idp=div(idtp, idtp + idfp), idr=div(idtp, idtp + idfn),
+                recall=div(n_det, n_obj), precision=div(n_det, c['n_fp'] + n_det), num_unique_objects=c['n_unique_objects'],
+                mostly_tracked=int((ratio >= 0.8).sum()), partially_tracked=int(((ratio >= 0.2) & (ratio < 0.8)).sum()),
+                mostly_lost=int((ratio < 0.2).sum()), num_false_positives=c['n_fp'], num_misses=c['n_miss'],
+                num_switches=c['n_switch'], num_fragmentations=c['n_fragmentations'],
+                mota=1.0 - div(c['n_miss'] + c['n_switch'] + c['n_fp'], n_obj) if n_obj else np.nan,
+                motp=div(float(c['sum_d2']), n_det))
+    return pd.Series([vals[k] for k in MOTCHALLENGE_METRICS], index=MOTCHALLENGE_METRICS)
+
+
 def compare_to_groundtruth(target, pred, max_d2):
     """The two libmot tables (index (FrameId, Id), columns X, Y, ... as AxonDetections.det2libmot_det makes them) ->
     event log over the union of their frames."""

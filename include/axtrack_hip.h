@@ -519,6 +519,27 @@ int axt_detection_confusion(const float *d_conf, const int32_t *d_x, const int32
                             int32_t *d_confusion, uint8_t *d_fp_mask, uint8_t *d_fn_mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking scores (the definition stands in csrc/mot.hip): the counts behind the MOTChallenge
+ * metrics of axtrack_amd/mot_metrics.py for n_assoc associations of the same detections at once.
+ * d_track i32 [n_assoc, n_frames, cap] (-1 = no identity; identities in [0, nh)); d_x, d_y, d_count the shared
+ * detections; labels d_gid (dense identities in [0, no)), d_gx, d_gy i32 [n_frames, gcap], d_gcount i32 [n_frames].
+ * Identities are unique within a frame on both sides; identities out of range take no part. A pair is admissible
+ * when dx^2 + dy^2 <= max_dist^2. Limits: cap, gcap <= 1024, max_dist <= 255, no, nh <= 2^24 (AXT_EINVAL beyond).
+ * Outputs: d_counts i64 [n_assoc, 10] = n_match, n_switch, n_miss, n_fp, sum of matched d2, n_obj, n_pred,
+ * n_unique_objects, n_fragmentations, idtp; d_tallies i32 [n_assoc, no, 2] = frames present, frames not missed.
+ * Event log (each pointer may be NULL): d_ev_kind u8 [n_assoc, n_frames, gcap] per label slot (0 none, 1 MATCH,
+ * 2 SWITCH, 3 MISS), d_ev_partner i32, same shape (the partner's detection slot, -1 = none), d_ev_fp u8
+ * [n_assoc, n_frames, cap] per detection slot. *scratch_bytes: in, the size of d_scratch; out, the size needed;
+ * with d_scratch == NULL the call only answers that size (the other pointers may be NULL then). Integer work,
+ * two calls give identical bits. Asynchronous.
+ * ------------------------------------------------------------------------------------------ */
+int axt_mot_scores(const int32_t *d_track, int n_assoc, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
+                   int n_frames, int cap, const int32_t *d_gid, const int32_t *d_gx, const int32_t *d_gy,
+                   const int32_t *d_gcount, int gcap, int no, int nh, int max_dist, int64_t *d_counts,
+                   int32_t *d_tallies, uint8_t *d_ev_kind, int32_t *d_ev_partner, uint8_t *d_ev_fp, void *d_scratch,
+                   size_t *scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rendering (video_plotting.py draw_all / setup_frame_drawing / draw_frame / draw_detections, which redraw every
  * frame as matplotlib patches): annotated uint8 RGB frames, DESIGN.md 6.8b.
  * axt_render_tile_size: edge of the square output tiles the primitive lists are binned by (64).
