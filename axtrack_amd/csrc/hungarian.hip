@@ -43,32 +43,51 @@ __device__ __forceinline__ int h_path_len_open(int xa, int ya, int xb, int yb, i
 }
 
 // wave-wide argmin of (key, idx): smallest key, ties to the smallest idx. Key (< 2^52) and index (< 2^11) travel as
-// one 64-bit word; inside each row of 16 lanes the minimum is formed with DPP moves (quad swaps, half-row and row
-// mirrors: 2-cycle VALU operations instead of ~100-cycle LDS-crossbar shuffles), the four row minima meet through
-// v_readlane.
-__device__ __forceinline__ unsigned long dpp_min_step(unsigned long v, unsigned long o) { return o < v ? o : v; }
-#define AXT_DPP_MIN(v, ctrl)                                                                              \
-    {                                                                                                     \
-        const unsigned lo_ = (unsigned)(v), hi_ = (unsigned)((v) >> 32);                                  \
-        const unsigned ol_ = __builtin_amdgcn_update_dpp(lo_, lo_, ctrl, 0xF, 0xF, false);                \
-        const unsigned oh_ = __builtin_amdgcn_update_dpp(hi_, hi_, ctrl, 0xF, 0xF, false);                \
-        (v) = dpp_min_step(v, ((unsigned long)oh_ << 32) | ol_);                                          \
-    }
+// one 64-bit word, whose minimum is formed in two 32-bit phases (below) with DPP operands (2-cycle VALU operations instead
+// of ~100-cycle LDS-crossbar shuffles).
+// wave-wide minimum of a 32-bit word, in lane 63's hands and returned wave-uniform: inside each row of 16 lanes by quad
+// swaps, half-row and row mirrors, then row_bcast:15 (rows 1 and 3 take in lane 15 of the row before) and row_bcast:31
+// (rows 2 and 3 take in lane 31; a row the mask leaves out keeps its value). The DPP modifier sits on v_min_u32 itself -- from __builtin_amdgcn_update_dpp hipcc makes
+// a copy, a v_mov_b32_dpp and the minimum, four instructions a round with the wait -- so the rounds are written out; each
+// reads the register the one before wrote, which a DPP operand may do after two wait states (s_nop 1), and the first may
+// follow a write to EXEC only after five (s_nop 4).
+__device__ __forceinline__ unsigned wave_min_u32(unsigned x)
+{
+    asm volatile("s_nop 4\n\t"
+                 "v_min_u32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_u32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_u32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_u32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"       // the row's minimum in all its lanes
+                 "s_nop 1\n\t"
+                 "v_min_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+                 "s_nop 1"
+                 : "+v"(x));
+    return __builtin_amdgcn_readlane(x, 63);
+}
+// The 64-bit minimum in two 32-bit phases: the smallest high word, then the smallest low word among the lanes that hold it.
+// (A lane left out of the second phase offers 0xffffffff, which no lane that takes part can undercut wrongly: the result is
+// the minimum of the low words that take part whatever they are; all lanes hold ~0 exactly when both phases return ~0.)
 __device__ __forceinline__ void wave_argmin(long &key, int &idx)
 {
-    unsigned long v = key >= (1l << 51) ? ~0ul : (((unsigned long)key << 11) | (unsigned)idx);   // keys are >= 0
-    AXT_DPP_MIN(v, 0xB1);        // quad_perm [1,0,3,2]
-    AXT_DPP_MIN(v, 0x4E);        // quad_perm [2,3,0,1]
-    AXT_DPP_MIN(v, 0x141);       // row_half_mirror
-    AXT_DPP_MIN(v, 0x140);       // row_mirror: every lane of a row now holds the row's minimum
-    unsigned long best = ~0ul;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, r * 16), hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), r * 16);
-        best = dpp_min_step(best, ((unsigned long)hi << 32) | lo);
-    }
+    const unsigned long v = key >= (1l << 51) ? ~0ul : (((unsigned long)key << 11) | (unsigned)idx);   // keys are >= 0
+    const unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
+    const unsigned mh = wave_min_u32(hi);
+    const unsigned ml = wave_min_u32(hi == mh ? lo : ~0u);
+    const unsigned long best = ((unsigned long)mh << 32) | ml;
     if (best == ~0ul) { key = HINF; idx = 0x7fffffff; }
     else { key = (long)(best >> 11); idx = (int)(best & 2047u); }
+}
+
+// a wave-uniform 64-bit value out of vector registers (an LDS read at a uniform address) into scalar ones
+__device__ __forceinline__ long wave_uniform(long a)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long)a >> 32));
+    return (long)(((unsigned long)hi << 32) | lo);
 }
 
 // One wave per frame pair (t, t+gap). succ/pred are per detection slot [n_frames*cap]:
@@ -83,9 +102,26 @@ __device__ __forceinline__ void wave_argmin(long &key, int &idx)
 // and wave 0 runs the searches alone.
 // Diagnostic build only (-DAXT_HUNG_STATS, profiles/hungarian_stats.py): per frame pair of the last gap-1 launch the
 // s_memtime ticks of the initialisation and of the searches, the number of searches and of search steps, n and m.
+// Of the register-resident searches (NC > 0) also the ticks of a search step by segment, summed over the pair's steps: [8] the
+// LDS round trip (cost row, u[cur], dummy[cur]), [9] the per-slot update, [10] wave_argmin, [11] the matched-row lookup. A
+// stamp waits for what its segment computed (the value handed to HUNG_SEG_END) and for every LDS read in flight, so the
+// stamped step is slower than the product's: the segments' shares are the finding, not their sum. Stamps exist in this build
+// only and write to g_hung_stats only.
 #ifdef AXT_HUNG_STATS
-__device__ unsigned long long g_hung_stats[4096 * 8];
+constexpr int HUNG_STAT_COLS = 16;
+__device__ unsigned long long g_hung_stats[4096 * HUNG_STAT_COLS];
 #define HUNG_STAMP() __builtin_amdgcn_s_memtime()
+#define HUNG_SEG_BEGIN() seg_t = HUNG_STAMP()
+#define HUNG_SEG_END(i, dep)                                          \
+    {                                                                 \
+        asm volatile("" ::"v"(dep));                                  \
+        const unsigned long long now_ = HUNG_STAMP();                 \
+        seg_sum[i] += now_ - seg_t;                                   \
+        seg_t = now_;                                                 \
+    }
+#else
+#define HUNG_SEG_BEGIN()
+#define HUNG_SEG_END(i, dep)
 #endif
 
 template <int GAP, int NC>
@@ -121,7 +157,7 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
 
 #ifdef AXT_HUNG_STATS
     const unsigned long long st0 = HUNG_STAMP();
-    unsigned long long st1 = 0, n_search = 0, n_step = 0;
+    unsigned long long st1 = 0, n_search = 0, n_step = 0, seg_t = 0, seg_sum[4] = {0, 0, 0, 0};
 #endif
     const long a0 = frame_off[t], b0 = frame_off[tb];
     for (int j = lane; j < m; j += nthr) {
@@ -248,7 +284,7 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
 #pragma unroll
             for (int k = 0; k < NS; ++k) { spc_r[k] = HINF; sc_r[k] = false; pred_r[k] = -1; }
             long minVal = 0, best_dummy = HINF;
-            int cur = i, dummy_row = -1, n_sr = 0, sink = -1;             // sink >= 0: real column; -2: dummy of dummy_row
+            int cur = i, dummy_row = -1, sink = -1;                       // sink >= 0: real column; -2: dummy of dummy_row
 #ifdef AXT_HUNG_STATS
             ++n_search;
 #endif
@@ -256,13 +292,7 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
 #ifdef AXT_HUNG_STATS
                 ++n_step;
 #endif
-                if (lane == 0) sr[n_sr] = cur;
-                ++n_sr;
-                const long ucur = u[cur];
-                const long rd = minVal + dummy[cur] - ucur;
-                if (rd < best_dummy) { best_dummy = rd; dummy_row = cur; }
-                long bkey = HINF;
-                int bidx = 0x7fffffff;
+                HUNG_SEG_BEGIN();
                 // branch-free over the lane's columns: the cost reads go out together, everything else is selects
                 long cst[NS];
 #pragma unroll
@@ -270,24 +300,38 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
                     const int j = lane + 64 * k;
                     if constexpr (CACHED) {
                         const long c = ccache[cur * cdim + min(j, cdim - 1)];     // columns >= m: not ok, whatever is read
-                        cst[k] = ok_r[k] ? c : HINF;
+                        cst[k] = c;                                               // (ok_r decides below)
                     } else {
                         cst[k] = !ok_r[k] ? HINF : link_cost(cur, j);
                     }
                 }
+                // the row's dual and dummy cost are wave-uniform: in scalar registers, what is formed from them costs no
+                // vector instruction
+                const long u_lds = u[cur], dummy_lds = dummy[cur];               // (both reads go out with the cost row's)
+                const long base = minVal - wave_uniform(u_lds);
+                const long rd = base + wave_uniform(dummy_lds);
+                HUNG_SEG_END(0, cst[0] + rd);
+                if (rd < best_dummy) { best_dummy = rd; dummy_row = cur; }
+                long bkey = HINF;
+                int bidx = 0x7fffffff;
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
-                    const bool open = ok_r[k] && !sc_r[k];
-                    const long r = minVal + cst[k] - ucur - v_r[k];
-                    const bool upd = open && cst[k] != HINF && r < spc_r[k];
+                    // reduced cost cst - u[cur] - v + minVal with the uniform part formed once; a link that is not admitted
+                    // shows in its high word alone (costs are below 2^51). A column that takes no part is never updated, so
+                    // its spc stays HINF and it needs no test of its own among the candidates.
+                    const long r = cst[k] + (base - v_r[k]);
+                    const bool upd = ok_r[k] && !sc_r[k] && (int)(cst[k] >> 32) < (int)(HINF >> 32) && r < spc_r[k];
                     spc_r[k] = upd ? r : spc_r[k];
                     pred_r[k] = upd ? cur : pred_r[k];
-                    const long cand = open ? spc_r[k] : HINF;
-                    const bool better = cand < bkey;
+                    const long cand = sc_r[k] ? HINF : spc_r[k];
+                    // (the first slot needs no comparison: a key of HINF is no candidate, whatever its column)
+                    const bool better = k == 0 || cand < bkey;
                     bkey = better ? cand : bkey;
                     bidx = better ? lane + 64 * k : bidx;
                 }
+                HUNG_SEG_END(1, bkey + bidx);
                 wave_argmin(bkey, bidx);
+                HUNG_SEG_END(2, bkey + bidx);
                 if (best_dummy <= bkey) { sink = -2; minVal = best_dummy; break; }
                 minVal = bkey;
                 // the winning column (wave-uniform index) joins the tree; its owner tells everyone the matched row
@@ -298,22 +342,23 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
                         if (lane == (bidx & 63)) sc_r[k] = true;
                         matched = __builtin_amdgcn_readlane(rc_r[k], bidx & 63);
                     }
+                HUNG_SEG_END(3, matched);
                 if (matched < 0) { sink = bidx; break; }
                 cur = matched;
             }
-            // publish what the row update and the augmentation read: distances and predecessors of the tree's columns
+            // dual update (Crouse 2016, Alg. 1). The rows of the tree are row i and the matched rows of the tree's columns, and
+            // a column's owner holds all that the update of its matched row needs: no list of the rows scanned, no distances in
+            // LDS. The augmentation reads the predecessors of the tree's columns.
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 const int j = lane + 64 * k;
-                if (j < m && sc_r[k]) { spc[j] = spc_r[k]; pred[j] = pred_r[k]; }
-                if (j < m && sc_r[k] && j != sink) v_r[k] -= minVal - spc_r[k];      // dual update of the columns
+                if (j < m && sc_r[k]) {
+                    pred[j] = pred_r[k];
+                    if (rc_r[k] >= 0) u[rc_r[k]] += minVal - spc_r[k];                   // (the sink has no matched row)
+                    if (j != sink) v_r[k] -= minVal - spc_r[k];
+                }
             }
-            __syncthreads();
-            // dual update (Crouse 2016, Alg. 1): rows of SR
-            for (int k = lane; k < n_sr; k += 64) {
-                const int r = sr[k];
-                u[r] += (k == 0) ? minVal : minVal - spc[col4row[r]];
-            }
+            if (lane == 0) u[i] += minVal;
             __syncthreads();
             // augment back to row i
             if (lane == 0) {
@@ -409,8 +454,10 @@ __global__ __launch_bounds__(NC > 0 ? 256 : 64) void hungarian_pair_kernel(
     }
 #ifdef AXT_HUNG_STATS
     if (GAP == 1 && lane == 0 && blockIdx.x < 4096) {
-        unsigned long long *o = g_hung_stats + blockIdx.x * 8;
+        unsigned long long *o = g_hung_stats + blockIdx.x * HUNG_STAT_COLS;
         o[0] = st1 - st0; o[1] = HUNG_STAMP() - st1; o[2] = n_search; o[3] = n_step; o[4] = n; o[5] = m;
+        for (int k = 0; k < 4; ++k) o[8 + k] = seg_sum[k];
+        (void)seg_t;
     }
 #endif
     for (int i = lane; i < n; i += 64) {
@@ -693,9 +740,9 @@ extern "C" int axt_chain_tracks(const int32_t *d_count, int n_frames, int cap, c
 }
 
 #ifdef AXT_HUNG_STATS
-// diagnostic build: the statistics of the last gap-1 launch, u64 [4096 frame pairs][8]
+// diagnostic build: the statistics of the last gap-1 launch, u64 [4096 frame pairs][16]
 extern "C" int axt_debug_hung_stats(unsigned long long *h_out)
 {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_hung_stats), sizeof(unsigned long long) * 4096 * 8) == hipSuccess ? 0 : -1;
+    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_hung_stats), sizeof(unsigned long long) * 4096 * HUNG_STAT_COLS) == hipSuccess ? 0 : -1;
 }
 #endif
