@@ -106,6 +106,17 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     'axt_head_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                                       c_double, c_double, c_void_p]),
+    'axt_head_trainer_input_grad': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'axt_cnn_block_features_frames': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                              c_void_p, c_void_p]),
+    'axt_conv_trainer_create': (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [c_int, ctypes.POINTER(c_void_p)]),
+    'axt_conv_trainer_destroy': (None, [c_void_p]),
+    'axt_conv_trainer_device_bytes': (c_size_t, [c_void_p]),
+    'axt_conv_trainer_read_weights': (c_int, [c_void_p] * 5),
+    'axt_conv_trainer_read_moments': (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int64)]),
+    'axt_conv_trainer_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'axt_conv_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
+                                      c_double, c_double, c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),
     'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),

@@ -1816,7 +1816,8 @@ int run_front_b(axt_detector *d, int nb, float *act4_out, hipStream_t st)
 
 // conv layers 5..7 for nb items whose block-4 output is in d_act[4]: d_act[7] [item,160,16,16] is what the first linear
 // layer reads (the flatten of model.py:50-53 is this buffer as it stands)
-int run_back_conv(axt_detector *d, int nb, hipStream_t st)
+// last: the last conv block to run (7, or 6 for axt_cnn_block_features_frames(block = 6))
+int run_back_conv(axt_detector *d, int nb, hipStream_t st, int last = 7)
 {
     int rc;
     {
@@ -1833,6 +1834,7 @@ int run_back_conv(axt_detector *d, int nb, hipStream_t st)
                       : launch_conv<80, 80, true, 8, 5>(d->d_act[5], d->d_wconv[6], d->d_bconv[6], d->d_act[6], 32, 1, nb, st);
         if (rc) return rc;
     }
+    if (last < 7) return AXT_OK;
     {
         ProfSpan ps(d, st, 7, nb);
         rc = d->arith == 2 ? launch_conv_wino<80, false, 2>(d->d_act[6], d->d_wwino[7], d->d_bconv[7], d->d_act[7], 16, nb, st)
@@ -1875,9 +1877,10 @@ int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
 }
 
 // d_feat != nullptr: stop after conv block 10 and copy its output, the input of the first linear layer, to
-// d_feat [n_items, 40960] (axt_cnn_features_frames); d_yolo is not written then
+// d_feat [n_items, 40960] (axt_cnn_features_frames); d_yolo is not written then. feat_block = 6: stop one block earlier and
+// copy d_act[6], [n_items, 20480] (axt_cnn_block_features_frames)
 int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, int tstep, int n_items, int n_tiles,
-                  const TileList &tl, float *d_yolo, hipStream_t st, float *d_feat = nullptr)
+                  const TileList &tl, float *d_yolo, hipStream_t st, float *d_feat = nullptr, int feat_block = 7)
 {
     for (int base = 0; base < n_items; base += d->max_batch) {
         const int nb = (n_items - base < d->max_batch) ? n_items - base : d->max_batch;
@@ -1892,9 +1895,10 @@ int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, 
             if (rc) return rc;
         }
         if (d_feat) {
-            const int rc = run_back_conv(d, nb, st);
+            const int rc = run_back_conv(d, nb, st, feat_block);
             if (rc) return rc;
-            AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)base * kFeat, d->d_act[7], (size_t)nb * kFeat * sizeof(float),
+            const size_t per_item = feat_block == 7 ? (size_t)kFeat : (size_t)80 * 16 * 16;
+            AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)base * per_item, d->d_act[feat_block], (size_t)nb * per_item * sizeof(float),
                                          hipMemcpyDeviceToDevice, st));
             continue;
         }
@@ -2129,6 +2133,28 @@ int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all,
     }
     if (n_frames == 0) return AXT_OK;
     return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, nullptr, (hipStream_t)stream, d_feat);
+}
+
+int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
+                                  const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream)
+{
+    AXT_REQUIRE(block == 6 || block == 7, "axt_cnn_block_features_frames: block %d is neither 6 nor 7", block);
+    AXT_REQUIRE(det && d_frames && d_feat && h_tile_yx, "null argument");
+    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
+    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",
+                t0, t0 + n_frames, T_all);
+    TileList tl;
+    tl.n = n_tiles;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * AXT_TILE < H && tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
+                    ty, tx, H, W);
+        tl.yx[2 * k] = (short)ty;
+        tl.yx[2 * k + 1] = (short)tx;
+    }
+    if (n_frames == 0) return AXT_OK;
+    return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, nullptr, (hipStream_t)stream, d_feat,
+                         block);
 }
 
 int axt_cnn_front_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,

@@ -8,6 +8,7 @@
 //                    LDS tiles, split over r so that a skinny product (B <= 64) fills the machine. WT: W is [J][R]
 //                    (forward, state_dict layout), else [R][J] (backward: dA = dZ W).
 //   head_reduce      sums the slabs in ascending s (+ bias, + Sigmoid | * a(1-a) for the backward pass)
+//   head_sum_slabs   sums the slabs in ascending s and nothing else (the input gradient dZ1 W1)
 //   yolo_loss_k      one workgroup: the five loss components in f64 through a fixed tree, and dY
 //   adam_fused       per weight element: g = sum_b dZ[b,n] In[b,k] in ascending b (never stored), then the Adam update
 //                    of w, m, v in place. The hot path: streams w, m, v once in and once out.
@@ -176,6 +177,16 @@ __global__ __launch_bounds__(256) void head_reduce(const float *__restrict__ sla
     out[i] = s;
 }
 
+// out[i] = sum_s slab[s][i] in ascending s, nothing else (axt_head_trainer_input_grad)
+__global__ __launch_bounds__(256) void head_sum_slabs(const float *__restrict__ slab, int S, size_t n, float *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = slab[i];
+    for (int k = 1; k < S; ++k) s += slab[(size_t)k * n + i];
+    out[i] = s;
+}
+
 // ------------------------------------------------------------------------------------------------ loss
 // pred [B,144,3], target table [.,144,4] gathered by index. comp f64 [5]: no_object, object, xy, summed, pos rate.
 __global__ __launch_bounds__(256) void yolo_loss_k(const float *__restrict__ pred, const float *__restrict__ target,
@@ -333,6 +344,7 @@ struct axt_head_trainer {
     float *a1 = nullptr, *a2 = nullptr;             // Sigmoid outputs of the last forward batch
     float *dz1 = nullptr, *dz2 = nullptr;
     float *slab = nullptr;
+    float *ig_dz1 = nullptr, *ig_dz2 = nullptr, *ig_slab = nullptr;    // axt_head_trainer_input_grad's own scratch, allocated by its first call
     double *d_comp = nullptr;
     int last_B = 0;                     // batch of the stashes
     size_t bytes = 0;
@@ -583,6 +595,40 @@ int axt_head_trainer_step(axt_head_trainer *t, const float *d_feat, const int32_
     if ((rc = launch_adam(t, 2, d_dy, t->a2, nullptr, B, a, st))) return rc;
     if ((rc = launch_adam(t, 1, t->dz2, t->a1, nullptr, B, a, st))) return rc;
     if ((rc = launch_adam(t, 0, t->dz1, d_feat, d_index, B, a, st))) return rc;
+    return AXT_OK;
+}
+
+// dFeat = dZ1 W1 from the stashes of the last _forward and the weights as they stand, in scratch of its own (allocated by
+// the first call): nothing that _forward, _loss or _step read or write is touched.
+int axt_head_trainer_input_grad(axt_head_trainer *t, const float *d_dy, int B, float *d_dfeat, void *stream)
+{
+    AXT_REQUIRE(t && d_dy && d_dfeat, "null argument");
+    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_head_trainer_input_grad: batch %d not in [1,%d]", B, t->max_batch);
+    AXT_REQUIRE(B == t->last_B, "axt_head_trainer_input_grad: the stashed activations are of a batch of %d, not %d: call "
+                "axt_head_trainer_forward on this batch first", t->last_B, B);
+    hipStream_t st = (hipStream_t)stream;
+    const int K0 = t->dims[0], H1 = t->dims[1], H2 = t->dims[2], NOUT = t->dims[3];
+    int S, chunk, rc;
+    if (!t->ig_slab) {
+        size_t floats = 0;
+        for (int l = 0; l < 3; ++l) {
+            plan_split(t->dims[l], t->dims[l + 1], &S, &chunk);             // J = in, R = out
+            floats = std::max(floats, (size_t)S * t->max_batch * t->dims[l]);
+        }
+        if ((rc = tr_alloc(t, (void **)&t->ig_dz1, (size_t)t->max_batch * H1 * sizeof(float), false))) return rc;
+        if ((rc = tr_alloc(t, (void **)&t->ig_dz2, (size_t)t->max_batch * H2 * sizeof(float), false))) return rc;
+        if ((rc = tr_alloc(t, (void **)&t->ig_slab, floats * sizeof(float), false))) return rc;
+    }
+    if ((rc = launch_head_gemm<false>(d_dy, nullptr, NOUT, t->w[2], H2, NOUT, B, t->ig_slab, &S, st))) return rc;
+    if ((rc = launch_head_reduce(t->ig_slab, S, B, H2, nullptr, t->a2, 2, t->ig_dz2, st))) return rc;
+    if ((rc = launch_head_gemm<false>(t->ig_dz2, nullptr, H2, t->w[1], H1, H2, B, t->ig_slab, &S, st))) return rc;
+    if ((rc = launch_head_reduce(t->ig_slab, S, B, H1, nullptr, t->a1, 2, t->ig_dz1, st))) return rc;
+    plan_split(K0, H1, &S, &chunk);
+    if (S == 1) return launch_head_gemm<false>(t->ig_dz1, nullptr, H1, t->w[0], K0, H1, B, d_dfeat, &S, st);  // one slab is the sum
+    if ((rc = launch_head_gemm<false>(t->ig_dz1, nullptr, H1, t->w[0], K0, H1, B, t->ig_slab, &S, st))) return rc;
+    const size_t n = (size_t)B * K0;
+    hipLaunchKernelGGL(head_sum_slabs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t->ig_slab, S, n, d_dfeat);
+    AXT_LAUNCH_CHECK();
     return AXT_OK;
 }
 

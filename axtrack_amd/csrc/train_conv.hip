@@ -1,0 +1,384 @@
+// train_conv.hip -- fine-tuning of one convolutional block (Conv2d 3x3 pad 1 + BatchNorm2d + LeakyReLU(0.1), model.py:5-18)
+// together with the linear head of train.hip: the block's forward pass in training form (unfolded BatchNorm, f32, the
+// weights change every step), its backward pass from the head's input gradient, and torch.optim.Adam with L2 weight decay
+// on conv.weight, conv.bias, batchnorm.weight and batchnorm.bias. BatchNorm uses its running statistics, which are never
+// updated. DESIGN.md 6.8e.
+//
+// Both products run over the im2col matrix X(q, r) of the batch, never stored:
+//   q = ci*9 + ky*3 + kx (the order of conv.weight's last three dimensions), r = b*H*W + h*W + w,
+//   X(q, r) = x[row(b)][ci][h+ky-1][w+kx-1], 0 outside the map.
+// Kernels
+//   conv_fwd_k       z[co][r] = sum_q W[co][q] X(q, r) + bias in ascending q (ci, ky, kx): every run of 16 q is one f32 FMA
+//                    chain from zero, the runs' sums are added in ascending order. Then y = gamma (z - mean) inv_sigma + beta,
+//                    F = y > 0 ? y : 0.1 y. 64 co x 64 r per workgroup from LDS tiles 16 deep, 4 x 4 outputs per thread.
+//                    Writes z (the stash) and F.
+//   conv_bn_back_k   one workgroup per output channel: dy = dF * (y > 0 ? 1 : 0.1) with y recomputed from the stashed z by
+//                    the forward's own expression (the sign information), dz = dy * gamma * inv_sigma stored for the
+//                    weight gradient, and dgamma = sum dy zhat, dbeta = sum dy, dbias = sum dz; then Adam on the three
+//                    per-channel parameters. Thread t sums r = t, t+256, ... of r = b*H*W + h*W + w in that order (b
+//                    ascending); the 256 partial sums meet in a fixed binary tree.
+//   conv_wgrad_k     slab[s][co][q] = sum over the s-th run of r of dz[co][r] X(q, r): the same tiles with the roles of q
+//                    and r exchanged, in ascending r (b, h, w): chains of 16 from zero, their sums added in ascending order.
+//                    The split of r into runs depends on the sizes and B only (plan_wgrad).
+//   conv_adam_w_k    per weight: g = slab[0] + slab[1] + ... in ascending s, then the Adam update of w, m, v in place
+// Determinism: no atomics; every sum has one fixed order that depends on Ci, Co, H, W and B only.
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "adam.h"
+#include "axt_common.h"
+
+namespace {
+
+constexpr int kMaxB = 64, kMaxC = 512, kMaxHW = 64;     // the limits include/axtrack_hip.h states
+constexpr int TM = 64, TN = 64, TK = 16, TPAD = 68;     // output channels and columns per workgroup, tile depth, LDS pitch
+constexpr float kSlope = 0.1f;
+constexpr double kBnEps = 1e-5;
+
+struct Geom { int Ci, Co, H, W, HW, K9; };
+
+// y of BatchNorm in the one form both passes use, so that the backward pass sees the forward's sign
+__device__ inline float bn_y(float z, float mean, float inv_sigma, float gamma, float beta, float *zhat)
+{
+    const float zh = __fmul_rn(__fsub_rn(z, mean), inv_sigma);
+    *zhat = zh;
+    return fmaf(gamma, zh, beta);
+}
+
+// x[row][ci][h+ky-1][w+kx-1] with q = ci*9 + ky*3 + kx; (b, h, w) already split; 0 outside the map
+__device__ inline float im2col(const float *__restrict__ x, size_t row, const Geom &g, int q, int h, int w)
+{
+    const int ci = q / 9, tap = q - ci * 9, ky = tap / 3, kx = tap - ky * 3;
+    const int hh = h + ky - 1, ww = w + kx - 1;
+    if (hh < 0 || hh >= g.H || ww < 0 || ww >= g.W) return 0.f;
+    return x[(row * g.Ci + ci) * g.HW + hh * g.W + ww];
+}
+
+// acc[i][j] += (sum_k As[k][tm*4+i] * Bs[k][tn*4+j]): the tile's 16 products in one FMA chain from zero, k ascending, and
+// that sum added to the running total -- a two-level sum whose error grows with sqrt(K / 16) + 4 instead of sqrt(K)
+__device__ inline void tile_fma(const float (*As)[TPAD], const float (*Bs)[TPAD], int tm, int tn, float (&total)[4][4])
+{
+    float acc[4][4] = {};
+#pragma unroll
+    for (int k = 0; k < TK; ++k) {
+        const float4 a4 = *reinterpret_cast<const float4 *>(&As[k][tm * 4]);
+        const float4 b4 = *reinterpret_cast<const float4 *>(&Bs[k][tn * 4]);
+        const float a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) total[i][j] += acc[i][j];
+}
+
+// grid (r tiles, co tiles). x: table [., Ci*H*W], rows picked by index (NULL: 0..B-1). z, F: [B][Co][H*W].
+__global__ __launch_bounds__(256) void conv_fwd_k(const float *__restrict__ x, const int *__restrict__ index, int B, Geom g,
+                                                  const float *__restrict__ Wt, const float *__restrict__ bias,
+                                                  const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                  const float *__restrict__ mean, const float *__restrict__ inv_sigma,
+                                                  float *__restrict__ z, float *__restrict__ F)
+{
+    __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // W[co][q] as [q][co]
+    __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // X(q, r) as [q][r]
+    const int tid = threadIdx.x, tm = tid / 16, tn = tid % 16;
+    const int r0 = blockIdx.x * TN, co0 = blockIdx.y * TM, R = B * g.HW;
+    // the column this thread stages: r is fixed, q walks
+    const int rl = tid % TN, r = r0 + rl;
+    const bool r_ok = r < R;
+    const int b = r_ok ? r / g.HW : 0, p = r - b * g.HW, h = p / g.W, w = p - h * g.W;
+    const size_t row = r_ok ? (size_t)(index ? index[b] : b) : 0;
+    float acc[4][4] = {};
+    for (int q0 = 0; q0 < g.K9; q0 += TK) {
+        for (int i = tid; i < TM * TK; i += 256) {
+            const int k = i % TK, c = i / TK;
+            As[k][c] = (co0 + c < g.Co && q0 + k < g.K9) ? Wt[(size_t)(co0 + c) * g.K9 + q0 + k] : 0.f;
+        }
+        for (int k = tid / TN; k < TK; k += 256 / TN)
+            Bs[k][rl] = (r_ok && q0 + k < g.K9) ? im2col(x, row, g, q0 + k, h, w) : 0.f;
+        __syncthreads();
+        tile_fma(As, Bs, tm, tn, acc);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int co = co0 + tm * 4 + i;
+        if (co >= g.Co) continue;
+        const float bi = bias[co], ga = gamma[co], be = beta[co], me = mean[co], is = inv_sigma[co];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rr = r0 + tn * 4 + j;
+            if (rr >= R) continue;
+            const int bb = rr / g.HW, pp = rr - bb * g.HW;
+            const size_t o = ((size_t)bb * g.Co + co) * g.HW + pp;
+            const float zz = acc[i][j] + bi;
+            float zh;
+            const float y = bn_y(zz, me, is, ga, be, &zh);
+            z[o] = zz;
+            F[o] = y > 0.f ? y : kSlope * y;
+        }
+    }
+}
+
+// grid (Co). dF, z, dz: [B][Co][H*W]. Updates bias, gamma, beta and their moments (p, m, v: [3][Co] in that order).
+__global__ __launch_bounds__(256) void conv_bn_back_k(const float *__restrict__ dF, const float *__restrict__ z, int B, Geom g,
+                                                      float *__restrict__ bias, float *__restrict__ gamma,
+                                                      float *__restrict__ beta, const float *__restrict__ mean,
+                                                      const float *__restrict__ inv_sigma, float *__restrict__ mom_m,
+                                                      float *__restrict__ mom_v, float *__restrict__ dz, AdamArgs a)
+{
+    __shared__ float red[3][256];
+    const int tid = threadIdx.x, co = blockIdx.x;
+    const float ga = gamma[co], be = beta[co], me = mean[co], is = inv_sigma[co];
+    const float fold = ga * is;
+    float s_gamma = 0.f, s_beta = 0.f, s_bias = 0.f;
+    for (int r = tid; r < B * g.HW; r += 256) {                        // r = b*H*W + p: thread t takes r = t, t + 256, ...
+        const int b = r / g.HW, p = r - b * g.HW;
+        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        float zh;
+        const float y = bn_y(z[o], me, is, ga, be, &zh);
+        const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+        const float d = dy * fold;
+        s_gamma = fmaf(dy, zh, s_gamma);
+        s_beta += dy;
+        s_bias += d;
+        dz[o] = d;
+    }
+    red[0][tid] = s_bias; red[1][tid] = s_gamma; red[2][tid] = s_beta;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w)
+            for (int q = 0; q < 3; ++q) red[q][tid] += red[q][tid + w];
+        __syncthreads();
+    }
+    if (tid < 3) {
+        float *param = tid == 0 ? bias : tid == 1 ? gamma : beta;
+        float w = param[co], m = mom_m[tid * g.Co + co], v = mom_v[tid * g.Co + co];
+        adam1(red[tid][0], w, m, v, a);
+        param[co] = w;
+        mom_m[tid * g.Co + co] = m;
+        mom_v[tid * g.Co + co] = v;
+    }
+}
+
+// grid (q tiles, co tiles, S). slab [S][Co][K9].
+__global__ __launch_bounds__(256) void conv_wgrad_k(const float *__restrict__ x, const int *__restrict__ index, int B, Geom g,
+                                                    const float *__restrict__ dz, int rchunk, float *__restrict__ slab)
+{
+    __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // dz[co][r] as [r][co]
+    __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // X(q, r) as [r][q]
+    const int tid = threadIdx.x, tm = tid / 16, tn = tid % 16;
+    const int q0 = blockIdx.x * TN, co0 = blockIdx.y * TM, R = B * g.HW;
+    const int r_begin = blockIdx.z * rchunk, r_end = min(R, r_begin + rchunk);
+    const int kl = tid % TK;                                          // the r this thread stages within a tile
+    float acc[4][4] = {};
+    for (int r0 = r_begin; r0 < r_end; r0 += TK) {
+        const int r = r0 + kl;
+        const bool r_ok = r < r_end;
+        const int b = r_ok ? r / g.HW : 0, p = r - b * g.HW, h = p / g.W, w = p - h * g.W;
+        const size_t row = r_ok ? (size_t)(index ? index[b] : b) : 0;
+        for (int c = tid / TK; c < TM; c += 256 / TK) {
+            As[kl][c] = (r_ok && co0 + c < g.Co) ? dz[((size_t)b * g.Co + co0 + c) * g.HW + p] : 0.f;
+            Bs[kl][c] = (r_ok && q0 + c < g.K9) ? im2col(x, row, g, q0 + c, h, w) : 0.f;
+        }
+        __syncthreads();
+        tile_fma(As, Bs, tm, tn, acc);
+        __syncthreads();
+    }
+    float *dst = slab + (size_t)blockIdx.z * g.Co * g.K9;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int co = co0 + tm * 4 + i;
+        if (co >= g.Co) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int q = q0 + tn * 4 + j;
+            if (q < g.K9) dst[(size_t)co * g.K9 + q] = acc[i][j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void conv_adam_w_k(float *__restrict__ W, float *__restrict__ M, float *__restrict__ V, int n,
+                                                     const float *__restrict__ slab, int S, AdamArgs a)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float gsum = slab[i];
+    for (int s = 1; s < S; ++s) gsum += slab[(size_t)s * n + i];
+    float w = W[i], m = M[i], v = V[i];
+    adam1(gsum, w, m, v, a);
+    W[i] = w; M[i] = m; V[i] = v;
+}
+
+// split of the reduction over r = B*H*W for the weight gradient: about 1024 workgroups, runs a multiple of the tile depth
+int wgrad_max_split(const Geom &g) { return std::max(1, std::min(64, 1024 / (axt_cdiv(g.K9, TN) * axt_cdiv(g.Co, TM)))); }
+
+void plan_wgrad(const Geom &g, int B, int *S, int *rchunk)
+{
+    const int R = B * g.HW;
+    const int chunk = axt_cdiv(axt_cdiv(R, wgrad_max_split(g)), TK) * TK;
+    *rchunk = chunk;
+    *S = axt_cdiv(R, chunk);
+}
+
+}  // namespace
+
+struct axt_conv_trainer {
+    Geom g = {};
+    int max_batch = 0;
+    long step = 0;
+    float *w = nullptr, *mw = nullptr, *vw = nullptr;       // conv.weight [Co][Ci][3][3] and its moments
+    float *p3 = nullptr, *m3 = nullptr, *v3 = nullptr;      // [3][Co]: conv.bias, batchnorm.weight, batchnorm.bias
+    float *mean = nullptr, *inv_sigma = nullptr;            // running_mean, 1 / sqrt(running_var + 1e-5)
+    float *z = nullptr, *dz = nullptr, *slab = nullptr;     // stash of the last forward batch; scratch
+    int last_B = 0;
+    size_t bytes = 0;
+    std::vector<void *> allocs;
+};
+
+namespace {
+
+int ct_alloc(axt_conv_trainer *t, float **p, size_t floats, bool zero)
+{
+    const size_t bytes = floats * sizeof(float);
+    if (hipMalloc((void **)p, bytes) != hipSuccess) {
+        axt_set_error("axt_conv_trainer: hipMalloc of %zu bytes failed", bytes);
+        return AXT_ENOMEM;
+    }
+    t->allocs.push_back(*p);
+    t->bytes += bytes;
+    if (zero) AXT_CHECK_HIP(hipMemset(*p, 0, bytes));
+    return AXT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void axt_conv_trainer_destroy(axt_conv_trainer *t)
+{
+    if (!t) return;
+    for (void *p : t->allocs) (void)hipFree(p);
+    delete t;
+}
+
+int axt_conv_trainer_create(int Ci, int Co, int H, int W, const float *h_weight, const float *h_bias, const float *h_gamma,
+                            const float *h_beta, const float *h_mean, const float *h_var, int max_batch,
+                            axt_conv_trainer **out)
+{
+    AXT_REQUIRE(out && h_weight && h_bias && h_gamma && h_beta && h_mean && h_var, "null argument");
+    AXT_REQUIRE(Ci >= 1 && Ci <= kMaxC && Co >= 1 && Co <= kMaxC, "axt_conv_trainer_create: channels %d -> %d not in [1,%d]",
+                Ci, Co, kMaxC);
+    AXT_REQUIRE(H >= 1 && H <= kMaxHW && W >= 1 && W <= kMaxHW, "axt_conv_trainer_create: map %d x %d not in [1,%d]", H, W,
+                kMaxHW);
+    AXT_REQUIRE(max_batch >= 1 && max_batch <= kMaxB, "axt_conv_trainer_create: max_batch %d not in [1,%d]", max_batch, kMaxB);
+    axt_conv_trainer *t = new (std::nothrow) axt_conv_trainer;
+    if (!t) {
+        axt_set_error("axt_conv_trainer_create: out of host memory");
+        return AXT_ENOMEM;
+    }
+    t->g = Geom{Ci, Co, H, W, H * W, Ci * 9};
+    t->max_batch = max_batch;
+    const size_t nw = (size_t)Co * Ci * 9, nz = (size_t)max_batch * Co * H * W;
+    std::vector<float> p3((size_t)3 * Co), is(Co);
+    for (int c = 0; c < Co; ++c) {
+        p3[c] = h_bias[c];
+        p3[Co + c] = h_gamma[c];
+        p3[2 * Co + c] = h_beta[c];
+        is[c] = (float)(1.0 / std::sqrt((double)h_var[c] + kBnEps));
+    }
+    int rc;
+    auto fail = [&](int code) { axt_conv_trainer_destroy(t); return code; };
+    if ((rc = ct_alloc(t, &t->w, nw, false)) || (rc = ct_alloc(t, &t->mw, nw, true)) || (rc = ct_alloc(t, &t->vw, nw, true)) ||
+        (rc = ct_alloc(t, &t->p3, p3.size(), false)) || (rc = ct_alloc(t, &t->m3, p3.size(), true)) ||
+        (rc = ct_alloc(t, &t->v3, p3.size(), true)) || (rc = ct_alloc(t, &t->mean, Co, false)) ||
+        (rc = ct_alloc(t, &t->inv_sigma, Co, false)) || (rc = ct_alloc(t, &t->z, nz, true)) ||
+        (rc = ct_alloc(t, &t->dz, nz, true)) || (rc = ct_alloc(t, &t->slab, (size_t)wgrad_max_split(t->g) * nw, false)))
+        return fail(rc);
+    if (hipMemcpy(t->w, h_weight, nw * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(t->p3, p3.data(), p3.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(t->mean, h_mean, Co * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(t->inv_sigma, is.data(), Co * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        axt_set_error("axt_conv_trainer_create: weight upload failed");
+        return fail(AXT_EHIP);
+    }
+    *out = t;
+    return AXT_OK;
+}
+
+size_t axt_conv_trainer_device_bytes(const axt_conv_trainer *t) { return t ? t->bytes : 0; }
+
+int axt_conv_trainer_read_weights(const axt_conv_trainer *t, float *h_weight, float *h_bias, float *h_gamma, float *h_beta)
+{
+    AXT_REQUIRE(t && h_weight && h_bias && h_gamma && h_beta, "null argument");
+    const size_t nc = (size_t)t->g.Co * sizeof(float);
+    AXT_CHECK_HIP(hipDeviceSynchronize());
+    AXT_CHECK_HIP(hipMemcpy(h_weight, t->w, (size_t)t->g.Co * t->g.K9 * sizeof(float), hipMemcpyDeviceToHost));
+    AXT_CHECK_HIP(hipMemcpy(h_bias, t->p3, nc, hipMemcpyDeviceToHost));
+    AXT_CHECK_HIP(hipMemcpy(h_gamma, t->p3 + t->g.Co, nc, hipMemcpyDeviceToHost));
+    AXT_CHECK_HIP(hipMemcpy(h_beta, t->p3 + 2 * t->g.Co, nc, hipMemcpyDeviceToHost));
+    return AXT_OK;
+}
+
+int axt_conv_trainer_read_moments(const axt_conv_trainer *t, int tensor, float *h_m, float *h_v, int64_t *step)
+{
+    AXT_REQUIRE(t && tensor >= 0 && tensor < 4, "axt_conv_trainer_read_moments: bad handle or tensor");
+    const size_t n = (tensor == 0 ? (size_t)t->g.Co * t->g.K9 : (size_t)t->g.Co) * sizeof(float);
+    const float *m = tensor == 0 ? t->mw : t->m3 + (size_t)(tensor - 1) * t->g.Co;
+    const float *v = tensor == 0 ? t->vw : t->v3 + (size_t)(tensor - 1) * t->g.Co;
+    AXT_CHECK_HIP(hipDeviceSynchronize());
+    if (h_m) AXT_CHECK_HIP(hipMemcpy(h_m, m, n, hipMemcpyDeviceToHost));
+    if (h_v) AXT_CHECK_HIP(hipMemcpy(h_v, v, n, hipMemcpyDeviceToHost));
+    if (step) *step = t->step;
+    return AXT_OK;
+}
+
+int axt_conv_trainer_forward(axt_conv_trainer *t, const float *d_in, const int32_t *d_index, int B, float *d_feat,
+                             void *stream)
+{
+    AXT_REQUIRE(t && d_in && d_feat, "null argument");
+    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_conv_trainer_forward: batch %d not in [1,%d]", B, t->max_batch);
+    const Geom &g = t->g;
+    const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Co, TM));
+    hipLaunchKernelGGL(conv_fwd_k, grid, dim3(256), 0, (hipStream_t)stream, d_in, d_index, B, g, t->w, t->p3, t->p3 + g.Co,
+                       t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->z, d_feat);
+    AXT_LAUNCH_CHECK();
+    t->last_B = B;
+    return AXT_OK;
+}
+
+int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t *d_index, int B, const float *d_dfeat,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, void *stream)
+{
+    AXT_REQUIRE(t && d_in && d_dfeat, "null argument");
+    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_conv_trainer_step: batch %d not in [1,%d]", B, t->max_batch);
+    AXT_REQUIRE(B == t->last_B, "axt_conv_trainer_step: the stashed activations are of a batch of %d, not %d: call "
+                "axt_conv_trainer_forward on this batch first", t->last_B, B);
+    AXT_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0,
+                "axt_conv_trainer_step: bad Adam parameters");
+    hipStream_t st = (hipStream_t)stream;
+    const Geom &g = t->g;
+    t->step += 1;
+    const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, t->step);
+    // dz from gamma as it stands: each workgroup reads its channel's gamma before it updates it
+    hipLaunchKernelGGL(conv_bn_back_k, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
+                       t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->m3, t->v3, t->dz, a);
+    AXT_LAUNCH_CHECK();
+    int S, rchunk;
+    plan_wgrad(g, B, &S, &rchunk);
+    hipLaunchKernelGGL(conv_wgrad_k, dim3(axt_cdiv(g.K9, TN), axt_cdiv(g.Co, TM), S), dim3(256), 0, st, d_in, d_index, B, g,
+                       t->dz, rchunk, t->slab);
+    AXT_LAUNCH_CHECK();
+    const int nw = g.Co * g.K9;
+    hipLaunchKernelGGL(conv_adam_w_k, dim3(axt_cdiv(nw, 256)), dim3(256), 0, st, t->w, t->mw, t->vw, nw, t->slab, S, a);
+    AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+}  // extern "C"

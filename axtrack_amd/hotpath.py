@@ -11,6 +11,7 @@ from . import _lib
 
 TILE, S, CELLS = 512, 12, 144
 FEATURES = 160 * 16 * 16                # what the first linear layer reads per tile (model.py:50-53)
+BLOCK_FEATURES = {7: FEATURES, 6: 80 * 16 * 16}      # Detector.features_frames(block=): floats per item after conv block 7 / 6
 CONF_FLOOR = float(np.float32(0.55))   # all_conf_thrs.min() as f32 (AxonDetections.py:76,122)
 MAX_PX_ASSOC_DIST = 500                # AxonDetections.py:77
 AXON_BOX_SIZE = 70                     # AxonDetections.py:78
@@ -162,28 +163,39 @@ class Detector:
         return out
 
 
-    def features_frames(self, frames, tile_yx, t0=0, n_frames=None, out=None):
+    def features_frames(self, frames, tile_yx, t0=0, n_frames=None, out=None, block=7):
         """The frozen trunk of detect_frames: frames f32 [T_all,H,W] on the GPU -> [n_frames * n_tiles, 40960], the input of
         the first linear layer per (frame, tile) item in the flatten order of model.py:50-53 (axt_cnn_features_frames).
         What training.HeadTrainer trains on. out: a contiguous f32 table of at least that many rows to write into (its
-        first n_frames * n_tiles rows are returned) instead of a new one."""
+        first n_frames * n_tiles rows are returned) instead of a new one. block=6: the trunk one conv block earlier,
+        [n_frames * n_tiles, 20480] = [item, 80, 16, 16], what training.ConvBlockTrainer reads
+        (axt_cnn_block_features_frames); block=7 is the default table."""
+        if block not in BLOCK_FEATURES:
+            raise ValueError(f'block must be one of {sorted(BLOCK_FEATURES)}, got {block}')
+        width = BLOCK_FEATURES[block]
         T_all, H, W = frames.shape
         if n_frames is None:
             n_frames = T_all - 4 - t0
         tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
         n_items = n_frames * len(tile_yx)
         if out is None:
-            out = torch.empty((n_items, FEATURES), dtype=torch.float32, device=self.device)
+            out = torch.empty((n_items, width), dtype=torch.float32, device=self.device)
         else:
             if not (out.is_contiguous() and out.dtype == torch.float32 and out.device == self.device and out.dim() == 2
-                    and out.shape[1] == FEATURES and out.shape[0] >= n_items):
-                raise ValueError(f'out must be a contiguous f32 table [>= {n_items}, {FEATURES}] on {self.device}')
+                    and out.shape[1] == width and out.shape[0] >= n_items):
+                raise ValueError(f'out must be a contiguous f32 table [>= {n_items}, {width}] on {self.device}')
             out = out[:n_items]
         assert frames.is_contiguous() and frames.dtype == torch.float32 and frames.device == self.device
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.axt_cnn_features_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,
-                                                         tile_yx.ctypes.data, len(tile_yx), out.data_ptr(), _stream()),
-                       'axt_cnn_features_frames')
+            if block == 7:
+                _lib.check(self._lib.axt_cnn_features_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,
+                                                             tile_yx.ctypes.data, len(tile_yx), out.data_ptr(), _stream()),
+                           'axt_cnn_features_frames')
+            else:
+                _lib.check(self._lib.axt_cnn_block_features_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,
+                                                                   tile_yx.ctypes.data, len(tile_yx), int(block),
+                                                                   out.data_ptr(), _stream()),
+                           'axt_cnn_block_features_frames')
         return out
 
     def front_frames(self, frames, tile_yx, t0, n_frames, item0):

@@ -7,7 +7,12 @@ by the inference kernels (Detector.features_frames; once, or once per epoch when
 (core_functionality.py:109-165); its every-tenth-epoch metrics run when a labelled test timelapse is given
 (fine_tune_head(test_timelapse=...)). With use_transforms it also restates the reference's augmentation (augment.py): a new
 translate / flip / rotate of frames and labels every epoch, the prepare_data resampling loop, and the feature table
-recomputed from the warped frames, which costs about one trunk pass per epoch."""
+recomputed from the warped frames, which costs about one trunk pass per epoch.
+
+fine_tune_head(train_last_conv=True) trains the last convolutional block (ConvNet.ConvBlock_10) jointly with the head
+(ConvBlockTrainer, csrc/train_conv.hip): the cached table is then the trunk's output one block earlier, and a step runs the
+block's forward pass in training form, the head, the loss, the head's input gradient, and both Adam updates. BatchNorm
+keeps its running statistics, as at inference. Conv blocks 0-6 stay frozen."""
 import ctypes
 import os
 
@@ -185,6 +190,17 @@ class HeadTrainer:
                                                        ADAM_BETAS[1], float(eps), float(P['WEIGHT_DECAY']), _stream()),
                        'axt_head_trainer_step')
 
+    def input_grad(self, dy):
+        """The gradient of the loss with respect to the feature rows the last forward() read: dy [B,12,12,3] -> [B, K0]
+        (axt_head_trainer_input_grad). From the weights as they stand, so call it before step(); it changes nothing that
+        step() reads."""
+        self._check_table(dy, CELLS * 3, 'dy')
+        out = torch.empty((dy.shape[0], self.dims[0]), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_input_grad(self._h, dy.data_ptr(), dy.shape[0], out.data_ptr(), _stream()),
+                       'axt_head_trainer_input_grad')
+        return out
+
     def weights(self):
         """The six fcs.* tensors as numpy arrays, in FC_KEYS order."""
         K0, H1, H2, NO = self.dims
@@ -208,6 +224,109 @@ class HeadTrainer:
         """The state dict this trainer was built from with the six fcs.* tensors replaced by the trained ones (numpy f32)."""
         sd = dict(self._sd)
         sd.update(zip(FC_KEYS, self.weights()))
+        return sd
+
+
+CONV_SUFFIXES = ('conv.weight', 'conv.bias', 'batchnorm.weight', 'batchnorm.bias')         # what ConvBlockTrainer trains
+CONV_STATS = ('batchnorm.running_mean', 'batchnorm.running_var')                           # what it reads and leaves alone
+LAST_CONV_BLOCK = 'ConvNet.ConvBlock_10'            # conv block 7 of the package's numbering: 80 -> 160 on 16 x 16 maps
+
+
+class ConvBlockTrainer:
+    """One block Conv2d 3x3 + BatchNorm2d + LeakyReLU(0.1) of the state dict (model.py:5-18) on the device with the Adam
+    moments of its four trainable tensors (axt_conv_trainer). forward / step work on batches picked by index from a table
+    [n_items, Ci*H*W] of the block's inputs (Detector.features_frames(block=6) for the last block); forward's output
+    [B, Co*H*W] is what HeadTrainer.forward reads. BatchNorm runs with its running statistics and never updates them."""
+
+    def __init__(self, state_dict, block_key=LAST_CONV_BLOCK, parameters=None, map_size=(16, 16), max_batch=64,
+                 device='cuda:0'):
+        _require_gpu()
+        self.device = torch.device(device)
+        self.max_batch = int(max_batch)
+        self.block_key = block_key
+        self.P = dict(TRAIN_DEFAULTS)
+        self.P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
+        self._sd = state_dict
+        self.keys = tuple(f'{block_key}.{k}' for k in CONV_SUFFIXES + CONV_STATS)
+        for k in self.keys:
+            if k not in state_dict:
+                raise KeyError(f'state_dict lacks {k}')
+        w = [_np32(state_dict[k]) for k in self.keys]
+        if w[0].ndim != 4 or w[0].shape[2:] != (3, 3) or any(a.shape != (w[0].shape[0],) for a in w[1:]):
+            raise ValueError(f'not a 3x3 conv block: {[a.shape for a in w]}')
+        self.Co, self.Ci = int(w[0].shape[0]), int(w[0].shape[1])
+        self.H, self.W = (int(v) for v in map_size)
+        self.in_width, self.out_width = self.Ci * self.H * self.W, self.Co * self.H * self.W
+        self._lib = _lib.load()
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_create(self.Ci, self.Co, self.H, self.W, *[a.ctypes.data for a in w],
+                                                         self.max_batch, ctypes.byref(handle)), 'axt_conv_trainer_create')
+        self._h = handle
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            self._lib.axt_conv_trainer_destroy(h)
+
+    @property
+    def device_bytes(self):
+        return int(self._lib.axt_conv_trainer_device_bytes(self._h))
+
+    _index = HeadTrainer._index
+    _check_table = HeadTrainer._check_table
+
+    def forward(self, inputs, index=None):
+        """inputs f32 [n_items, Ci*H*W] on the GPU, index: which rows form the batch (default: all) -> [B, Co*H*W]."""
+        self._check_table(inputs, self.in_width, 'inputs')
+        index = self._index(index, inputs.shape[0])
+        out = torch.empty((len(index), self.out_width), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_forward(self._h, inputs.data_ptr(), index.data_ptr(), len(index),
+                                                          out.data_ptr(), _stream()), 'axt_conv_trainer_forward')
+        return out
+
+    def step(self, inputs, index, dfeat, lr=None, eps=ADAM_EPS):
+        """Backward pass of the batch the last forward() ran from dfeat [B, Co*H*W], the gradient with respect to its
+        output (HeadTrainer.input_grad), and one Adam step of the four tensors."""
+        self._check_table(inputs, self.in_width, 'inputs')
+        self._check_table(dfeat, self.out_width, 'dfeat')
+        index = self._index(index, inputs.shape[0])
+        if len(index) != dfeat.shape[0]:
+            raise ValueError(f'{dfeat.shape[0]} gradients for a batch of {len(index)}')
+        P = self.P
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_step(self._h, inputs.data_ptr(), index.data_ptr(), len(index),
+                                                       dfeat.data_ptr(), float(P['LR'] if lr is None else lr), ADAM_BETAS[0],
+                                                       ADAM_BETAS[1], float(eps), float(P['WEIGHT_DECAY']), _stream()),
+                       'axt_conv_trainer_step')
+
+    def _shapes(self):
+        return [(self.Co, self.Ci, 3, 3), (self.Co,), (self.Co,), (self.Co,)]
+
+    def weights(self):
+        """conv.weight, conv.bias, batchnorm.weight, batchnorm.bias as numpy arrays."""
+        out = [np.empty(s, np.float32) for s in self._shapes()]
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_read_weights(self._h, *[a.ctypes.data for a in out]),
+                       'axt_conv_trainer_read_weights')
+        return out
+
+    def moments(self, tensor):
+        """Adam state of tensor 0..3 (the order of weights()): (m, v, step count)."""
+        shape = self._shapes()[tensor]
+        m, v = np.empty(shape, np.float32), np.empty(shape, np.float32)
+        step = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_read_moments(self._h, int(tensor), m.ctypes.data, v.ctypes.data,
+                                                               ctypes.byref(step)), 'axt_conv_trainer_read_moments')
+        return m, v, int(step.value)
+
+    def state_dict(self, base=None):
+        """The state dict this trainer was built from (or `base`) with the block's four trained tensors replaced (numpy
+        f32); the running statistics and num_batches_tracked pass through."""
+        sd = dict(self._sd if base is None else base)
+        sd.update(zip(self.keys[:4], self.weights()))
         return sd
 
 
@@ -265,7 +384,7 @@ def _epoch_metrics(sd, timelapse, labels, parameters, subset):
 
 def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
                    use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
-                   metrics_every=10):
+                   metrics_every=10, train_last_conv=False):
     """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
     one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
     (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
@@ -287,9 +406,16 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
     (taken modulo the number of frames where the set has fewer than ten), and all frames of the test set; the confusion
     counts are summed over the frames and turned into precision / recall / F1 at the 13 thresholds. The result is
     history.attrs['metrics']: a DataFrame, rows (metric, threshold), columns (epoch, 'train' | 'test'). The evaluation
-    reads the weights only: history and the returned state dict are what they are without it."""
+    reads the weights only: history and the returned state dict are what they are without it.
+
+    train_last_conv: also train the last convolutional block (ConvNet.ConvBlock_10: conv.weight, conv.bias,
+    batchnorm.weight, batchnorm.bias; BatchNorm keeps its running statistics, as at inference) with the same learning
+    rate, Adam eps and weight decay. The cached table is then the trunk's output one block earlier
+    (Detector.features_frames(block=6)), and a step is conv forward, head forward, loss, the head's input gradient, conv
+    step, head step. The returned state dict and the checkpoints carry both sets of tensors."""
     import pandas as pd
-    from .hotpath import Detector, FEATURES
+    from .hotpath import Detector, BLOCK_FEATURES
+    block = 6 if train_last_conv else 7                 # which conv block's output the cached table holds
     for tl in (timelapse, test_timelapse):
         if getattr(tl, 'frame_sharded', False):
             raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
@@ -328,8 +454,8 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         if unknown:
             raise ValueError(f'unknown augmentation keys {unknown}; known: {augment.TRANSFORM_KEYS}')
         # the kept tiles change with every draw: one feature table for all tiles, of which an epoch uses the first rows
-        table = torch.empty((len(timelapse) * timelapse.ytiles * timelapse.xtiles, FEATURES), dtype=torch.float32,
-                            device=timelapse.device)
+        table = torch.empty((len(timelapse) * timelapse.ytiles * timelapse.xtiles, BLOCK_FEATURES[block]),
+                            dtype=torch.float32, device=timelapse.device)
         warped = torch.empty_like(timelapse.frames)
         label_xy = augment.label_floats(labels)
         label_xy = (*label_xy, np.full(len(labels), label_xy[0].shape[1], np.int32))
@@ -340,9 +466,13 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         trainer = HeadTrainer(sd, P, max_batch=bs, device=timelapse.device)
     else:
         tile_yx = timelapse.tile_yx
-        features = detector.features_frames(timelapse.frames, tile_yx)
+        features = detector.features_frames(timelapse.frames, tile_yx, block=block)
         targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
+    conv = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device) if train_last_conv else None
+    # the state dict of this moment: the head's tensors, and the conv block's where it is trained
+    current = (lambda: conv.state_dict(trainer.state_dict())) if train_last_conv else trainer.state_dict
+    identity = {}                                       # batch size -> rows 0..B-1 on the device: the head reads conv.forward's output
     rng = np.random.default_rng(seed)
     checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
     history, metrics = {}, {}
@@ -352,21 +482,32 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
             tf, warped, tile_yx, lab = _augmented_epoch(timelapse.frames, label_xy, None if transforms is None else
                                                         transforms[epoch], draw, min_pos_rate, max_redraws, warped)
             used.append(tf)
-            features = detector.features_frames(warped, tile_yx, out=table)
+            features = detector.features_frames(warped, tile_yx, out=table, block=block)
             targets = yolo_targets(lab, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         lr = learning_rate(P['LR'], P['LR_DECAYRATE'], epoch)
         rows = []
         for batch in epoch_batches(features.shape[0], bs, P['SHUFFLE'], P['DROP_LAST'], rng):
-            yolo = trainer.forward(features, batch)
-            comp, dy = trainer.loss(yolo, targets, batch)
-            trainer.step(features, batch, dy, lr=lr)
+            if train_last_conv:
+                feats = conv.forward(features, batch)
+                if len(batch) not in identity:
+                    identity[len(batch)] = torch.arange(len(batch), dtype=torch.int32, device=trainer.device)
+                rows_all = identity[len(batch)]
+                yolo = trainer.forward(feats, rows_all)
+                comp, dy = trainer.loss(yolo, targets, batch)
+                dfeat = trainer.input_grad(dy)              # from the head's weights before they move
+                conv.step(features, batch, dfeat, lr=lr)
+                trainer.step(feats, rows_all, dy, lr=lr)
+            else:
+                yolo = trainer.forward(features, batch)
+                comp, dy = trainer.loss(yolo, targets, batch)
+                trainer.step(features, batch, dy, lr=lr)
             rows.append([comp[k] for k in COMPONENTS])
         history[epoch] = np.mean(np.array(rows, np.float64).reshape(-1, 5), axis=0)
         if dest_dir is not None and epoch in checkpoints:
             os.makedirs(dest_dir, exist_ok=True)
-            save_checkpoint(trainer.state_dict(), f'{dest_dir}/E{epoch:04}.pth')
+            save_checkpoint(current(), f'{dest_dir}/E{epoch:04}.pth')
         if with_metrics and epoch % int(metrics_every) == 0:
-            now = trainer.state_dict()
+            now = current()
             tstart = int(m_rng.integers(0, 10)) % len(timelapse)
             metrics[(epoch, 'train')] = _epoch_metrics(now, timelapse, labels if explicit_labels else None, parameters,
                                                        list(range(tstart, len(timelapse), 10)))
@@ -377,4 +518,4 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         history.attrs['metrics'] = pd.DataFrame(metrics)
     if augmented:
         history.attrs['transforms'] = used
-    return trainer.state_dict(), history
+    return current(), history

@@ -106,6 +106,13 @@ int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, 
 int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                             const int32_t *h_tile_yx, int n_tiles, float *d_feat, void *stream);
 
+/* The trunk up to conv block `block` of the package's numbering (0..7), for training the blocks after it:
+ * axt_cnn_features_frames' arguments and chunking. block = 7: exactly axt_cnn_features_frames. block = 6: stops before conv
+ * block 7 (ConvNet.ConvBlock_10); d_feat f32 [n_frames*n_tiles, 20480] is [item, 80, 16, 16] NCHW, the output of
+ * ConvBlock_8 after its max-pool. Any other block: AXT_EINVAL. */
+int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
+                                  const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream);
+
 /* The same forward pass in two calls, for input that arrives in chunks (Timelapse.from_host_u16: the reference's inference()
  * starts from a host Timelapse and construct_tiles() moves it to the device, Timelapse.py:492-566): axt_cnn_front_frames runs
  * conv blocks 0-5 (through the second max-pool) for the (frame, tile) items of frames t0 .. t0+n_frames-1 and leaves their
@@ -605,6 +612,48 @@ int axt_head_trainer_loss(axt_head_trainer *tr, const float *d_yolo, const float
                           double lambda_obj, double lambda_noobj, double lambda_coord, double *h_components, float *d_dy,
                           void *stream);
 int axt_head_trainer_step(axt_head_trainer *tr, const float *d_feat, const int32_t *d_index, int B, const float *d_dy,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fine-tuning of the last convolutional block together with the head.
+ *
+ * axt_head_trainer_input_grad: the gradient of the loss with respect to the rows _forward read. From d_dy [B, NOUT], the
+ *   a1, a2 stashed by the last _forward (same B) and the weights as they stand: dZ2 = (dY W3) * a2 (1 - a2),
+ *   dZ1 = (dZ2 W2) * a1 (1 - a1), d_dfeat [B, K0] = dZ1 W1. Same kernels and fixed slab order as _step, no atomics.
+ *   Works in scratch of its own, allocated by the first call (_device_bytes grows then): calling it before _step leaves
+ *   _step's results byte-identical.
+ *
+ * axt_conv_trainer: one block Conv2d(Ci, Co, 3, padding 1) + BatchNorm2d + LeakyReLU(0.1) (model.py:5-18) in training
+ * form. Created from host tensors in the state dict's layout: conv.weight [Co,Ci,3,3], conv.bias, batchnorm.weight,
+ * batchnorm.bias, batchnorm.running_mean, batchnorm.running_var [Co]. Holds the four trainable tensors with Adam
+ * moments m, v (f32, zero), the step count, and z of the last forward batch. Limits: 1 <= Ci, Co <= 512,
+ * 1 <= H, W <= 64, 1 <= max_batch <= 64. BatchNorm runs with its running statistics, as at inference (eps 1e-5); they are
+ * never updated.
+ * _forward: d_index i32 [B] (NULL = rows 0..B-1) picks rows of the table d_in [., Ci*H*W] (NCHW per row);
+ *   z = conv3x3(x) + bias, y = gamma (z - mean) / sqrt(var + 1e-5) + beta, d_feat [B, Co*H*W] = y > 0 ? y : 0.1 y in the
+ *   order c*H*W + h*W + w -- the rows axt_head_trainer_forward reads. f32, BatchNorm not folded; per output FMA chains
+ *   of 16 terms in ascending (ci, ky, kx), their sums added in ascending order.
+ * _step: d_dfeat [B, Co*H*W] is the gradient with respect to _forward's output for the same batch (same d_in, d_index,
+ *   B). dy = dF * (y > 0 ? 1 : 0.1), dgamma = sum dy zhat, dbeta = sum dy, dz = dy gamma / sqrt(var + 1e-5),
+ *   dbias = sum dz, dW[co,ci,ky,kx] = sum_{b,h,w} dz[b,co,h,w] x[b,ci,h+ky-1,w+kx-1] (taps outside the map contribute
+ *   nothing), all from the parameters as they stand, then torch.optim.Adam with L2 weight decay on the four tensors
+ *   (t = the handle's step count after its increment). Sums run over b, h, w ascending within a fixed split that
+ *   depends on the sizes and B only, the parts added in ascending order. No atomics: byte-identical from run to run.
+ * _read_weights; _read_moments (tensor 0..3: conv.weight, conv.bias, batchnorm.weight, batchnorm.bias; any pointer may
+ *   be NULL): device -> host, synchronous.
+ * ------------------------------------------------------------------------------------------ */
+int axt_head_trainer_input_grad(axt_head_trainer *tr, const float *d_dy, int B, float *d_dfeat, void *stream);
+typedef struct axt_conv_trainer axt_conv_trainer;
+int axt_conv_trainer_create(int Ci, int Co, int H, int W, const float *h_weight, const float *h_bias, const float *h_gamma,
+                            const float *h_beta, const float *h_mean, const float *h_var, int max_batch,
+                            axt_conv_trainer **out);
+void axt_conv_trainer_destroy(axt_conv_trainer *tr);
+size_t axt_conv_trainer_device_bytes(const axt_conv_trainer *tr);
+int axt_conv_trainer_read_weights(const axt_conv_trainer *tr, float *h_weight, float *h_bias, float *h_gamma, float *h_beta);
+int axt_conv_trainer_read_moments(const axt_conv_trainer *tr, int tensor, float *h_m, float *h_v, int64_t *step);
+int axt_conv_trainer_forward(axt_conv_trainer *tr, const float *d_in, const int32_t *d_index, int B, float *d_feat,
+                             void *stream);
+int axt_conv_trainer_step(axt_conv_trainer *tr, const float *d_in, const int32_t *d_index, int B, const float *d_dfeat,
                           double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
 
 /* Training augmentation of a whole timelapse in one launch (data_utils.transform_X: translate, then flip, then rotate;
