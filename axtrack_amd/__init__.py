@@ -19,7 +19,7 @@ from .detections import AxonDetections
 from .hotpath import Detector
 from .render import render_inference
 from .timelapse import Timelapse, estimate_stnd_scaler, load_labels_csv
-from .training import ConvBlockTrainer, HeadTrainer, fine_tune_head, yolo_targets
+from .training import ConvBlockTrainer, ConvStageTrainer, HeadTrainer, fine_tune_head, yolo_targets
 from .augment import (Transform, transform_from_uniforms, draw_transform, augment_frames, transform_labels,
                       pos_label_rate)
 from .segment import (segment_microchannels, flood_initial_mask, segment_mask, save_final_mask,
@@ -27,7 +27,7 @@ from .segment import (segment_microchannels, flood_initial_mask, segment_mask, s
 
 __all__ = ['setup_inference', 'prepare_input_data', 'inference', 'visualize_inference', 'PKG_DIR', 'DEPLOYED_MODEL_DIR',
            '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse', 'render_inference',
-           'ConvBlockTrainer', 'HeadTrainer', 'fine_tune_head', 'yolo_targets',
+           'ConvBlockTrainer', 'ConvStageTrainer', 'HeadTrainer', 'fine_tune_head', 'yolo_targets',
            'prepare_training_data', 'estimate_stnd_scaler', 'load_labels_csv',
            'Transform', 'transform_from_uniforms', 'draw_transform', 'augment_frames', 'transform_labels', 'pos_label_rate',
            'segment_microchannels', 'flood_initial_mask', 'segment_mask', 'save_final_mask', 'otsu_threshold_from_hist']

@@ -117,6 +117,9 @@ SIGNATURES = {
     'axt_conv_trainer_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'axt_conv_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                                       c_double, c_double, c_void_p]),
+    'axt_conv_trainer_input_grad': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'axt_maxpool2_forward': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    'axt_maxpool2_backward': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),
     'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),

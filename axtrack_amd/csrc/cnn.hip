@@ -1878,7 +1878,8 @@ int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
 
 // d_feat != nullptr: stop after conv block 10 and copy its output, the input of the first linear layer, to
 // d_feat [n_items, 40960] (axt_cnn_features_frames); d_yolo is not written then. feat_block = 6: stop one block earlier and
-// copy d_act[6], [n_items, 20480] (axt_cnn_block_features_frames)
+// copy d_act[6], [n_items, 20480]; feat_block = 4: run none of conv blocks 5..7 and copy d_act[4], [n_items, 81920]
+// (axt_cnn_block_features_frames)
 int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, int tstep, int n_items, int n_tiles,
                   const TileList &tl, float *d_yolo, hipStream_t st, float *d_feat = nullptr, int feat_block = 7)
 {
@@ -1895,9 +1896,9 @@ int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, 
             if (rc) return rc;
         }
         if (d_feat) {
-            const int rc = run_back_conv(d, nb, st, feat_block);
+            const int rc = feat_block >= 6 ? run_back_conv(d, nb, st, feat_block) : AXT_OK;
             if (rc) return rc;
-            const size_t per_item = feat_block == 7 ? (size_t)kFeat : (size_t)80 * 16 * 16;
+            const size_t per_item = feat_block == 7 ? (size_t)kFeat : feat_block == 6 ? (size_t)80 * 16 * 16 : (size_t)80 * 32 * 32;
             AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)base * per_item, d->d_act[feat_block], (size_t)nb * per_item * sizeof(float),
                                          hipMemcpyDeviceToDevice, st));
             continue;
@@ -2138,7 +2139,7 @@ int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all,
 int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                                   const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream)
 {
-    AXT_REQUIRE(block == 6 || block == 7, "axt_cnn_block_features_frames: block %d is neither 6 nor 7", block);
+    AXT_REQUIRE(block == 4 || block == 6 || block == 7, "axt_cnn_block_features_frames: block %d is none of 4, 6, 7", block);
     AXT_REQUIRE(det && d_frames && d_feat && h_tile_yx, "null argument");
     AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
     AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",

@@ -21,6 +21,15 @@
 //                    and r exchanged, in ascending r (b, h, w): chains of 16 from zero, their sums added in ascending order.
 //                    The split of r into runs depends on the sizes and B only (plan_wgrad).
 //   conv_adam_w_k    per weight: g = slab[0] + slab[1] + ... in ascending s, then the Adam update of w, m, v in place
+// For a stage of several blocks (conv blocks 5, 6, the max-pool, conv block 7), the gradient handed to the block in front:
+//   conv_dgrad_k     dx[ci][r] = sum_q W[co][ci][ky][kx] dz(q, r) with q = co*9 + ky*3 + kx and dz(q, r) =
+//                    dz[b][co][h-ky+1][w-kx+1], 0 outside the map: conv_fwd_k's product with Co*9 as the depth, the weights
+//                    read transposed and flipped where they lie. dz is formed while staging, from dF, the stashed z and
+//                    gamma as it stands, by conv_bn_back_k's expressions; the same chains of 16 in ascending q. 64 ci x 64 r
+//                    per workgroup. Reads nothing that the step writes except the parameters: it runs before the step.
+//   maxpool2_fwd_k   nn.MaxPool2d(2, 2), one thread per output element
+//   maxpool2_bwd_k   one thread per input element recomputes its window's winner (the first maximum under a strict >) and
+//                    writes the window's gradient or +0.0: every element is written, nothing is scattered
 // Determinism: no atomics; every sum has one fixed order that depends on Ci, Co, H, W and B only.
 #include <algorithm>
 #include <cmath>
@@ -34,6 +43,8 @@ namespace {
 
 constexpr int kMaxB = 64, kMaxC = 512, kMaxHW = 64;     // the limits include/axtrack_hip.h states
 constexpr int TM = 64, TN = 64, TK = 16, TPAD = 68;     // output channels and columns per workgroup, tile depth, LDS pitch
+constexpr int kMaxPoolHW = 32768;                       // the max-pool's limits: a map's side, and the elements of a call
+constexpr int64_t kMaxPoolElems = (int64_t)1 << 38;     // (one thread each, 256 per workgroup, below 2^31 workgroups)
 constexpr float kSlope = 0.1f;
 constexpr double kBnEps = 1e-5;
 
@@ -215,6 +226,112 @@ __global__ __launch_bounds__(256) void conv_adam_w_k(float *__restrict__ W, floa
     W[i] = w; M[i] = m; V[i] = v;
 }
 
+// dz[b][co][h-ky+1][w-kx+1] with q = co*9 + ky*3 + kx, formed from the stashed z and dF by conv_bn_back_k's expressions and
+// from gamma as it stands; (b, h, w) already split; 0 outside the map
+__device__ inline float dz_col(const float *__restrict__ dF, const float *__restrict__ z, int b, const Geom &g, int q, int h,
+                               int w, const float *__restrict__ gamma, const float *__restrict__ beta,
+                               const float *__restrict__ mean, const float *__restrict__ inv_sigma)
+{
+    const int co = q / 9, tap = q - co * 9, ky = tap / 3, kx = tap - ky * 3;
+    const int hh = h - ky + 1, ww = w - kx + 1;
+    if (hh < 0 || hh >= g.H || ww < 0 || ww >= g.W) return 0.f;
+    const size_t o = ((size_t)b * g.Co + co) * g.HW + hh * g.W + ww;
+    const float ga = gamma[co], is = inv_sigma[co];
+    const float fold = ga * is;
+    float zh;
+    const float y = bn_y(z[o], mean[co], is, ga, beta[co], &zh);
+    const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+    return dy * fold;
+}
+
+// grid (r tiles, ci tiles). dx[b][ci][h][w] = sum_q Wt[co][ci][ky][kx] dz[b][co][h-ky+1][w-kx+1] in ascending q = co*9 + ky*3
+// + kx: conv_fwd_k's product with Co*9 as the depth and the weights read transposed and flipped where they lie. dF, z:
+// [B][Co][H*W]; dx: [B][Ci][H*W].
+__global__ __launch_bounds__(256) void conv_dgrad_k(const float *__restrict__ dF, const float *__restrict__ z, int B, Geom g,
+                                                    const float *__restrict__ Wt, const float *__restrict__ gamma,
+                                                    const float *__restrict__ beta, const float *__restrict__ mean,
+                                                    const float *__restrict__ inv_sigma, float *__restrict__ dx)
+{
+    __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // W[co][ci][tap] as [q][ci]
+    __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // dz of the shifted position as [q][r]
+    const int tid = threadIdx.x, tm = tid / 16, tn = tid % 16;
+    const int r0 = blockIdx.x * TN, ci0 = blockIdx.y * TM, R = B * g.HW, K = g.Co * 9;
+    const int rl = tid % TN, r = r0 + rl;
+    const bool r_ok = r < R;
+    const int b = r_ok ? r / g.HW : 0, p = r - b * g.HW, h = p / g.W, w = p - h * g.W;
+    float acc[4][4] = {};
+    for (int q0 = 0; q0 < K; q0 += TK) {
+        for (int i = tid; i < TM * TK; i += 256) {
+            const int k = i % TK, c = i / TK, q = q0 + k, co = q / 9;
+            As[k][c] = (ci0 + c < g.Ci && q < K) ? Wt[((size_t)co * g.Ci + ci0 + c) * 9 + (q - co * 9)] : 0.f;
+        }
+        for (int k = tid / TN; k < TK; k += 256 / TN)
+            Bs[k][rl] = (r_ok && q0 + k < K) ? dz_col(dF, z, b, g, q0 + k, h, w, gamma, beta, mean, inv_sigma) : 0.f;
+        __syncthreads();
+        tile_fma(As, Bs, tm, tn, acc);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int ci = ci0 + tm * 4 + i;
+        if (ci >= g.Ci) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rr = r0 + tn * 4 + j;
+            if (rr >= R) continue;
+            const int bb = rr / g.HW, pp = rr - bb * g.HW;
+            dx[((size_t)bb * g.Ci + ci) * g.HW + pp] = acc[i][j];
+        }
+    }
+}
+
+// the winner of a 2 x 2 window as torch's CPU max_pool2d picks it: the first maximum in the order (0,0), (0,1), (1,0), (1,1)
+// under a strict > (-0.0 and +0.0 tie), a NaN taking over. p: the window's top left element, W: the row pitch.
+__device__ inline int pool_winner(const float *__restrict__ p, int W, float *value)
+{
+    const float v[4] = {p[0], p[1], p[W], p[W + 1]};
+    int win = 0;
+    float m = v[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (v[k] > m || v[k] != v[k]) { m = v[k]; win = k; }
+    *value = m;
+    return win;
+}
+
+// one thread per output element. in [n_maps][H][W], out [n_maps][H/2][W/2].
+__global__ __launch_bounds__(256) void maxpool2_fwd_k(const float *__restrict__ in, size_t n_out, int H, int W,
+                                                      float *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_out) return;
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t n = i / ((size_t)Ho * Wo);
+    const int rem = (int)(i - n * Ho * Wo), ho = rem / Wo, wo = rem - ho * Wo;
+    float m;
+    (void)pool_winner(in + (n * H + 2 * ho) * W + 2 * wo, W, &m);
+    out[i] = m;
+}
+
+// one thread per input element: it recomputes its window's winner and takes the window's gradient if that is itself
+__global__ __launch_bounds__(256) void maxpool2_bwd_k(const float *__restrict__ in, const float *__restrict__ dout,
+                                                      size_t n_in, int H, int W, float *__restrict__ din)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_in) return;
+    const int Ho = H / 2, Wo = W / 2;
+    const size_t n = i / ((size_t)H * W);
+    const int rem = (int)(i - n * H * W), h = rem / W, w = rem - h * W;
+    const int ho = h / 2, wo = w / 2;
+    float g = 0.f;
+    if (ho < Ho && wo < Wo) {                                       // not in a trailing odd row or column
+        float m;
+        const int win = pool_winner(in + (n * H + 2 * ho) * W + 2 * wo, W, &m);
+        if (win == (h - 2 * ho) * 2 + (w - 2 * wo)) g = dout[(n * Ho + ho) * Wo + wo];
+    }
+    din[i] = g;
+}
+
 // split of the reduction over r = B*H*W for the weight gradient: about 1024 workgroups, runs a multiple of the tile depth
 int wgrad_max_split(const Geom &g) { return std::max(1, std::min(64, 1024 / (axt_cdiv(g.K9, TN) * axt_cdiv(g.Co, TM)))); }
 
@@ -377,6 +494,51 @@ int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t 
     AXT_LAUNCH_CHECK();
     const int nw = g.Co * g.K9;
     hipLaunchKernelGGL(conv_adam_w_k, dim3(axt_cdiv(nw, 256)), dim3(256), 0, st, t->w, t->mw, t->vw, nw, t->slab, S, a);
+    AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+// dz is formed while staging and the sums stay in registers: nothing of the handle is written, and nothing is allocated
+int axt_conv_trainer_input_grad(axt_conv_trainer *t, const float *d_dfeat, int B, float *d_dx, void *stream)
+{
+    AXT_REQUIRE(t && d_dfeat && d_dx, "null argument");
+    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_conv_trainer_input_grad: batch %d not in [1,%d]", B, t->max_batch);
+    AXT_REQUIRE(B == t->last_B, "axt_conv_trainer_input_grad: the stashed activations are of a batch of %d, not %d: call "
+                "axt_conv_trainer_forward on this batch first", t->last_B, B);
+    const Geom &g = t->g;
+    const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Ci, TM));
+    hipLaunchKernelGGL(conv_dgrad_k, grid, dim3(256), 0, (hipStream_t)stream, d_dfeat, t->z, B, g, t->w, t->p3 + g.Co,
+                       t->p3 + 2 * g.Co, t->mean, t->inv_sigma, d_dx);
+    AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+int axt_maxpool2_forward(const float *d_in, int64_t n_maps, int H, int W, float *d_out, void *stream)
+{
+    AXT_REQUIRE(d_in && d_out, "null argument");
+    AXT_REQUIRE(H >= 2 && H <= kMaxPoolHW && W >= 2 && W <= kMaxPoolHW, "axt_maxpool2_forward: map %d x %d not in [2,%d]", H, W,
+                kMaxPoolHW);
+    AXT_REQUIRE(n_maps >= 0 && n_maps <= kMaxPoolElems / ((int64_t)H * W), "axt_maxpool2_forward: %lld maps of %d x %d exceed "
+                "%lld elements", (long long)n_maps, H, W, (long long)kMaxPoolElems);
+    if (n_maps == 0) return AXT_OK;
+    const size_t n_out = (size_t)n_maps * (H / 2) * (W / 2);
+    hipLaunchKernelGGL(maxpool2_fwd_k, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_in, n_out, H,
+                       W, d_out);
+    AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+int axt_maxpool2_backward(const float *d_in, const float *d_dout, int64_t n_maps, int H, int W, float *d_din, void *stream)
+{
+    AXT_REQUIRE(d_in && d_dout && d_din, "null argument");
+    AXT_REQUIRE(H >= 2 && H <= kMaxPoolHW && W >= 2 && W <= kMaxPoolHW, "axt_maxpool2_backward: map %d x %d not in [2,%d]", H,
+                W, kMaxPoolHW);
+    AXT_REQUIRE(n_maps >= 0 && n_maps <= kMaxPoolElems / ((int64_t)H * W), "axt_maxpool2_backward: %lld maps of %d x %d exceed "
+                "%lld elements", (long long)n_maps, H, W, (long long)kMaxPoolElems);
+    if (n_maps == 0) return AXT_OK;
+    const size_t n_in = (size_t)n_maps * H * W;
+    hipLaunchKernelGGL(maxpool2_bwd_k, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_in, d_dout,
+                       n_in, H, W, d_din);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
 }

@@ -11,7 +11,8 @@ from . import _lib
 
 TILE, S, CELLS = 512, 12, 144
 FEATURES = 160 * 16 * 16                # what the first linear layer reads per tile (model.py:50-53)
-BLOCK_FEATURES = {7: FEATURES, 6: 80 * 16 * 16}      # Detector.features_frames(block=): floats per item after conv block 7 / 6
+# Detector.features_frames(block=): floats per item after conv block 7 / 6 / 4
+BLOCK_FEATURES = {7: FEATURES, 6: 80 * 16 * 16, 4: 80 * 32 * 32}
 CONF_FLOOR = float(np.float32(0.55))   # all_conf_thrs.min() as f32 (AxonDetections.py:76,122)
 MAX_PX_ASSOC_DIST = 500                # AxonDetections.py:77
 AXON_BOX_SIZE = 70                     # AxonDetections.py:78
@@ -29,6 +30,15 @@ def _require_gpu():
 # ConvBlock_i modules of the deployed ARCHITECTURE that hold a convolution (blocks 3, 6, 9 are the max-pools;
 # deployed_model/params.txt:34, model.py:85-103)
 CONV_BLOCKS = (0, 1, 2, 4, 5, 7, 8, 10)
+# per conv block 0..7 of the package's numbering: the side of the square map its convolution writes, and whether one of the
+# max-pools follows it (training.ConvStageTrainer takes keys and sizes from here)
+CONV_MAP_SIDE = (256, 128, 128, 64, 64, 32, 32, 16)
+CONV_POOLED = (False, False, True, False, True, False, True, False)
+
+
+def conv_block_key(i):
+    """State-dict prefix of conv block i of the package's numbering (0..7)."""
+    return f'ConvNet.ConvBlock_{CONV_BLOCKS[i]}'
 
 
 def state_dict_tensor_order():
@@ -169,7 +179,8 @@ class Detector:
         What training.HeadTrainer trains on. out: a contiguous f32 table of at least that many rows to write into (its
         first n_frames * n_tiles rows are returned) instead of a new one. block=6: the trunk one conv block earlier,
         [n_frames * n_tiles, 20480] = [item, 80, 16, 16], what training.ConvBlockTrainer reads
-        (axt_cnn_block_features_frames); block=7 is the default table."""
+        (axt_cnn_block_features_frames); block=4: three conv blocks earlier, [n_frames * n_tiles, 81920] = [item, 80, 32, 32],
+        what training.ConvStageTrainer reads; block=7 is the default table."""
         if block not in BLOCK_FEATURES:
             raise ValueError(f'block must be one of {sorted(BLOCK_FEATURES)}, got {block}')
         width = BLOCK_FEATURES[block]

@@ -12,7 +12,12 @@ recomputed from the warped frames, which costs about one trunk pass per epoch.
 fine_tune_head(train_last_conv=True) trains the last convolutional block (ConvNet.ConvBlock_10) jointly with the head
 (ConvBlockTrainer, csrc/train_conv.hip): the cached table is then the trunk's output one block earlier, and a step runs the
 block's forward pass in training form, the head, the loss, the head's input gradient, and both Adam updates. BatchNorm
-keeps its running statistics, as at inference. Conv blocks 0-6 stay frozen."""
+keeps its running statistics, as at inference. Conv blocks 0-6 stay frozen.
+
+fine_tune_head(train_conv_blocks=3) trains the whole last conv stage (ConvStageTrainer: conv blocks 5 and 6, the 2 x 2
+max-pool, conv block 7) from the table three blocks earlier: the blocks' input gradients (axt_conv_trainer_input_grad) and
+the pool's gradient (axt_maxpool2_backward) carry the head's input gradient back through the stage. Conv blocks 0-4 stay
+frozen."""
 import ctypes
 import os
 
@@ -301,6 +306,17 @@ class ConvBlockTrainer:
                                                        ADAM_BETAS[1], float(eps), float(P['WEIGHT_DECAY']), _stream()),
                        'axt_conv_trainer_step')
 
+    def input_grad(self, dfeat):
+        """The gradient of the loss with respect to the input rows the last forward() read: dfeat [B, Co*H*W] ->
+        [B, Ci*H*W] (axt_conv_trainer_input_grad). From gamma and the weights as they stand, so call it before step(); it
+        changes nothing that step() reads."""
+        self._check_table(dfeat, self.out_width, 'dfeat')
+        out = torch.empty((dfeat.shape[0], self.in_width), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_input_grad(self._h, dfeat.data_ptr(), dfeat.shape[0], out.data_ptr(),
+                                                             _stream()), 'axt_conv_trainer_input_grad')
+        return out
+
     def _shapes(self):
         return [(self.Co, self.Ci, 3, 3), (self.Co,), (self.Co,), (self.Co,)]
 
@@ -327,6 +343,131 @@ class ConvBlockTrainer:
         f32); the running statistics and num_batches_tracked pass through."""
         sd = dict(self._sd if base is None else base)
         sd.update(zip(self.keys[:4], self.weights()))
+        return sd
+
+
+def _check_maps(x, H, W, what):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+            and x.numel() % (H * W) == 0):
+        raise ValueError(f'{what} must be a contiguous f32 tensor of whole {H} x {W} maps on the GPU')
+    return x.numel() // (H * W)
+
+
+def maxpool2_forward(x, H, W):
+    """nn.MaxPool2d(2, 2) on every H x W map of x (f32 on the GPU, any leading shape, H*W innermost) -> a flat tensor of
+    the [H//2, W//2] maps in the same order (axt_maxpool2_forward)."""
+    n = _check_maps(x, H, W, 'x')
+    out = torch.empty(n * (H // 2) * (W // 2), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().axt_maxpool2_forward(x.data_ptr(), n, int(H), int(W), out.data_ptr(), _stream()),
+                   'axt_maxpool2_forward')
+    return out
+
+
+def maxpool2_backward(x, dout, H, W):
+    """The gradient of maxpool2_forward(x, H, W) with respect to x from dout, the gradient with respect to its output: each
+    window's gradient goes to its first maximum (torch's choice on the CPU), every other element is +0.0
+    (axt_maxpool2_backward) -> a tensor shaped like x."""
+    n = _check_maps(x, H, W, 'x')
+    if _check_maps(dout, max(H // 2, 1), max(W // 2, 1), 'dout') != n or dout.device != x.device:
+        raise ValueError(f'dout does not hold the {n} pooled maps of x')
+    din = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().axt_maxpool2_backward(x.data_ptr(), dout.data_ptr(), n, int(H), int(W), din.data_ptr(),
+                                                     _stream()), 'axt_maxpool2_backward')
+    return din
+
+
+STAGE_BLOCKS = (5, 6, 7)                            # the last conv stage: conv blocks 5 and 6, the max-pool, conv block 7
+
+
+class ConvStageTrainer:
+    """The last conv stage of the state dict -- conv block 5, conv block 6, the 2 x 2 max-pool, conv block 7 -- as three
+    ConvBlockTrainers chained on the device, of which the last `depth` (1..3) are trained; a block in front of them runs
+    forward only and never steps. forward / backward_and_step work on batches picked by index from a table
+    [n_items, Ci*H*W] of the stage's inputs (Detector.features_frames(block=4)); forward's output is what
+    HeadTrainer.forward reads. block_keys, map_size: the three blocks' state-dict prefixes and the (H, W) of the maps the
+    first two run on (the third runs on the pooled (H // 2, W // 2)); default: the deployed architecture's, from
+    hotpath's table of conv blocks."""
+
+    def __init__(self, state_dict, depth=3, parameters=None, max_batch=64, device='cuda:0', block_keys=None, map_size=None):
+        from .hotpath import CONV_MAP_SIDE, CONV_POOLED, conv_block_key
+        if depth not in (1, 2, 3):
+            raise ValueError(f'depth must be 1, 2 or 3, got {depth!r}')
+        if block_keys is None:
+            assert [CONV_POOLED[i] for i in STAGE_BLOCKS] == [False, True, False]
+            block_keys = [conv_block_key(i) for i in STAGE_BLOCKS]
+            map_size = (CONV_MAP_SIDE[STAGE_BLOCKS[0]],) * 2
+        if len(block_keys) != 3 or map_size is None:
+            raise ValueError('a stage is three blocks (block_keys) on maps of map_size = (H, W)')
+        self.depth = int(depth)
+        self.H, self.W = (int(v) for v in map_size)
+        if self.H < 2 or self.W < 2:
+            raise ValueError(f'maps of {self.H} x {self.W} leave the max-pool nothing')
+        sizes = [(self.H, self.W), (self.H, self.W), (self.H // 2, self.W // 2)]
+        self.blocks = [ConvBlockTrainer(state_dict, k, parameters, map_size=s, max_batch=max_batch, device=device)
+                       for k, s in zip(block_keys, sizes)]
+        for a, b in zip(self.blocks, self.blocks[1:]):
+            if a.Co != b.Ci:
+                raise ValueError(f'{a.block_key} writes {a.Co} channels, {b.block_key} reads {b.Ci}')
+        self.trained = [i >= 3 - self.depth for i in range(3)]
+        self.device, self.max_batch = self.blocks[0].device, int(max_batch)
+        self.in_width, self.out_width = self.blocks[0].in_width, self.blocks[2].out_width
+        self._sd = state_dict
+        self._rows = {}                                 # batch size -> rows 0..B-1 on the device
+        self._kept = None
+
+    @property
+    def device_bytes(self):
+        return sum(b.device_bytes for b in self.blocks)
+
+    def _identity(self, B):
+        if B not in self._rows:
+            self._rows[B] = torch.arange(B, dtype=torch.int32, device=self.device)
+        return self._rows[B]
+
+    def forward(self, table, batch=None):
+        """table f32 [n_items, Ci*H*W] on the GPU, batch: which rows (default: all) -> [B, Co*(H//2)*(W//2)], the head's
+        input rows. The outputs in between are kept for backward_and_step."""
+        b5, b6, b7 = self.blocks
+        f5 = b5.forward(table, batch)
+        rows = self._identity(f5.shape[0])
+        f6 = b6.forward(f5, rows)
+        pooled = maxpool2_forward(f6, self.H, self.W).reshape(f5.shape[0], b7.in_width)
+        f7 = b7.forward(pooled, rows)
+        self._kept = (f5, f6, pooled, f7)
+        return f7
+
+    def backward_and_step(self, table, batch, dfeat, lr=None, eps=ADAM_EPS):
+        """From dfeat [B, out_width], the gradient with respect to forward's output of the same batch
+        (HeadTrainer.input_grad): back to front, per trained block its input gradient where a trained block lies in front
+        of it, the pool's gradient between conv blocks 7 and 6, then the block's Adam step -- so every gradient is taken
+        from weights that have not moved yet. Returns the gradients handed on: {'pooled', 'f6', 'f5'} where formed."""
+        if self._kept is None or self._kept[3].shape[0] != dfeat.shape[0]:
+            raise ValueError('backward_and_step needs forward() on this batch first')
+        b5, b6, b7 = self.blocks
+        f5, f6, pooled, _ = self._kept
+        rows = self._identity(dfeat.shape[0])
+        grads = {}
+        if self.trained[1]:
+            grads['pooled'] = b7.input_grad(dfeat)
+        b7.step(pooled, rows, dfeat, lr=lr, eps=eps)
+        if self.trained[1]:
+            grads['f6'] = maxpool2_backward(f6, grads['pooled'], self.H, self.W)
+            if self.trained[0]:
+                grads['f5'] = b6.input_grad(grads['f6'])
+            b6.step(f5, rows, grads['f6'], lr=lr, eps=eps)
+        if self.trained[0]:
+            b5.step(table, batch, grads['f5'], lr=lr, eps=eps)
+        return grads
+
+    def state_dict(self, base=None):
+        """The state dict this stage was built from (or `base`) with the trained blocks' four tensors each replaced
+        (numpy f32); everything else, a forward-only block's tensors included, passes through."""
+        sd = dict(self._sd if base is None else base)
+        for blk, trained in zip(self.blocks, self.trained):
+            if trained:
+                sd = blk.state_dict(sd)
         return sd
 
 
@@ -384,7 +525,7 @@ def _epoch_metrics(sd, timelapse, labels, parameters, subset):
 
 def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
                    use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
-                   metrics_every=10, train_last_conv=False):
+                   metrics_every=10, train_conv_blocks=None, train_last_conv=False):
     """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
     one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
     (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
@@ -412,10 +553,28 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
     batchnorm.weight, batchnorm.bias; BatchNorm keeps its running statistics, as at inference) with the same learning
     rate, Adam eps and weight decay. The cached table is then the trunk's output one block earlier
     (Detector.features_frames(block=6)), and a step is conv forward, head forward, loss, the head's input gradient, conv
-    step, head step. The returned state dict and the checkpoints carry both sets of tensors."""
+    step, head step. The returned state dict and the checkpoints carry both sets of tensors.
+
+    train_conv_blocks: how many of the last conv blocks to train with the head, 0..3 (None: 1 with train_last_conv, else
+    0; train_last_conv=True with another number than 1 is a ValueError). 0 is the head alone, 1 is train_last_conv. 3
+    trains the whole last stage (ConvStageTrainer: conv blocks 5 and 6 on 32 x 32 maps, the max-pool, conv block 7) on the
+    cached table Detector.features_frames(block=4); a step is the three forwards with the pool, head forward, loss, the
+    head's input gradient, then back to front each block's input gradient, the pool's gradient and the block's step, and
+    the head's step. 2 reads the same table (conv block 5's output is not offered as one) and runs conv block 5 forward
+    only: its tensors come back as they went in. Every trained block takes the head's learning rate, Adam eps and weight
+    decay and keeps its running statistics. Conv blocks 0-4 stay frozen."""
     import pandas as pd
     from .hotpath import Detector, BLOCK_FEATURES
-    block = 6 if train_last_conv else 7                 # which conv block's output the cached table holds
+    if train_conv_blocks is None:
+        depth = 1 if train_last_conv else 0
+    else:
+        if isinstance(train_conv_blocks, bool) or train_conv_blocks not in (0, 1, 2, 3):
+            raise ValueError(f'train_conv_blocks must be 0, 1, 2 or 3, got {train_conv_blocks!r}')
+        depth = int(train_conv_blocks)
+        if train_last_conv and depth != 1:
+            raise ValueError(f'train_last_conv=True means train_conv_blocks=1, not {depth}')
+    train_last_conv = depth == 1
+    block = (7, 6, 4, 4)[depth]                         # which conv block's output the cached table holds
     for tl in (timelapse, test_timelapse):
         if getattr(tl, 'frame_sharded', False):
             raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
@@ -470,8 +629,10 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
     conv = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device) if train_last_conv else None
-    # the state dict of this moment: the head's tensors, and the conv block's where it is trained
-    current = (lambda: conv.state_dict(trainer.state_dict())) if train_last_conv else trainer.state_dict
+    stage = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device) if depth >= 2 else None
+    # the state dict of this moment: the head's tensors, and the conv blocks' where they are trained
+    current = ((lambda: stage.state_dict(trainer.state_dict())) if stage else
+               (lambda: conv.state_dict(trainer.state_dict())) if train_last_conv else trainer.state_dict)
     identity = {}                                       # batch size -> rows 0..B-1 on the device: the head reads conv.forward's output
     rng = np.random.default_rng(seed)
     checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
@@ -487,7 +648,17 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         lr = learning_rate(P['LR'], P['LR_DECAYRATE'], epoch)
         rows = []
         for batch in epoch_batches(features.shape[0], bs, P['SHUFFLE'], P['DROP_LAST'], rng):
-            if train_last_conv:
+            if stage:
+                feats = stage.forward(features, batch)
+                if len(batch) not in identity:
+                    identity[len(batch)] = torch.arange(len(batch), dtype=torch.int32, device=trainer.device)
+                rows_all = identity[len(batch)]
+                yolo = trainer.forward(feats, rows_all)
+                comp, dy = trainer.loss(yolo, targets, batch)
+                dfeat = trainer.input_grad(dy)              # from the head's weights before they move
+                stage.backward_and_step(features, batch, dfeat, lr=lr)
+                trainer.step(feats, rows_all, dy, lr=lr)
+            elif train_last_conv:
                 feats = conv.forward(features, batch)
                 if len(batch) not in identity:
                     identity[len(batch)] = torch.arange(len(batch), dtype=torch.int32, device=trainer.device)
