@@ -118,6 +118,8 @@ SIGNATURES = {
     'axt_conv_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                                       c_double, c_double, c_void_p]),
     'axt_conv_trainer_input_grad': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'axt_conv_trainer_set_batch_stats': (c_int, [c_void_p, c_int, c_double]),
+    'axt_conv_trainer_read_stats': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_void_p]),
     'axt_maxpool2_forward': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     'axt_maxpool2_backward': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),

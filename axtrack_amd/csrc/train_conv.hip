@@ -1,8 +1,9 @@
 // train_conv.hip -- fine-tuning of one convolutional block (Conv2d 3x3 pad 1 + BatchNorm2d + LeakyReLU(0.1), model.py:5-18)
 // together with the linear head of train.hip: the block's forward pass in training form (unfolded BatchNorm, f32, the
 // weights change every step), its backward pass from the head's input gradient, and torch.optim.Adam with L2 weight decay
-// on conv.weight, conv.bias, batchnorm.weight and batchnorm.bias. BatchNorm uses its running statistics, which are never
-// updated. DESIGN.md 6.8e.
+// on conv.weight, conv.bias, batchnorm.weight and batchnorm.bias. BatchNorm uses its running statistics and leaves them
+// alone, or, after axt_conv_trainer_set_batch_stats, the statistics of each batch as nn.BatchNorm2d does in train mode (the
+// kernels at the end of the list). DESIGN.md 6.8e.
 //
 // Both products run over the im2col matrix X(q, r) of the batch, never stored:
 //   q = ci*9 + ky*3 + kx (the order of conv.weight's last three dimensions), r = b*H*W + h*W + w,
@@ -30,6 +31,17 @@
 //   maxpool2_fwd_k   nn.MaxPool2d(2, 2), one thread per output element
 //   maxpool2_bwd_k   one thread per input element recomputes its window's winner (the first maximum under a strict >) and
 //                    writes the window's gradient or +0.0: every element is written, nothing is scattered
+// Batch statistics (train-mode BatchNorm), n = B*H*W elements per channel, one workgroup per output channel each:
+//   bn_batch_fwd_k   from the z that conv_fwd_k stashed: mu = sum z / n, then var = sum (z - mu)^2 / n in a second pass (never
+//                    E[z^2] - mu^2), inv = 1 / sqrt(var + 1e-5); running_mean and running_var move by the momentum (var
+//                    times n / (n - 1)), and the eval-mode 1 / sqrt(running_var + 1e-5) follows; a third pass overwrites F
+//                    with leaky(bn_y(z, mu, inv, gamma, beta)).
+//   bn_batch_back_k  pass 1: dbeta = sum dy, dgamma = sum dy zhat with dy and zhat from bn_y on (mu, inv); pass 2:
+//                    dz = gamma inv (dy - dbeta / n - zhat dgamma / n) into the dz buffer. With kAdam: Adam on gamma and
+//                    beta, and on conv.bias with the gradient 0 that sum dz is by definition. Without: dz only, for
+//   conv_dgrad_dz_k  conv_dgrad_k's product with the staged dz read from the dz buffer instead of formed from dF.
+//                    The sums follow conv_bn_back_k: thread t takes r = t, t + 256, ..., the 256 partial sums meet in a
+//                    fixed binary tree.
 // Determinism: no atomics; every sum has one fixed order that depends on Ci, Co, H, W and B only.
 #include <algorithm>
 #include <cmath>
@@ -332,6 +344,150 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_k(const float *__restrict__ 
     din[i] = g;
 }
 
+// ---- batch statistics (train-mode BatchNorm) ----
+// the sum of v over the workgroup's 256 threads in a fixed binary tree, handed to every thread
+__device__ inline float sum256(float v, float *red, int tid)
+{
+    red[tid] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    const float s = red[0];
+    __syncthreads();
+    return s;
+}
+
+struct BnUpdate { float one_minus_m, m, unbias; };             // formed in f64 on the host and rounded once
+
+// grid (Co). z, F: [B][Co][H*W]. stats [3][Co]: the batch's mean, biased variance and 1 / sqrt(var + eps). Moves
+// running_mean and running_var, and run_inv = 1 / sqrt(running_var + eps) for the eval-mode kernels with them.
+__global__ __launch_bounds__(256) void bn_batch_fwd_k(const float *__restrict__ z, int B, Geom g,
+                                                      const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                      float *__restrict__ run_mean, float *__restrict__ run_var,
+                                                      float *__restrict__ run_inv, float *__restrict__ stats, BnUpdate u,
+                                                      float *__restrict__ F)
+{
+    __shared__ float red[256];
+    const int tid = threadIdx.x, co = blockIdx.x, n = B * g.HW;
+    float s = 0.f;
+    for (int r = tid; r < n; r += 256) {                               // r = b*H*W + p: thread t takes r = t, t + 256, ...
+        const int b = r / g.HW, p = r - b * g.HW;
+        s += z[((size_t)b * g.Co + co) * g.HW + p];
+    }
+    const float mu = __fdiv_rn(sum256(s, red, tid), (float)n);
+    s = 0.f;
+    for (int r = tid; r < n; r += 256) {
+        const int b = r / g.HW, p = r - b * g.HW;
+        const float d = __fsub_rn(z[((size_t)b * g.Co + co) * g.HW + p], mu);
+        s = fmaf(d, d, s);
+    }
+    const float var = __fdiv_rn(sum256(s, red, tid), (float)n);
+    const float inv = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(var, (float)kBnEps)));
+    if (tid == 0) {
+        stats[co] = mu;
+        stats[g.Co + co] = var;
+        stats[2 * g.Co + co] = inv;
+        run_mean[co] = __fadd_rn(__fmul_rn(u.one_minus_m, run_mean[co]), __fmul_rn(u.m, mu));
+        const float rv = __fadd_rn(__fmul_rn(u.one_minus_m, run_var[co]), __fmul_rn(u.m, __fmul_rn(var, u.unbias)));
+        run_var[co] = rv;
+        run_inv[co] = (float)(1.0 / sqrt((double)rv + kBnEps));
+    }
+    const float ga = gamma[co], be = beta[co];
+    for (int r = tid; r < n; r += 256) {
+        const int b = r / g.HW, p = r - b * g.HW;
+        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        float zh;
+        const float y = bn_y(z[o], mu, inv, ga, be, &zh);
+        F[o] = y > 0.f ? y : kSlope * y;
+    }
+}
+
+// grid (Co). dF, z, dz: [B][Co][H*W]; stats as bn_batch_fwd_k wrote it. kAdam: updates bias, gamma, beta and their moments
+// (p, m, v: [3][Co] in that order) as conv_bn_back_k does, bias with the gradient 0.
+template <bool kAdam>
+__global__ __launch_bounds__(256) void bn_batch_back_k(const float *__restrict__ dF, const float *__restrict__ z, int B, Geom g,
+                                                       float *__restrict__ bias, float *__restrict__ gamma,
+                                                       float *__restrict__ beta, const float *__restrict__ stats,
+                                                       float *__restrict__ mom_m, float *__restrict__ mom_v,
+                                                       float *__restrict__ dz, AdamArgs a)
+{
+    __shared__ float red[256];
+    const int tid = threadIdx.x, co = blockIdx.x, n = B * g.HW;
+    const float ga = gamma[co], be = beta[co], mu = stats[co], is = stats[2 * g.Co + co];
+    const float fold = ga * is;
+    float s_gamma = 0.f, s_beta = 0.f;
+    for (int r = tid; r < n; r += 256) {
+        const int b = r / g.HW, p = r - b * g.HW;
+        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        float zh;
+        const float y = bn_y(z[o], mu, is, ga, be, &zh);
+        const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+        s_gamma = fmaf(dy, zh, s_gamma);
+        s_beta += dy;
+    }
+    const float dgamma = sum256(s_gamma, red, tid), dbeta = sum256(s_beta, red, tid);
+    const float mg = __fdiv_rn(dgamma, (float)n), mb = __fdiv_rn(dbeta, (float)n);
+    for (int r = tid; r < n; r += 256) {
+        const int b = r / g.HW, p = r - b * g.HW;
+        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        float zh;
+        const float y = bn_y(z[o], mu, is, ga, be, &zh);
+        const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+        dz[o] = fold * ((dy - mb) - zh * mg);
+    }
+    if (kAdam && tid < 3) {                                            // every thread has read gamma and beta by now
+        float *param = tid == 0 ? bias : tid == 1 ? gamma : beta;
+        float w = param[co], m = mom_m[tid * g.Co + co], v = mom_v[tid * g.Co + co];
+        adam1(tid == 0 ? 0.f : tid == 1 ? dgamma : dbeta, w, m, v, a);
+        param[co] = w;
+        mom_m[tid * g.Co + co] = m;
+        mom_v[tid * g.Co + co] = v;
+    }
+}
+
+// grid (r tiles, ci tiles). conv_dgrad_k with dz(q, r) = dz[b][co][h-ky+1][w-kx+1] read from the dz buffer, 0 outside the map.
+__global__ __launch_bounds__(256) void conv_dgrad_dz_k(const float *__restrict__ dz, int B, Geom g,
+                                                       const float *__restrict__ Wt, float *__restrict__ dx)
+{
+    __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // W[co][ci][tap] as [q][ci]
+    __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // dz of the shifted position as [q][r]
+    const int tid = threadIdx.x, tm = tid / 16, tn = tid % 16;
+    const int r0 = blockIdx.x * TN, ci0 = blockIdx.y * TM, R = B * g.HW, K = g.Co * 9;
+    const int rl = tid % TN, r = r0 + rl;
+    const bool r_ok = r < R;
+    const int b = r_ok ? r / g.HW : 0, p = r - b * g.HW, h = p / g.W, w = p - h * g.W;
+    float acc[4][4] = {};
+    for (int q0 = 0; q0 < K; q0 += TK) {
+        for (int i = tid; i < TM * TK; i += 256) {
+            const int k = i % TK, c = i / TK, q = q0 + k, co = q / 9;
+            As[k][c] = (ci0 + c < g.Ci && q < K) ? Wt[((size_t)co * g.Ci + ci0 + c) * 9 + (q - co * 9)] : 0.f;
+        }
+        for (int k = tid / TN; k < TK; k += 256 / TN) {
+            const int q = q0 + k, co = q / 9, tap = q - co * 9, ky = tap / 3, kx = tap - ky * 3;
+            const int hh = h - ky + 1, ww = w - kx + 1;
+            const bool ok = r_ok && q < K && hh >= 0 && hh < g.H && ww >= 0 && ww < g.W;
+            Bs[k][rl] = ok ? dz[((size_t)b * g.Co + co) * g.HW + hh * g.W + ww] : 0.f;
+        }
+        __syncthreads();
+        tile_fma(As, Bs, tm, tn, acc);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int ci = ci0 + tm * 4 + i;
+        if (ci >= g.Ci) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rr = r0 + tn * 4 + j;
+            if (rr >= R) continue;
+            const int bb = rr / g.HW, pp = rr - bb * g.HW;
+            dx[((size_t)bb * g.Ci + ci) * g.HW + pp] = acc[i][j];
+        }
+    }
+}
+
 // split of the reduction over r = B*H*W for the weight gradient: about 1024 workgroups, runs a multiple of the tile depth
 int wgrad_max_split(const Geom &g) { return std::max(1, std::min(64, 1024 / (axt_cdiv(g.K9, TN) * axt_cdiv(g.Co, TM)))); }
 
@@ -356,6 +512,12 @@ struct axt_conv_trainer {
     int last_B = 0;
     size_t bytes = 0;
     std::vector<void *> allocs;
+    // batch statistics (axt_conv_trainer_set_batch_stats): the device buffers exist from the first switch on
+    bool batch_stats = false, last_batch_stats = false;
+    double momentum = 0.1;
+    int64_t forwards = 0;                                   // forwards in batch mode: what num_batches_tracked grows by
+    std::vector<float> var0;                                // running_var as created, until run_var takes over
+    float *run_var = nullptr, *bstats = nullptr;            // [Co]; [3][Co]: the last batch's mean, biased variance, inv
 };
 
 namespace {
@@ -401,6 +563,7 @@ int axt_conv_trainer_create(int Ci, int Co, int H, int W, const float *h_weight,
     }
     t->g = Geom{Ci, Co, H, W, H * W, Ci * 9};
     t->max_batch = max_batch;
+    t->var0.assign(h_var, h_var + Co);
     const size_t nw = (size_t)Co * Ci * 9, nz = (size_t)max_batch * Co * H * W;
     std::vector<float> p3((size_t)3 * Co), is(Co);
     for (int c = 0; c < Co; ++c) {
@@ -462,11 +625,23 @@ int axt_conv_trainer_forward(axt_conv_trainer *t, const float *d_in, const int32
     AXT_REQUIRE(t && d_in && d_feat, "null argument");
     AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_conv_trainer_forward: batch %d not in [1,%d]", B, t->max_batch);
     const Geom &g = t->g;
+    const int n = B * g.HW;
+    AXT_REQUIRE(!t->batch_stats || n >= 2, "axt_conv_trainer_forward: batch statistics need more than %d value per channel "
+                "(B * H * W >= 2)", n);
     const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Co, TM));
     hipLaunchKernelGGL(conv_fwd_k, grid, dim3(256), 0, (hipStream_t)stream, d_in, d_index, B, g, t->w, t->p3, t->p3 + g.Co,
                        t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->z, d_feat);
     AXT_LAUNCH_CHECK();
+    if (t->batch_stats) {
+        const double m = t->momentum;
+        const BnUpdate u = {(float)(1.0 - m), (float)m, (float)((double)n / (n - 1))};
+        hipLaunchKernelGGL(bn_batch_fwd_k, dim3(g.Co), dim3(256), 0, (hipStream_t)stream, t->z, B, g, t->p3 + g.Co,
+                           t->p3 + 2 * g.Co, t->mean, t->run_var, t->inv_sigma, t->bstats, u, d_feat);
+        AXT_LAUNCH_CHECK();
+        t->forwards += 1;
+    }
     t->last_B = B;
+    t->last_batch_stats = t->batch_stats;
     return AXT_OK;
 }
 
@@ -484,8 +659,12 @@ int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t 
     t->step += 1;
     const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, t->step);
     // dz from gamma as it stands: each workgroup reads its channel's gamma before it updates it
-    hipLaunchKernelGGL(conv_bn_back_k, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
-                       t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->m3, t->v3, t->dz, a);
+    if (t->last_batch_stats)
+        hipLaunchKernelGGL(bn_batch_back_k<true>, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
+                           t->p3 + 2 * g.Co, t->bstats, t->m3, t->v3, t->dz, a);
+    else
+        hipLaunchKernelGGL(conv_bn_back_k, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
+                           t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->m3, t->v3, t->dz, a);
     AXT_LAUNCH_CHECK();
     int S, rchunk;
     plan_wgrad(g, B, &S, &rchunk);
@@ -507,9 +686,56 @@ int axt_conv_trainer_input_grad(axt_conv_trainer *t, const float *d_dfeat, int B
                 "axt_conv_trainer_forward on this batch first", t->last_B, B);
     const Geom &g = t->g;
     const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Ci, TM));
+    if (t->last_batch_stats) {
+        // batch form: dz goes through the handle's dz buffer, which _step writes again with the same values from the same
+        // inputs; the parameters and the moments are left alone
+        hipLaunchKernelGGL(bn_batch_back_k<false>, dim3(g.Co), dim3(256), 0, (hipStream_t)stream, d_dfeat, t->z, B, g, t->p3,
+                           t->p3 + g.Co, t->p3 + 2 * g.Co, t->bstats, t->m3, t->v3, t->dz, AdamArgs{});
+        AXT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(conv_dgrad_dz_k, grid, dim3(256), 0, (hipStream_t)stream, t->dz, B, g, t->w, d_dx);
+        AXT_LAUNCH_CHECK();
+        return AXT_OK;
+    }
     hipLaunchKernelGGL(conv_dgrad_k, grid, dim3(256), 0, (hipStream_t)stream, d_dfeat, t->z, B, g, t->w, t->p3 + g.Co,
                        t->p3 + 2 * g.Co, t->mean, t->inv_sigma, d_dx);
     AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+int axt_conv_trainer_set_batch_stats(axt_conv_trainer *t, int on, double momentum)
+{
+    AXT_REQUIRE(t, "null argument");
+    AXT_REQUIRE(momentum > 0 && momentum <= 1, "axt_conv_trainer_set_batch_stats: momentum %g not in (0,1]", momentum);
+    if (on && !t->run_var) {
+        const size_t Co = t->g.Co;
+        float *rv = nullptr, *bs = nullptr;
+        int rc;
+        if ((rc = ct_alloc(t, &rv, Co, false)) || (rc = ct_alloc(t, &bs, 3 * Co, true))) return rc;
+        AXT_CHECK_HIP(hipMemcpy(rv, t->var0.data(), Co * sizeof(float), hipMemcpyHostToDevice));
+        t->run_var = rv;
+        t->bstats = bs;
+    }
+    t->batch_stats = on != 0;
+    t->momentum = momentum;
+    return AXT_OK;
+}
+
+int axt_conv_trainer_read_stats(const axt_conv_trainer *t, float *h_running_mean, float *h_running_var,
+                                int64_t *num_batches_tracked, float *h_batch_mean, float *h_batch_var)
+{
+    AXT_REQUIRE(t, "null argument");
+    AXT_REQUIRE(t->forwards > 0 || (!h_batch_mean && !h_batch_var), "axt_conv_trainer_read_stats: no forward has run with "
+                "batch statistics yet");
+    const size_t nc = (size_t)t->g.Co * sizeof(float);
+    AXT_CHECK_HIP(hipDeviceSynchronize());
+    if (h_running_mean) AXT_CHECK_HIP(hipMemcpy(h_running_mean, t->mean, nc, hipMemcpyDeviceToHost));
+    if (h_running_var) {
+        if (t->run_var) AXT_CHECK_HIP(hipMemcpy(h_running_var, t->run_var, nc, hipMemcpyDeviceToHost));
+        else std::copy(t->var0.begin(), t->var0.end(), h_running_var);
+    }
+    if (num_batches_tracked) *num_batches_tracked = t->forwards;
+    if (h_batch_mean) AXT_CHECK_HIP(hipMemcpy(h_batch_mean, t->bstats, nc, hipMemcpyDeviceToHost));
+    if (h_batch_var) AXT_CHECK_HIP(hipMemcpy(h_batch_var, t->bstats + t->g.Co, nc, hipMemcpyDeviceToHost));
     return AXT_OK;
 }
 

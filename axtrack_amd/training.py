@@ -12,7 +12,9 @@ recomputed from the warped frames, which costs about one trunk pass per epoch.
 fine_tune_head(train_last_conv=True) trains the last convolutional block (ConvNet.ConvBlock_10) jointly with the head
 (ConvBlockTrainer, csrc/train_conv.hip): the cached table is then the trunk's output one block earlier, and a step runs the
 block's forward pass in training form, the head, the loss, the head's input gradient, and both Adam updates. BatchNorm
-keeps its running statistics, as at inference. Conv blocks 0-6 stay frozen.
+keeps its running statistics, as at inference, unless bn_batch_stats=True asks for train-mode BatchNorm: every trained
+block then normalises a batch with that batch's own mean and variance, its gradients go through them, and running_mean,
+running_var and num_batches_tracked move as nn.BatchNorm2d moves them. Conv blocks 0-6 stay frozen.
 
 fine_tune_head(train_conv_blocks=3) trains the whole last conv stage (ConvStageTrainer: conv blocks 5 and 6, the 2 x 2
 max-pool, conv block 7) from the table three blocks earlier: the blocks' input gradients (axt_conv_trainer_input_grad) and
@@ -233,7 +235,8 @@ class HeadTrainer:
 
 
 CONV_SUFFIXES = ('conv.weight', 'conv.bias', 'batchnorm.weight', 'batchnorm.bias')         # what ConvBlockTrainer trains
-CONV_STATS = ('batchnorm.running_mean', 'batchnorm.running_var')                           # what it reads and leaves alone
+CONV_STATS = ('batchnorm.running_mean', 'batchnorm.running_var')                           # read; moved with batch_stats only
+CONV_COUNTER = 'batchnorm.num_batches_tracked'
 LAST_CONV_BLOCK = 'ConvNet.ConvBlock_10'            # conv block 7 of the package's numbering: 80 -> 160 on 16 x 16 maps
 
 
@@ -241,10 +244,14 @@ class ConvBlockTrainer:
     """One block Conv2d 3x3 + BatchNorm2d + LeakyReLU(0.1) of the state dict (model.py:5-18) on the device with the Adam
     moments of its four trainable tensors (axt_conv_trainer). forward / step work on batches picked by index from a table
     [n_items, Ci*H*W] of the block's inputs (Detector.features_frames(block=6) for the last block); forward's output
-    [B, Co*H*W] is what HeadTrainer.forward reads. BatchNorm runs with its running statistics and never updates them."""
+    [B, Co*H*W] is what HeadTrainer.forward reads. BatchNorm runs with its running statistics and never updates them,
+    or with batch_stats=True as nn.BatchNorm2d in train mode (momentum: its momentum): forward normalises the batch with
+    its own mean and biased variance and moves running_mean, running_var (by the unbiased variance) and the batch count;
+    step and input_grad take the gradients through the statistics, and conv.bias, whose gradient is then 0 by definition,
+    moves by its weight decay alone. A batch of fewer than 2 values per channel is a ValueError then."""
 
     def __init__(self, state_dict, block_key=LAST_CONV_BLOCK, parameters=None, map_size=(16, 16), max_batch=64,
-                 device='cuda:0'):
+                 device='cuda:0', batch_stats=False, momentum=0.1):
         _require_gpu()
         self.device = torch.device(device)
         self.max_batch = int(max_batch)
@@ -268,6 +275,13 @@ class ConvBlockTrainer:
             _lib.check(self._lib.axt_conv_trainer_create(self.Ci, self.Co, self.H, self.W, *[a.ctypes.data for a in w],
                                                          self.max_batch, ctypes.byref(handle)), 'axt_conv_trainer_create')
         self._h = handle
+        self.batch_stats, self.momentum = bool(batch_stats), float(momentum)
+        if self.batch_stats:                            # a trainer that never asks makes the calls it always made
+            if not 0 < self.momentum <= 1:
+                raise ValueError(f'momentum must be in (0, 1], got {momentum!r}')
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.axt_conv_trainer_set_batch_stats(self._h, 1, self.momentum),
+                           'axt_conv_trainer_set_batch_stats')
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -287,8 +301,11 @@ class ConvBlockTrainer:
         index = self._index(index, inputs.shape[0])
         out = torch.empty((len(index), self.out_width), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.axt_conv_trainer_forward(self._h, inputs.data_ptr(), index.data_ptr(), len(index),
-                                                          out.data_ptr(), _stream()), 'axt_conv_trainer_forward')
+            rc = self._lib.axt_conv_trainer_forward(self._h, inputs.data_ptr(), index.data_ptr(), len(index), out.data_ptr(),
+                                                    _stream())
+        if self.batch_stats and rc == -22:              # the one thing left to refuse here: fewer than 2 values per channel
+            raise ValueError(self._lib.axt_last_error().decode())
+        _lib.check(rc, 'axt_conv_trainer_forward')
         return out
 
     def step(self, inputs, index, dfeat, lr=None, eps=ADAM_EPS):
@@ -338,11 +355,45 @@ class ConvBlockTrainer:
                                                                ctypes.byref(step)), 'axt_conv_trainer_read_moments')
         return m, v, int(step.value)
 
+    def stats(self):
+        """BatchNorm's statistics as the handle holds them: dict(running_mean, running_var [Co] f32,
+        num_batches_tracked: the forwards that ran with batch statistics, batch_mean, batch_var: the mean and biased
+        variance of the last such forward, None before there was one)."""
+        rm, rv, bm, bv = (np.empty(self.Co, np.float32) for _ in range(4))
+        n = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_conv_trainer_read_stats(self._h, rm.ctypes.data, rv.ctypes.data, ctypes.byref(n), None,
+                                                             None), 'axt_conv_trainer_read_stats')
+            if n.value:
+                _lib.check(self._lib.axt_conv_trainer_read_stats(self._h, None, None, None, bm.ctypes.data, bv.ctypes.data),
+                           'axt_conv_trainer_read_stats')
+        return dict(running_mean=rm, running_var=rv, num_batches_tracked=int(n.value), batch_mean=bm if n.value else None,
+                    batch_var=bv if n.value else None)
+
     def state_dict(self, base=None):
         """The state dict this trainer was built from (or `base`) with the block's four trained tensors replaced (numpy
-        f32); the running statistics and num_batches_tracked pass through."""
+        f32); the running statistics and num_batches_tracked pass through. With batch_stats, running_mean and running_var
+        are replaced too and num_batches_tracked grows by the number of forwards, each in the dtype and container (torch
+        tensor or numpy array) it came in; a missing num_batches_tracked is created as int64."""
         sd = dict(self._sd if base is None else base)
         sd.update(zip(self.keys[:4], self.weights()))
+        if self.batch_stats:
+            st = self.stats()
+
+            def like(old, new):
+                if isinstance(old, torch.Tensor):
+                    return torch.from_numpy(np.asarray(new)).to(dtype=old.dtype, device=old.device)
+                return np.asarray(new).astype(np.asarray(old).dtype)
+
+            for k, name in zip(self.keys[4:6], ('running_mean', 'running_var')):
+                sd[k] = like(sd[k], st[name])
+            k = f'{self.block_key}.{CONV_COUNTER}'
+            old = sd.get(k)
+            if old is None:
+                sd[k] = np.array(st['num_batches_tracked'], np.int64)
+            else:
+                before = int(old.cpu()) if isinstance(old, torch.Tensor) else int(np.asarray(old))
+                sd[k] = like(old, np.asarray(before + st['num_batches_tracked']))
         return sd
 
 
@@ -388,9 +439,11 @@ class ConvStageTrainer:
     [n_items, Ci*H*W] of the stage's inputs (Detector.features_frames(block=4)); forward's output is what
     HeadTrainer.forward reads. block_keys, map_size: the three blocks' state-dict prefixes and the (H, W) of the maps the
     first two run on (the third runs on the pooled (H // 2, W // 2)); default: the deployed architecture's, from
-    hotpath's table of conv blocks."""
+    hotpath's table of conv blocks. batch_stats, momentum: train-mode BatchNorm (ConvBlockTrainer's) in the trained blocks;
+    a forward-only block keeps its running statistics."""
 
-    def __init__(self, state_dict, depth=3, parameters=None, max_batch=64, device='cuda:0', block_keys=None, map_size=None):
+    def __init__(self, state_dict, depth=3, parameters=None, max_batch=64, device='cuda:0', block_keys=None, map_size=None,
+                 batch_stats=False, momentum=0.1):
         from .hotpath import CONV_MAP_SIDE, CONV_POOLED, conv_block_key
         if depth not in (1, 2, 3):
             raise ValueError(f'depth must be 1, 2 or 3, got {depth!r}')
@@ -405,12 +458,14 @@ class ConvStageTrainer:
         if self.H < 2 or self.W < 2:
             raise ValueError(f'maps of {self.H} x {self.W} leave the max-pool nothing')
         sizes = [(self.H, self.W), (self.H, self.W), (self.H // 2, self.W // 2)]
-        self.blocks = [ConvBlockTrainer(state_dict, k, parameters, map_size=s, max_batch=max_batch, device=device)
-                       for k, s in zip(block_keys, sizes)]
+        self.trained = [i >= 3 - self.depth for i in range(3)]
+        self.batch_stats = bool(batch_stats)
+        self.blocks = [ConvBlockTrainer(state_dict, k, parameters, map_size=s, max_batch=max_batch, device=device,
+                                        **(dict(batch_stats=True, momentum=momentum) if self.batch_stats and tr else {}))
+                       for k, s, tr in zip(block_keys, sizes, self.trained)]
         for a, b in zip(self.blocks, self.blocks[1:]):
             if a.Co != b.Ci:
                 raise ValueError(f'{a.block_key} writes {a.Co} channels, {b.block_key} reads {b.Ci}')
-        self.trained = [i >= 3 - self.depth for i in range(3)]
         self.device, self.max_batch = self.blocks[0].device, int(max_batch)
         self.in_width, self.out_width = self.blocks[0].in_width, self.blocks[2].out_width
         self._sd = state_dict
@@ -463,7 +518,8 @@ class ConvStageTrainer:
 
     def state_dict(self, base=None):
         """The state dict this stage was built from (or `base`) with the trained blocks' four tensors each replaced
-        (numpy f32); everything else, a forward-only block's tensors included, passes through."""
+        (numpy f32), and with batch_stats their running statistics and batch counts (ConvBlockTrainer.state_dict);
+        everything else, a forward-only block's tensors included, passes through."""
         sd = dict(self._sd if base is None else base)
         for blk, trained in zip(self.blocks, self.trained):
             if trained:
@@ -525,7 +581,7 @@ def _epoch_metrics(sd, timelapse, labels, parameters, subset):
 
 def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
                    use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
-                   metrics_every=10, train_conv_blocks=None, train_last_conv=False):
+                   metrics_every=10, train_conv_blocks=None, bn_batch_stats=False, bn_momentum=0.1, train_last_conv=False):
     """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
     one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
     (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
@@ -562,7 +618,15 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
     head's input gradient, then back to front each block's input gradient, the pool's gradient and the block's step, and
     the head's step. 2 reads the same table (conv block 5's output is not offered as one) and runs conv block 5 forward
     only: its tensors come back as they went in. Every trained block takes the head's learning rate, Adam eps and weight
-    decay and keeps its running statistics. Conv blocks 0-4 stay frozen."""
+    decay and keeps its running statistics. Conv blocks 0-4 stay frozen.
+
+    bn_batch_stats: train-mode BatchNorm in the trained conv blocks, as the reference's model.train() has it
+    (bn_momentum: nn.BatchNorm2d's momentum, 0.1). Each trained block normalises a batch with the batch's own mean and
+    biased variance, its gradients go through those statistics (conv.bias then has gradient 0 by definition and moves by
+    weight decay alone), and every forward moves running_mean, running_var and num_batches_tracked; the returned state
+    dict and the checkpoints carry them, and the every-tenth-epoch evaluation reads them. A forward-only block
+    (train_conv_blocks=2's conv block 5) and the frozen trunk keep their running statistics. With the head alone
+    (train_conv_blocks=0) it is a ValueError: nothing would use it. Default False: running statistics, never updated."""
     import pandas as pd
     from .hotpath import Detector, BLOCK_FEATURES
     if train_conv_blocks is None:
@@ -574,6 +638,11 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         if train_last_conv and depth != 1:
             raise ValueError(f'train_last_conv=True means train_conv_blocks=1, not {depth}')
     train_last_conv = depth == 1
+    if bn_batch_stats and depth == 0:
+        raise ValueError('bn_batch_stats=True needs trained conv blocks (train_conv_blocks >= 1): the head has no BatchNorm')
+    if bn_batch_stats and not 0 < float(bn_momentum) <= 1:
+        raise ValueError(f'bn_momentum must be in (0, 1], got {bn_momentum!r}')
+    bn = dict(batch_stats=True, momentum=float(bn_momentum)) if bn_batch_stats else {}
     block = (7, 6, 4, 4)[depth]                         # which conv block's output the cached table holds
     for tl in (timelapse, test_timelapse):
         if getattr(tl, 'frame_sharded', False):
@@ -628,8 +697,8 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         features = detector.features_frames(timelapse.frames, tile_yx, block=block)
         targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
-    conv = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device) if train_last_conv else None
-    stage = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device) if depth >= 2 else None
+    conv = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device, **bn) if train_last_conv else None
+    stage = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device, **bn) if depth >= 2 else None
     # the state dict of this moment: the head's tensors, and the conv blocks' where they are trained
     current = ((lambda: stage.state_dict(trainer.state_dict())) if stage else
                (lambda: conv.state_dict(trainer.state_dict())) if train_last_conv else trainer.state_dict)

@@ -629,8 +629,10 @@ int axt_head_trainer_step(axt_head_trainer *tr, const float *d_feat, const int32
  * form. Created from host tensors in the state dict's layout: conv.weight [Co,Ci,3,3], conv.bias, batchnorm.weight,
  * batchnorm.bias, batchnorm.running_mean, batchnorm.running_var [Co]. Holds the four trainable tensors with Adam
  * moments m, v (f32, zero), the step count, and z of the last forward batch. Limits: 1 <= Ci, Co <= 512,
- * 1 <= H, W <= 64, 1 <= max_batch <= 64. BatchNorm runs with its running statistics, as at inference (eps 1e-5); they are
- * never updated.
+ * 1 <= H, W <= 64, 1 <= max_batch <= 64. By default BatchNorm runs with its running statistics, as at inference
+ * (eps 1e-5), and leaves them alone; with batch statistics switched on (axtrack_hip_stage.h: _set_batch_stats) it
+ * normalises every batch with that batch's own statistics and moves the running ones, as nn.BatchNorm2d does in train
+ * mode. The handle keeps running_mean and running_var either way (_read_stats).
  * _forward: d_index i32 [B] (NULL = rows 0..B-1) picks rows of the table d_in [., Ci*H*W] (NCHW per row);
  *   z = conv3x3(x) + bias, y = gamma (z - mean) / sqrt(var + 1e-5) + beta, d_feat [B, Co*H*W] = y > 0 ? y : 0.1 y in the
  *   order c*H*W + h*W + w -- the rows axt_head_trainer_forward reads. f32, BatchNorm not folded; per output FMA chains
