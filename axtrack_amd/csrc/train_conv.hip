@@ -26,8 +26,10 @@
 //   conv_dgrad_k     dx[ci][r] = sum_q W[co][ci][ky][kx] dz(q, r) with q = co*9 + ky*3 + kx and dz(q, r) =
 //                    dz[b][co][h-ky+1][w-kx+1], 0 outside the map: conv_fwd_k's product with Co*9 as the depth, the weights
 //                    read transposed and flipped where they lie. dz is formed while staging, from dF, the stashed z and
-//                    gamma as it stands, by conv_bn_back_k's expressions; the same chains of 16 in ascending q. 64 ci x 64 r
-//                    per workgroup. Reads nothing that the step writes except the parameters: it runs before the step.
+//                    gamma as it stands, by conv_bn_back_k's expressions (DzFromDF), or with batch statistics read from
+//                    the dz buffer that bn_batch_back_k<false> filled (DzStored): one kernel, templated on that source;
+//                    the same chains of 16 in ascending q. 64 ci x 64 r per workgroup. Reads nothing that the step
+//                    writes except the parameters: it runs before the step.
 //   maxpool2_fwd_k   nn.MaxPool2d(2, 2), one thread per output element
 //   maxpool2_bwd_k   one thread per input element recomputes its window's winner (the first maximum under a strict >) and
 //                    writes the window's gradient or +0.0: every element is written, nothing is scattered
@@ -39,9 +41,8 @@
 //   bn_batch_back_k  pass 1: dbeta = sum dy, dgamma = sum dy zhat with dy and zhat from bn_y on (mu, inv); pass 2:
 //                    dz = gamma inv (dy - dbeta / n - zhat dgamma / n) into the dz buffer. With kAdam: Adam on gamma and
 //                    beta, and on conv.bias with the gradient 0 that sum dz is by definition. Without: dz only, for
-//   conv_dgrad_dz_k  conv_dgrad_k's product with the staged dz read from the dz buffer instead of formed from dF.
-//                    The sums follow conv_bn_back_k: thread t takes r = t, t + 256, ..., the 256 partial sums meet in a
-//                    fixed binary tree.
+//                    conv_dgrad_k<DzStored>. The sums follow conv_bn_back_k: thread t takes r = t, t + 256, ..., the 256
+//                    partial sums meet in a fixed binary tree (sum256, which all three per-channel kernels share).
 // Determinism: no atomics; every sum has one fixed order that depends on Ci, Co, H, W and B only.
 #include <algorithm>
 #include <cmath>
@@ -68,6 +69,62 @@ __device__ inline float bn_y(float z, float mean, float inv_sigma, float gamma, 
     const float zh = __fmul_rn(__fsub_rn(z, mean), inv_sigma);
     *zhat = zh;
     return fmaf(gamma, zh, beta);
+}
+
+__device__ inline float leaky(float y) { return y > 0.f ? y : kSlope * y; }
+
+// the gradient with respect to y from dF, the gradient with respect to leaky(y): y recomputed from the stashed z by bn_y, so
+// the sign test is the forward's (y == 0 takes the slope)
+__device__ inline float leaky_back(float z, float dF, float mean, float inv_sigma, float gamma, float beta, float *zhat)
+{
+    const float y = bn_y(z, mean, inv_sigma, gamma, beta, zhat);
+    return y > 0.f ? dF : kSlope * dF;
+}
+
+// the offset of element r = b*HW + p of channel c in an array [B][C][HW]. The per-channel kernels walk it with thread t on
+// r = t, t + 256, ... (b ascending)
+__device__ inline size_t chan_off(int r, int C, int HW, int c)
+{
+    const int b = r / HW, p = r - b * HW;
+    return ((size_t)b * C + c) * HW + p;
+}
+
+// the sums of v[0..N-1] over the workgroup's 256 threads in one fixed binary tree (one set of barriers for all N), handed to
+// every thread; red may be used again afterwards
+template <int N>
+__device__ inline void sum256(float (&v)[N], float (*red)[256], int tid)
+{
+    for (int q = 0; q < N; ++q) red[q][tid] = v[q];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w)
+            for (int q = 0; q < N; ++q) red[q][tid] += red[q][tid + w];
+        __syncthreads();
+    }
+    for (int q = 0; q < N; ++q) v[q] = red[q][0];
+    __syncthreads();
+}
+
+__device__ inline float sum256(float v, float (*red)[256], int tid)
+{
+    float s[1] = {v};
+    sum256(s, red, tid);
+    return s[0];
+}
+
+// threads 0..2: Adam on conv.bias, batchnorm.weight, batchnorm.bias of channel co with the gradients grad[0..2] (p, m, v:
+// [3][Co] in that order). Every thread of the workgroup has read the parameters it needs by the time this is called.
+__device__ inline void adam_bias_gamma_beta(int tid, int co, int Co, const float (&grad)[3], float *__restrict__ bias,
+                                            float *__restrict__ gamma, float *__restrict__ beta, float *__restrict__ mom_m,
+                                            float *__restrict__ mom_v, const AdamArgs &a)
+{
+    if (tid >= 3) return;
+    float *param = tid == 0 ? bias : tid == 1 ? gamma : beta;
+    float w = param[co], m = mom_m[tid * Co + co], v = mom_v[tid * Co + co];
+    adam1(tid == 0 ? grad[0] : tid == 1 ? grad[1] : grad[2], w, m, v, a);
+    param[co] = w;
+    mom_m[tid * Co + co] = m;
+    mom_v[tid * Co + co] = v;
 }
 
 // x[row][ci][h+ky-1][w+kx-1] with q = ci*9 + ky*3 + kx; (b, h, w) already split; 0 outside the map
@@ -137,13 +194,11 @@ __global__ __launch_bounds__(256) void conv_fwd_k(const float *__restrict__ x, c
         for (int j = 0; j < 4; ++j) {
             const int rr = r0 + tn * 4 + j;
             if (rr >= R) continue;
-            const int bb = rr / g.HW, pp = rr - bb * g.HW;
-            const size_t o = ((size_t)bb * g.Co + co) * g.HW + pp;
+            const size_t o = chan_off(rr, g.Co, g.HW, co);
             const float zz = acc[i][j] + bi;
             float zh;
-            const float y = bn_y(zz, me, is, ga, be, &zh);
             z[o] = zz;
-            F[o] = y > 0.f ? y : kSlope * y;
+            F[o] = leaky(bn_y(zz, me, is, ga, be, &zh));
         }
     }
 }
@@ -159,34 +214,19 @@ __global__ __launch_bounds__(256) void conv_bn_back_k(const float *__restrict__ 
     const int tid = threadIdx.x, co = blockIdx.x;
     const float ga = gamma[co], be = beta[co], me = mean[co], is = inv_sigma[co];
     const float fold = ga * is;
-    float s_gamma = 0.f, s_beta = 0.f, s_bias = 0.f;
-    for (int r = tid; r < B * g.HW; r += 256) {                        // r = b*H*W + p: thread t takes r = t, t + 256, ...
-        const int b = r / g.HW, p = r - b * g.HW;
-        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+    float s[3] = {};                                                   // dbias, dgamma, dbeta
+    for (int r = tid; r < B * g.HW; r += 256) {
+        const size_t o = chan_off(r, g.Co, g.HW, co);
         float zh;
-        const float y = bn_y(z[o], me, is, ga, be, &zh);
-        const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+        const float dy = leaky_back(z[o], dF[o], me, is, ga, be, &zh);
         const float d = dy * fold;
-        s_gamma = fmaf(dy, zh, s_gamma);
-        s_beta += dy;
-        s_bias += d;
+        s[1] = fmaf(dy, zh, s[1]);
+        s[2] += dy;
+        s[0] += d;
         dz[o] = d;
     }
-    red[0][tid] = s_bias; red[1][tid] = s_gamma; red[2][tid] = s_beta;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w)
-            for (int q = 0; q < 3; ++q) red[q][tid] += red[q][tid + w];
-        __syncthreads();
-    }
-    if (tid < 3) {
-        float *param = tid == 0 ? bias : tid == 1 ? gamma : beta;
-        float w = param[co], m = mom_m[tid * g.Co + co], v = mom_v[tid * g.Co + co];
-        adam1(red[tid][0], w, m, v, a);
-        param[co] = w;
-        mom_m[tid * g.Co + co] = m;
-        mom_v[tid * g.Co + co] = v;
-    }
+    sum256(s, red, tid);
+    adam_bias_gamma_beta(tid, co, g.Co, s, bias, gamma, beta, mom_m, mom_v, a);
 }
 
 // grid (q tiles, co tiles, S). slab [S][Co][K9].
@@ -238,31 +278,31 @@ __global__ __launch_bounds__(256) void conv_adam_w_k(float *__restrict__ W, floa
     W[i] = w; M[i] = m; V[i] = v;
 }
 
-// dz[b][co][h-ky+1][w-kx+1] with q = co*9 + ky*3 + kx, formed from the stashed z and dF by conv_bn_back_k's expressions and
-// from gamma as it stands; (b, h, w) already split; 0 outside the map
-__device__ inline float dz_col(const float *__restrict__ dF, const float *__restrict__ z, int b, const Geom &g, int q, int h,
-                               int w, const float *__restrict__ gamma, const float *__restrict__ beta,
-                               const float *__restrict__ mean, const float *__restrict__ inv_sigma)
-{
-    const int co = q / 9, tap = q - co * 9, ky = tap / 3, kx = tap - ky * 3;
-    const int hh = h - ky + 1, ww = w - kx + 1;
-    if (hh < 0 || hh >= g.H || ww < 0 || ww >= g.W) return 0.f;
-    const size_t o = ((size_t)b * g.Co + co) * g.HW + hh * g.W + ww;
-    const float ga = gamma[co], is = inv_sigma[co];
-    const float fold = ga * is;
-    float zh;
-    const float y = bn_y(z[o], mean[co], is, ga, beta[co], &zh);
-    const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
-    return dy * fold;
-}
+// The two sources of dz for conv_dgrad_k: dz at offset o of a [B][Co][H*W] array, in channel co.
+// Formed from the stashed z and dF by conv_bn_back_k's expressions and from gamma as it stands (running statistics):
+struct DzFromDF {
+    const float *__restrict__ dF, *__restrict__ z, *__restrict__ gamma, *__restrict__ beta, *__restrict__ mean,
+        *__restrict__ inv_sigma;
+    __device__ float operator()(size_t o, int co) const
+    {
+        const float ga = gamma[co], is = inv_sigma[co];
+        const float fold = ga * is;
+        float zh;
+        const float dy = leaky_back(z[o], dF[o], mean[co], is, ga, beta[co], &zh);
+        return dy * fold;
+    }
+};
+// Read from the dz buffer that bn_batch_back_k wrote (batch statistics):
+struct DzStored {
+    const float *__restrict__ dz;
+    __device__ float operator()(size_t o, int) const { return dz[o]; }
+};
 
 // grid (r tiles, ci tiles). dx[b][ci][h][w] = sum_q Wt[co][ci][ky][kx] dz[b][co][h-ky+1][w-kx+1] in ascending q = co*9 + ky*3
-// + kx: conv_fwd_k's product with Co*9 as the depth and the weights read transposed and flipped where they lie. dF, z:
-// [B][Co][H*W]; dx: [B][Ci][H*W].
-__global__ __launch_bounds__(256) void conv_dgrad_k(const float *__restrict__ dF, const float *__restrict__ z, int B, Geom g,
-                                                    const float *__restrict__ Wt, const float *__restrict__ gamma,
-                                                    const float *__restrict__ beta, const float *__restrict__ mean,
-                                                    const float *__restrict__ inv_sigma, float *__restrict__ dx)
+// + kx, 0 outside the map: conv_fwd_k's product with Co*9 as the depth and the weights read transposed and flipped where they
+// lie. dz: one of the two sources above; dx: [B][Ci][H*W].
+template <class Dz>
+__global__ __launch_bounds__(256) void conv_dgrad_k(Dz dz, int B, Geom g, const float *__restrict__ Wt, float *__restrict__ dx)
 {
     __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // W[co][ci][tap] as [q][ci]
     __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // dz of the shifted position as [q][r]
@@ -277,8 +317,12 @@ __global__ __launch_bounds__(256) void conv_dgrad_k(const float *__restrict__ dF
             const int k = i % TK, c = i / TK, q = q0 + k, co = q / 9;
             As[k][c] = (ci0 + c < g.Ci && q < K) ? Wt[((size_t)co * g.Ci + ci0 + c) * 9 + (q - co * 9)] : 0.f;
         }
-        for (int k = tid / TN; k < TK; k += 256 / TN)
-            Bs[k][rl] = (r_ok && q0 + k < K) ? dz_col(dF, z, b, g, q0 + k, h, w, gamma, beta, mean, inv_sigma) : 0.f;
+        for (int k = tid / TN; k < TK; k += 256 / TN) {
+            const int q = q0 + k, co = q / 9, tap = q - co * 9, ky = tap / 3, kx = tap - ky * 3;
+            const int hh = h - ky + 1, ww = w - kx + 1;
+            const bool ok = r_ok && q < K && hh >= 0 && hh < g.H && ww >= 0 && ww < g.W;
+            Bs[k][rl] = ok ? dz(((size_t)b * g.Co + co) * g.HW + hh * g.W + ww, co) : 0.f;
+        }
         __syncthreads();
         tile_fma(As, Bs, tm, tn, acc);
         __syncthreads();
@@ -290,9 +334,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_k(const float *__restrict__ dF
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int rr = r0 + tn * 4 + j;
-            if (rr >= R) continue;
-            const int bb = rr / g.HW, pp = rr - bb * g.HW;
-            dx[((size_t)bb * g.Ci + ci) * g.HW + pp] = acc[i][j];
+            if (rr < R) dx[chan_off(rr, g.Ci, g.HW, ci)] = acc[i][j];
         }
     }
 }
@@ -345,20 +387,6 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_k(const float *__restrict__ 
 }
 
 // ---- batch statistics (train-mode BatchNorm) ----
-// the sum of v over the workgroup's 256 threads in a fixed binary tree, handed to every thread
-__device__ inline float sum256(float v, float *red, int tid)
-{
-    red[tid] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    const float s = red[0];
-    __syncthreads();
-    return s;
-}
-
 struct BnUpdate { float one_minus_m, m, unbias; };             // formed in f64 on the host and rounded once
 
 // grid (Co). z, F: [B][Co][H*W]. stats [3][Co]: the batch's mean, biased variance and 1 / sqrt(var + eps). Moves
@@ -369,18 +397,14 @@ __global__ __launch_bounds__(256) void bn_batch_fwd_k(const float *__restrict__ 
                                                       float *__restrict__ run_inv, float *__restrict__ stats, BnUpdate u,
                                                       float *__restrict__ F)
 {
-    __shared__ float red[256];
+    __shared__ float red[1][256];
     const int tid = threadIdx.x, co = blockIdx.x, n = B * g.HW;
     float s = 0.f;
-    for (int r = tid; r < n; r += 256) {                               // r = b*H*W + p: thread t takes r = t, t + 256, ...
-        const int b = r / g.HW, p = r - b * g.HW;
-        s += z[((size_t)b * g.Co + co) * g.HW + p];
-    }
+    for (int r = tid; r < n; r += 256) s += z[chan_off(r, g.Co, g.HW, co)];
     const float mu = __fdiv_rn(sum256(s, red, tid), (float)n);
     s = 0.f;
     for (int r = tid; r < n; r += 256) {
-        const int b = r / g.HW, p = r - b * g.HW;
-        const float d = __fsub_rn(z[((size_t)b * g.Co + co) * g.HW + p], mu);
+        const float d = __fsub_rn(z[chan_off(r, g.Co, g.HW, co)], mu);
         s = fmaf(d, d, s);
     }
     const float var = __fdiv_rn(sum256(s, red, tid), (float)n);
@@ -396,11 +420,9 @@ __global__ __launch_bounds__(256) void bn_batch_fwd_k(const float *__restrict__ 
     }
     const float ga = gamma[co], be = beta[co];
     for (int r = tid; r < n; r += 256) {
-        const int b = r / g.HW, p = r - b * g.HW;
-        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        const size_t o = chan_off(r, g.Co, g.HW, co);
         float zh;
-        const float y = bn_y(z[o], mu, inv, ga, be, &zh);
-        F[o] = y > 0.f ? y : kSlope * y;
+        F[o] = leaky(bn_y(z[o], mu, inv, ga, be, &zh));
     }
 }
 
@@ -413,79 +435,27 @@ __global__ __launch_bounds__(256) void bn_batch_back_k(const float *__restrict__
                                                        float *__restrict__ mom_m, float *__restrict__ mom_v,
                                                        float *__restrict__ dz, AdamArgs a)
 {
-    __shared__ float red[256];
+    __shared__ float red[1][256];
     const int tid = threadIdx.x, co = blockIdx.x, n = B * g.HW;
     const float ga = gamma[co], be = beta[co], mu = stats[co], is = stats[2 * g.Co + co];
     const float fold = ga * is;
     float s_gamma = 0.f, s_beta = 0.f;
     for (int r = tid; r < n; r += 256) {
-        const int b = r / g.HW, p = r - b * g.HW;
-        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        const size_t o = chan_off(r, g.Co, g.HW, co);
         float zh;
-        const float y = bn_y(z[o], mu, is, ga, be, &zh);
-        const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+        const float dy = leaky_back(z[o], dF[o], mu, is, ga, be, &zh);
         s_gamma = fmaf(dy, zh, s_gamma);
         s_beta += dy;
     }
     const float dgamma = sum256(s_gamma, red, tid), dbeta = sum256(s_beta, red, tid);
     const float mg = __fdiv_rn(dgamma, (float)n), mb = __fdiv_rn(dbeta, (float)n);
     for (int r = tid; r < n; r += 256) {
-        const int b = r / g.HW, p = r - b * g.HW;
-        const size_t o = ((size_t)b * g.Co + co) * g.HW + p;
+        const size_t o = chan_off(r, g.Co, g.HW, co);
         float zh;
-        const float y = bn_y(z[o], mu, is, ga, be, &zh);
-        const float dy = y > 0.f ? dF[o] : kSlope * dF[o];
+        const float dy = leaky_back(z[o], dF[o], mu, is, ga, be, &zh);
         dz[o] = fold * ((dy - mb) - zh * mg);
     }
-    if (kAdam && tid < 3) {                                            // every thread has read gamma and beta by now
-        float *param = tid == 0 ? bias : tid == 1 ? gamma : beta;
-        float w = param[co], m = mom_m[tid * g.Co + co], v = mom_v[tid * g.Co + co];
-        adam1(tid == 0 ? 0.f : tid == 1 ? dgamma : dbeta, w, m, v, a);
-        param[co] = w;
-        mom_m[tid * g.Co + co] = m;
-        mom_v[tid * g.Co + co] = v;
-    }
-}
-
-// grid (r tiles, ci tiles). conv_dgrad_k with dz(q, r) = dz[b][co][h-ky+1][w-kx+1] read from the dz buffer, 0 outside the map.
-__global__ __launch_bounds__(256) void conv_dgrad_dz_k(const float *__restrict__ dz, int B, Geom g,
-                                                       const float *__restrict__ Wt, float *__restrict__ dx)
-{
-    __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // W[co][ci][tap] as [q][ci]
-    __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // dz of the shifted position as [q][r]
-    const int tid = threadIdx.x, tm = tid / 16, tn = tid % 16;
-    const int r0 = blockIdx.x * TN, ci0 = blockIdx.y * TM, R = B * g.HW, K = g.Co * 9;
-    const int rl = tid % TN, r = r0 + rl;
-    const bool r_ok = r < R;
-    const int b = r_ok ? r / g.HW : 0, p = r - b * g.HW, h = p / g.W, w = p - h * g.W;
-    float acc[4][4] = {};
-    for (int q0 = 0; q0 < K; q0 += TK) {
-        for (int i = tid; i < TM * TK; i += 256) {
-            const int k = i % TK, c = i / TK, q = q0 + k, co = q / 9;
-            As[k][c] = (ci0 + c < g.Ci && q < K) ? Wt[((size_t)co * g.Ci + ci0 + c) * 9 + (q - co * 9)] : 0.f;
-        }
-        for (int k = tid / TN; k < TK; k += 256 / TN) {
-            const int q = q0 + k, co = q / 9, tap = q - co * 9, ky = tap / 3, kx = tap - ky * 3;
-            const int hh = h - ky + 1, ww = w - kx + 1;
-            const bool ok = r_ok && q < K && hh >= 0 && hh < g.H && ww >= 0 && ww < g.W;
-            Bs[k][rl] = ok ? dz[((size_t)b * g.Co + co) * g.HW + hh * g.W + ww] : 0.f;
-        }
-        __syncthreads();
-        tile_fma(As, Bs, tm, tn, acc);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ci = ci0 + tm * 4 + i;
-        if (ci >= g.Ci) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int rr = r0 + tn * 4 + j;
-            if (rr >= R) continue;
-            const int bb = rr / g.HW, pp = rr - bb * g.HW;
-            dx[((size_t)bb * g.Ci + ci) * g.HW + pp] = acc[i][j];
-        }
-    }
+    if (kAdam) adam_bias_gamma_beta(tid, co, g.Co, {0.f, dgamma, dbeta}, bias, gamma, beta, mom_m, mom_v, a);
 }
 
 // split of the reduction over r = B*H*W for the weight gradient: about 1024 workgroups, runs a multiple of the tile depth
@@ -532,6 +502,33 @@ int ct_alloc(axt_conv_trainer *t, float **p, size_t floats, bool zero)
     t->allocs.push_back(*p);
     t->bytes += bytes;
     if (zero) AXT_CHECK_HIP(hipMemset(*p, 0, bytes));
+    return AXT_OK;
+}
+
+// what _step and _input_grad ask of their batch: in range, and the one the last forward stashed
+int ct_check_stashed(const axt_conv_trainer *t, int B, const char *fn)
+{
+    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "%s: batch %d not in [1,%d]", fn, B, t->max_batch);
+    AXT_REQUIRE(B == t->last_B, "%s: the stashed activations are of a batch of %d, not %d: call axt_conv_trainer_forward on "
+                "this batch first", fn, t->last_B, B);
+    return AXT_OK;
+}
+
+// kAdam: the step's form. Without: dz only; the parameters and the moments are left alone.
+template <bool kAdam>
+void launch_bn_batch_back(axt_conv_trainer *t, const float *d_dfeat, int B, const AdamArgs &a, hipStream_t st)
+{
+    const Geom &g = t->g;
+    hipLaunchKernelGGL(bn_batch_back_k<kAdam>, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
+                       t->p3 + 2 * g.Co, t->bstats, t->m3, t->v3, t->dz, a);
+}
+
+// what both max-pool entry points ask of their sizes
+int pool_check(int64_t n_maps, int H, int W, const char *fn)
+{
+    AXT_REQUIRE(H >= 2 && H <= kMaxPoolHW && W >= 2 && W <= kMaxPoolHW, "%s: map %d x %d not in [2,%d]", fn, H, W, kMaxPoolHW);
+    AXT_REQUIRE(n_maps >= 0 && n_maps <= kMaxPoolElems / ((int64_t)H * W), "%s: %lld maps of %d x %d exceed %lld elements", fn,
+                (long long)n_maps, H, W, (long long)kMaxPoolElems);
     return AXT_OK;
 }
 
@@ -649,9 +646,7 @@ int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t 
                           double lr, double beta1, double beta2, double eps, double weight_decay, void *stream)
 {
     AXT_REQUIRE(t && d_in && d_dfeat, "null argument");
-    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_conv_trainer_step: batch %d not in [1,%d]", B, t->max_batch);
-    AXT_REQUIRE(B == t->last_B, "axt_conv_trainer_step: the stashed activations are of a batch of %d, not %d: call "
-                "axt_conv_trainer_forward on this batch first", t->last_B, B);
+    if (int rc = ct_check_stashed(t, B, "axt_conv_trainer_step")) return rc;
     AXT_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0,
                 "axt_conv_trainer_step: bad Adam parameters");
     hipStream_t st = (hipStream_t)stream;
@@ -660,8 +655,7 @@ int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t 
     const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, t->step);
     // dz from gamma as it stands: each workgroup reads its channel's gamma before it updates it
     if (t->last_batch_stats)
-        hipLaunchKernelGGL(bn_batch_back_k<true>, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
-                           t->p3 + 2 * g.Co, t->bstats, t->m3, t->v3, t->dz, a);
+        launch_bn_batch_back<true>(t, d_dfeat, B, a, st);
     else
         hipLaunchKernelGGL(conv_bn_back_k, dim3(g.Co), dim3(256), 0, st, d_dfeat, t->z, B, g, t->p3, t->p3 + g.Co,
                            t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->m3, t->v3, t->dz, a);
@@ -681,23 +675,20 @@ int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t 
 int axt_conv_trainer_input_grad(axt_conv_trainer *t, const float *d_dfeat, int B, float *d_dx, void *stream)
 {
     AXT_REQUIRE(t && d_dfeat && d_dx, "null argument");
-    AXT_REQUIRE(B >= 1 && B <= t->max_batch, "axt_conv_trainer_input_grad: batch %d not in [1,%d]", B, t->max_batch);
-    AXT_REQUIRE(B == t->last_B, "axt_conv_trainer_input_grad: the stashed activations are of a batch of %d, not %d: call "
-                "axt_conv_trainer_forward on this batch first", t->last_B, B);
+    if (int rc = ct_check_stashed(t, B, "axt_conv_trainer_input_grad")) return rc;
+    hipStream_t st = (hipStream_t)stream;
     const Geom &g = t->g;
     const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Ci, TM));
     if (t->last_batch_stats) {
         // batch form: dz goes through the handle's dz buffer, which _step writes again with the same values from the same
-        // inputs; the parameters and the moments are left alone
-        hipLaunchKernelGGL(bn_batch_back_k<false>, dim3(g.Co), dim3(256), 0, (hipStream_t)stream, d_dfeat, t->z, B, g, t->p3,
-                           t->p3 + g.Co, t->p3 + 2 * g.Co, t->bstats, t->m3, t->v3, t->dz, AdamArgs{});
+        // inputs
+        launch_bn_batch_back<false>(t, d_dfeat, B, AdamArgs{}, st);
         AXT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(conv_dgrad_dz_k, grid, dim3(256), 0, (hipStream_t)stream, t->dz, B, g, t->w, d_dx);
-        AXT_LAUNCH_CHECK();
-        return AXT_OK;
+        hipLaunchKernelGGL(conv_dgrad_k<DzStored>, grid, dim3(256), 0, st, DzStored{t->dz}, B, g, t->w, d_dx);
+    } else {
+        const DzFromDF dz = {d_dfeat, t->z, t->p3 + g.Co, t->p3 + 2 * g.Co, t->mean, t->inv_sigma};
+        hipLaunchKernelGGL(conv_dgrad_k<DzFromDF>, grid, dim3(256), 0, st, dz, B, g, t->w, d_dx);
     }
-    hipLaunchKernelGGL(conv_dgrad_k, grid, dim3(256), 0, (hipStream_t)stream, d_dfeat, t->z, B, g, t->w, t->p3 + g.Co,
-                       t->p3 + 2 * g.Co, t->mean, t->inv_sigma, d_dx);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
 }
@@ -742,10 +733,7 @@ int axt_conv_trainer_read_stats(const axt_conv_trainer *t, float *h_running_mean
 int axt_maxpool2_forward(const float *d_in, int64_t n_maps, int H, int W, float *d_out, void *stream)
 {
     AXT_REQUIRE(d_in && d_out, "null argument");
-    AXT_REQUIRE(H >= 2 && H <= kMaxPoolHW && W >= 2 && W <= kMaxPoolHW, "axt_maxpool2_forward: map %d x %d not in [2,%d]", H, W,
-                kMaxPoolHW);
-    AXT_REQUIRE(n_maps >= 0 && n_maps <= kMaxPoolElems / ((int64_t)H * W), "axt_maxpool2_forward: %lld maps of %d x %d exceed "
-                "%lld elements", (long long)n_maps, H, W, (long long)kMaxPoolElems);
+    if (int rc = pool_check(n_maps, H, W, "axt_maxpool2_forward")) return rc;
     if (n_maps == 0) return AXT_OK;
     const size_t n_out = (size_t)n_maps * (H / 2) * (W / 2);
     hipLaunchKernelGGL(maxpool2_fwd_k, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_in, n_out, H,
@@ -757,10 +745,7 @@ int axt_maxpool2_forward(const float *d_in, int64_t n_maps, int H, int W, float 
 int axt_maxpool2_backward(const float *d_in, const float *d_dout, int64_t n_maps, int H, int W, float *d_din, void *stream)
 {
     AXT_REQUIRE(d_in && d_dout && d_din, "null argument");
-    AXT_REQUIRE(H >= 2 && H <= kMaxPoolHW && W >= 2 && W <= kMaxPoolHW, "axt_maxpool2_backward: map %d x %d not in [2,%d]", H,
-                W, kMaxPoolHW);
-    AXT_REQUIRE(n_maps >= 0 && n_maps <= kMaxPoolElems / ((int64_t)H * W), "axt_maxpool2_backward: %lld maps of %d x %d exceed "
-                "%lld elements", (long long)n_maps, H, W, (long long)kMaxPoolElems);
+    if (int rc = pool_check(n_maps, H, W, "axt_maxpool2_backward")) return rc;
     if (n_maps == 0) return AXT_OK;
     const size_t n_in = (size_t)n_maps * H * W;
     hipLaunchKernelGGL(maxpool2_bwd_k, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_in, d_dout,

@@ -9,18 +9,12 @@ by the inference kernels (Detector.features_frames; once, or once per epoch when
 translate / flip / rotate of frames and labels every epoch, the prepare_data resampling loop, and the feature table
 recomputed from the warped frames, which costs about one trunk pass per epoch.
 
-fine_tune_head(train_last_conv=True) trains the last convolutional block (ConvNet.ConvBlock_10) jointly with the head
-(ConvBlockTrainer, csrc/train_conv.hip): the cached table is then the trunk's output one block earlier, and a step runs the
-block's forward pass in training form, the head, the loss, the head's input gradient, and both Adam updates. BatchNorm
-keeps its running statistics, as at inference, unless bn_batch_stats=True asks for train-mode BatchNorm: every trained
-block then normalises a batch with that batch's own mean and variance, its gradients go through them, and running_mean,
-running_var and num_batches_tracked move as nn.BatchNorm2d moves them. Conv blocks 0-6 stay frozen.
-
-fine_tune_head(train_conv_blocks=3) trains the whole last conv stage (ConvStageTrainer: conv blocks 5 and 6, the 2 x 2
-max-pool, conv block 7) from the table three blocks earlier: the blocks' input gradients (axt_conv_trainer_input_grad) and
-the pool's gradient (axt_maxpool2_backward) carry the head's input gradient back through the stage. Conv blocks 0-4 stay
-frozen."""
+The last one to three conv blocks can be trained jointly with the head (csrc/train_conv.hip): ConvBlockTrainer is one
+block, ConvStageTrainer the last stage (conv blocks 5 and 6, the 2 x 2 max-pool, conv block 7), either with BatchNorm's
+running statistics or with train-mode BatchNorm. The cached table is then the trunk's output that many blocks earlier.
+fine_tune_head's docstring says what each option (train_conv_blocks, train_last_conv, bn_batch_stats) does to a step."""
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -96,54 +90,62 @@ def _np32(v):
     return np.ascontiguousarray(v, np.float32)
 
 
-class HeadTrainer:
-    """Device-resident fcs.1/3/5 with their Adam moments (axt_head_trainer). forward / loss / step work on batches picked
-    by index from a feature table [n_items, K0] and a target table [n_items, 12, 12, 4] that stay on the GPU."""
+def _train_parameters(parameters):
+    """TRAIN_DEFAULTS with the keys of `parameters` that it knows replaced."""
+    P = dict(TRAIN_DEFAULTS)
+    P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
+    return P
 
-    def __init__(self, state_dict, parameters=None, max_batch=64, device='cuda:0'):
+
+@functools.lru_cache(maxsize=None)
+def _first_rows(B, device):
+    """Rows 0..B-1 as an i32 tensor on `device`: the index with which a trainer reads the whole output of the one in front
+    of it. One tensor per batch size (at most max_batch of them) for every trainer and the step loop."""
+    return torch.arange(B, dtype=torch.int32, device=device)
+
+
+class _HandleTrainer:
+    """What HeadTrainer and ConvBlockTrainer share: the training parameters, the library handle's life, and the checks of
+    a batch's index and of a table. _CREATE, _DESTROY, _DEVICE_BYTES: the library's functions for the handle."""
+    _CREATE = _DESTROY = _DEVICE_BYTES = None
+
+    def __init__(self, state_dict, keys, parameters, max_batch, device):
         _require_gpu()
         self.device = torch.device(device)
         self.max_batch = int(max_batch)
-        self.P = dict(TRAIN_DEFAULTS)
-        self.P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
+        self.P = _train_parameters(parameters)
         self._sd = state_dict
-        for k in FC_KEYS:
+        for k in keys:
             if k not in state_dict:
                 raise KeyError(f'state_dict lacks {k}')
-        w = [_np32(state_dict[k]) for k in FC_KEYS]
-        self.dims = (w[0].shape[1], w[0].shape[0], w[2].shape[0], w[4].shape[0])
-        if w[2].shape[1] != self.dims[1] or w[4].shape[1] != self.dims[2] or any(
-                w[2 * i + 1].shape != (self.dims[i + 1],) for i in range(3)):
-            raise ValueError(f'inconsistent head shapes: {[a.shape for a in w]}')
+
+    def _create(self, *args):
+        """The handle from _CREATE(*args, max_batch, &handle); the caller has checked everything it can on the host."""
         self._lib = _lib.load()
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.axt_head_trainer_create(*self.dims, *[a.ctypes.data for a in w], self.max_batch,
-                                                         ctypes.byref(handle)), 'axt_head_trainer_create')
+            _lib.check(getattr(self._lib, self._CREATE)(*args, self.max_batch, ctypes.byref(handle)), self._CREATE)
         self._h = handle
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
         if h:
-            self._lib.axt_head_trainer_destroy(h)
+            getattr(self._lib, self._DESTROY)(h)
 
     @property
     def device_bytes(self):
-        return int(self._lib.axt_head_trainer_device_bytes(self._h))
+        return int(getattr(self._lib, self._DEVICE_BYTES)(self._h))
 
     def _index(self, index, n):
         """Batch rows as a device i32 tensor, checked against the table's n rows (on the host where the index is there)."""
         if index is None:
             index = np.arange(n)
-        if isinstance(index, torch.Tensor):
-            index = index.to(self.device, torch.int32).contiguous()
-            bad = bool(((index < 0) | (index >= n)).any())
-        else:
-            index = np.ascontiguousarray(index, np.int32)
-            bad = bool(((index < 0) | (index >= n)).any())
-            index = torch.from_numpy(index).to(self.device)
-        if bad:
+        on_device = isinstance(index, torch.Tensor)
+        index = index.to(self.device, torch.int32).contiguous() if on_device else np.ascontiguousarray(index, np.int32)
+        if bool(((index < 0) | (index >= n)).any()):
             raise IndexError(f'batch index outside the table of {n} rows')
+        if not on_device:
+            index = torch.from_numpy(index).to(self.device)
         if not 1 <= len(index) <= self.max_batch:
             raise ValueError(f'a batch of {len(index)} rows; this trainer takes 1..{self.max_batch}')
         return index
@@ -152,6 +154,21 @@ class HeadTrainer:
         if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device and t.dim() >= 2
                 and t[0].numel() == width):
             raise ValueError(f'{what} must be a contiguous f32 tensor [n, {width}] on {self.device}')
+
+
+class HeadTrainer(_HandleTrainer):
+    """Device-resident fcs.1/3/5 with their Adam moments (axt_head_trainer). forward / loss / step work on batches picked
+    by index from a feature table [n_items, K0] and a target table [n_items, 12, 12, 4] that stay on the GPU."""
+    _CREATE, _DESTROY, _DEVICE_BYTES = (f'axt_head_trainer_{f}' for f in ('create', 'destroy', 'device_bytes'))
+
+    def __init__(self, state_dict, parameters=None, max_batch=64, device='cuda:0'):
+        super().__init__(state_dict, FC_KEYS, parameters, max_batch, device)
+        w = [_np32(state_dict[k]) for k in FC_KEYS]
+        self.dims = (w[0].shape[1], w[0].shape[0], w[2].shape[0], w[4].shape[0])
+        if w[2].shape[1] != self.dims[1] or w[4].shape[1] != self.dims[2] or any(
+                w[2 * i + 1].shape != (self.dims[i + 1],) for i in range(3)):
+            raise ValueError(f'inconsistent head shapes: {[a.shape for a in w]}')
+        self._create(*self.dims, *[a.ctypes.data for a in w])
 
     def forward(self, features, index=None):
         """features f32 [n_items, K0] on the GPU, index: which rows form the batch (default: all) -> [B, 12, 12, 3]."""
@@ -240,7 +257,7 @@ CONV_COUNTER = 'batchnorm.num_batches_tracked'
 LAST_CONV_BLOCK = 'ConvNet.ConvBlock_10'            # conv block 7 of the package's numbering: 80 -> 160 on 16 x 16 maps
 
 
-class ConvBlockTrainer:
+class ConvBlockTrainer(_HandleTrainer):
     """One block Conv2d 3x3 + BatchNorm2d + LeakyReLU(0.1) of the state dict (model.py:5-18) on the device with the Adam
     moments of its four trainable tensors (axt_conv_trainer). forward / step work on batches picked by index from a table
     [n_items, Ci*H*W] of the block's inputs (Detector.features_frames(block=6) for the last block); forward's output
@@ -249,51 +266,28 @@ class ConvBlockTrainer:
     its own mean and biased variance and moves running_mean, running_var (by the unbiased variance) and the batch count;
     step and input_grad take the gradients through the statistics, and conv.bias, whose gradient is then 0 by definition,
     moves by its weight decay alone. A batch of fewer than 2 values per channel is a ValueError then."""
+    _CREATE, _DESTROY, _DEVICE_BYTES = (f'axt_conv_trainer_{f}' for f in ('create', 'destroy', 'device_bytes'))
 
     def __init__(self, state_dict, block_key=LAST_CONV_BLOCK, parameters=None, map_size=(16, 16), max_batch=64,
                  device='cuda:0', batch_stats=False, momentum=0.1):
-        _require_gpu()
-        self.device = torch.device(device)
-        self.max_batch = int(max_batch)
         self.block_key = block_key
-        self.P = dict(TRAIN_DEFAULTS)
-        self.P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
-        self._sd = state_dict
         self.keys = tuple(f'{block_key}.{k}' for k in CONV_SUFFIXES + CONV_STATS)
-        for k in self.keys:
-            if k not in state_dict:
-                raise KeyError(f'state_dict lacks {k}')
+        super().__init__(state_dict, self.keys, parameters, max_batch, device)
         w = [_np32(state_dict[k]) for k in self.keys]
         if w[0].ndim != 4 or w[0].shape[2:] != (3, 3) or any(a.shape != (w[0].shape[0],) for a in w[1:]):
             raise ValueError(f'not a 3x3 conv block: {[a.shape for a in w]}')
         self.Co, self.Ci = int(w[0].shape[0]), int(w[0].shape[1])
         self.H, self.W = (int(v) for v in map_size)
         self.in_width, self.out_width = self.Ci * self.H * self.W, self.Co * self.H * self.W
-        self._lib = _lib.load()
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.axt_conv_trainer_create(self.Ci, self.Co, self.H, self.W, *[a.ctypes.data for a in w],
-                                                         self.max_batch, ctypes.byref(handle)), 'axt_conv_trainer_create')
-        self._h = handle
-        self.batch_stats, self.momentum = bool(batch_stats), float(momentum)
+        self._create(self.Ci, self.Co, self.H, self.W, *[a.ctypes.data for a in w])
+        self.batch_stats = bool(batch_stats)
+        self.momentum = float(momentum) if self.batch_stats else momentum       # read with batch statistics only
         if self.batch_stats:                            # a trainer that never asks makes the calls it always made
             if not 0 < self.momentum <= 1:
                 raise ValueError(f'momentum must be in (0, 1], got {momentum!r}')
             with torch.cuda.device(self.device):
                 _lib.check(self._lib.axt_conv_trainer_set_batch_stats(self._h, 1, self.momentum),
                            'axt_conv_trainer_set_batch_stats')
-
-    def __del__(self):
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            self._lib.axt_conv_trainer_destroy(h)
-
-    @property
-    def device_bytes(self):
-        return int(self._lib.axt_conv_trainer_device_bytes(self._h))
-
-    _index = HeadTrainer._index
-    _check_table = HeadTrainer._check_table
 
     def forward(self, inputs, index=None):
         """inputs f32 [n_items, Ci*H*W] on the GPU, index: which rows form the batch (default: all) -> [B, Co*H*W]."""
@@ -461,7 +455,7 @@ class ConvStageTrainer:
         self.trained = [i >= 3 - self.depth for i in range(3)]
         self.batch_stats = bool(batch_stats)
         self.blocks = [ConvBlockTrainer(state_dict, k, parameters, map_size=s, max_batch=max_batch, device=device,
-                                        **(dict(batch_stats=True, momentum=momentum) if self.batch_stats and tr else {}))
+                                        batch_stats=self.batch_stats and tr, momentum=momentum)
                        for k, s, tr in zip(block_keys, sizes, self.trained)]
         for a, b in zip(self.blocks, self.blocks[1:]):
             if a.Co != b.Ci:
@@ -469,24 +463,18 @@ class ConvStageTrainer:
         self.device, self.max_batch = self.blocks[0].device, int(max_batch)
         self.in_width, self.out_width = self.blocks[0].in_width, self.blocks[2].out_width
         self._sd = state_dict
-        self._rows = {}                                 # batch size -> rows 0..B-1 on the device
         self._kept = None
 
     @property
     def device_bytes(self):
         return sum(b.device_bytes for b in self.blocks)
 
-    def _identity(self, B):
-        if B not in self._rows:
-            self._rows[B] = torch.arange(B, dtype=torch.int32, device=self.device)
-        return self._rows[B]
-
     def forward(self, table, batch=None):
         """table f32 [n_items, Ci*H*W] on the GPU, batch: which rows (default: all) -> [B, Co*(H//2)*(W//2)], the head's
         input rows. The outputs in between are kept for backward_and_step."""
         b5, b6, b7 = self.blocks
         f5 = b5.forward(table, batch)
-        rows = self._identity(f5.shape[0])
+        rows = _first_rows(f5.shape[0], self.device)
         f6 = b6.forward(f5, rows)
         pooled = maxpool2_forward(f6, self.H, self.W).reshape(f5.shape[0], b7.in_width)
         f7 = b7.forward(pooled, rows)
@@ -502,7 +490,7 @@ class ConvStageTrainer:
             raise ValueError('backward_and_step needs forward() on this batch first')
         b5, b6, b7 = self.blocks
         f5, f6, pooled, _ = self._kept
-        rows = self._identity(dfeat.shape[0])
+        rows = _first_rows(dfeat.shape[0], self.device)
         grads = {}
         if self.trained[1]:
             grads['pooled'] = b7.input_grad(dfeat)
@@ -637,12 +625,10 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         depth = int(train_conv_blocks)
         if train_last_conv and depth != 1:
             raise ValueError(f'train_last_conv=True means train_conv_blocks=1, not {depth}')
-    train_last_conv = depth == 1
     if bn_batch_stats and depth == 0:
         raise ValueError('bn_batch_stats=True needs trained conv blocks (train_conv_blocks >= 1): the head has no BatchNorm')
     if bn_batch_stats and not 0 < float(bn_momentum) <= 1:
         raise ValueError(f'bn_momentum must be in (0, 1], got {bn_momentum!r}')
-    bn = dict(batch_stats=True, momentum=float(bn_momentum)) if bn_batch_stats else {}
     block = (7, 6, 4, 4)[depth]                         # which conv block's output the cached table holds
     for tl in (timelapse, test_timelapse):
         if getattr(tl, 'frame_sharded', False):
@@ -665,8 +651,7 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         raise ValueError('pass use_transforms (drawn every epoch) or transforms (one per epoch), not both')
     if transforms is not None and len(transforms) != epochs:
         raise ValueError(f'{len(transforms)} transforms for {epochs} epochs')
-    P = dict(TRAIN_DEFAULTS)
-    P.update({k: v for k, v in (parameters or {}).items() if k in TRAIN_DEFAULTS})
+    P = _train_parameters(parameters)
     if isinstance(model, Detector):
         detector, sd = model, getattr(model, 'state_dict_source', None)
         if sd is None:
@@ -697,12 +682,22 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         features = detector.features_frames(timelapse.frames, tile_yx, block=block)
         targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
-    conv = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device, **bn) if train_last_conv else None
-    stage = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device, **bn) if depth >= 2 else None
-    # the state dict of this moment: the head's tensors, and the conv blocks' where they are trained
-    current = ((lambda: stage.state_dict(trainer.state_dict())) if stage else
-               (lambda: conv.state_dict(trainer.state_dict())) if train_last_conv else trainer.state_dict)
-    identity = {}                                       # batch size -> rows 0..B-1 on the device: the head reads conv.forward's output
+    # the trained conv blocks in front of the head: the stage, one block, or none. Their step calls take the same arguments.
+    if depth >= 2:
+        trunk = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device,
+                                 batch_stats=bn_batch_stats, momentum=bn_momentum)
+        trunk_step = trunk.backward_and_step
+    elif depth == 1:
+        trunk = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device,
+                                 batch_stats=bn_batch_stats, momentum=bn_momentum)
+        trunk_step = trunk.step
+    else:
+        trunk = None
+
+    def current():
+        """The state dict of this moment: the head's tensors, and the conv blocks' where they are trained."""
+        return trunk.state_dict(trainer.state_dict()) if trunk else trainer.state_dict()
+
     rng = np.random.default_rng(seed)
     checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
     history, metrics = {}, {}
@@ -717,30 +712,19 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         lr = learning_rate(P['LR'], P['LR_DECAYRATE'], epoch)
         rows = []
         for batch in epoch_batches(features.shape[0], bs, P['SHUFFLE'], P['DROP_LAST'], rng):
-            if stage:
-                feats = stage.forward(features, batch)
-                if len(batch) not in identity:
-                    identity[len(batch)] = torch.arange(len(batch), dtype=torch.int32, device=trainer.device)
-                rows_all = identity[len(batch)]
-                yolo = trainer.forward(feats, rows_all)
-                comp, dy = trainer.loss(yolo, targets, batch)
-                dfeat = trainer.input_grad(dy)              # from the head's weights before they move
-                stage.backward_and_step(features, batch, dfeat, lr=lr)
-                trainer.step(feats, rows_all, dy, lr=lr)
-            elif train_last_conv:
-                feats = conv.forward(features, batch)
-                if len(batch) not in identity:
-                    identity[len(batch)] = torch.arange(len(batch), dtype=torch.int32, device=trainer.device)
-                rows_all = identity[len(batch)]
-                yolo = trainer.forward(feats, rows_all)
-                comp, dy = trainer.loss(yolo, targets, batch)
-                dfeat = trainer.input_grad(dy)              # from the head's weights before they move
-                conv.step(features, batch, dfeat, lr=lr)
-                trainer.step(feats, rows_all, dy, lr=lr)
+            # what the head reads: the trunk's output for this batch, of which it takes rows 0..B-1, or the cached table
+            if trunk:
+                feats, head_rows = trunk.forward(features, batch), _first_rows(len(batch), trainer.device)
             else:
-                yolo = trainer.forward(features, batch)
-                comp, dy = trainer.loss(yolo, targets, batch)
-                trainer.step(features, batch, dy, lr=lr)
+                feats, head_rows = features, batch
+            yolo = trainer.forward(feats, head_rows)
+            comp, dy = trainer.loss(yolo, targets, batch)
+            # the order: the head's input gradient is taken from the head's weights before they move, so before any step;
+            # then the trunk steps (back to front, each block's input gradient before its own step), then the head
+            if trunk:
+                dfeat = trainer.input_grad(dy)
+                trunk_step(features, batch, dfeat, lr=lr)
+            trainer.step(feats, head_rows, dy, lr=lr)
             rows.append([comp[k] for k in COMPONENTS])
         history[epoch] = np.mean(np.array(rows, np.float64).reshape(-1, 5), axis=0)
         if dest_dir is not None and epoch in checkpoints:

@@ -1,5 +1,5 @@
 """Train-mode BatchNorm in the trained conv blocks on the GPU (csrc/train_conv.hip: bn_batch_fwd_k, bn_batch_back_k,
-conv_dgrad_dz_k; axtrack_amd/training.py: ConvBlockTrainer(batch_stats=), ConvStageTrainer(batch_stats=),
+conv_dgrad_k<DzStored>; axtrack_amd/training.py: ConvBlockTrainer(batch_stats=), ConvStageTrainer(batch_stats=),
 fine_tune_head(bn_batch_stats=)) against tests/train_bn_reference.py. Every step is judged on its own by the restarted
 scheme: against one step of the f64 reference and of the f32 yardstick, restarted from what the GPU held after the step
 before -- tensors, moments, running statistics and batch count. Judged: F, dfeat, dx, the batch's mean and variance, the
