@@ -712,8 +712,9 @@ static int sources_left_open(const int16_t *d_Dtmp, const int32_t *d_count, cons
     if (nf == 0) return AXT_OK;
     std::vector<int> hf((size_t)n_frames * cap);
     hc.resize(n_frames);
-    AXT_CHECK_HIP(hipMemcpy(hf.data(), d_flags, hf.size() * 4, hipMemcpyDeviceToHost));
-    AXT_CHECK_HIP(hipMemcpy(hc.data(), d_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+    AXT_CHECK_HIP(hipMemcpyAsync(hf.data(), d_flags, hf.size() * 4, hipMemcpyDeviceToHost, st));
+    AXT_CHECK_HIP(hipMemcpyAsync(hc.data(), d_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
+    AXT_CHECK_HIP(hipStreamSynchronize(st));
     for (int t = 0; t < n_frames; ++t)
         for (int i = 0; i < hc[t] && i < cap; ++i)
             if (hf[(size_t)t * cap + i]) open.push_back(t * cap + i);
