@@ -6,7 +6,8 @@ visualize_inference exists and says that matplotlib / video plotting is out of s
 annotated frames on the GPU and writes PNG frames or one animated PNG; segment_mask makes the microchannel mask of
 prepare_input_data(mask_fname=...) from a transmission image (data_prep_nbs/00_segment_bg.ipynb); fine_tune_head
 trains the detector's three linear layers on labelled frames with the convolutional trunk frozen (training.py), with the
-reference's translate / flip / rotate augmentation redrawn every epoch if asked (augment.py); prepare_training_data
+reference's translate / flip / rotate augmentation redrawn every epoch if asked (augment.py); fine_tune_detector trains
+any number of the conv blocks with it, down to the whole network; prepare_training_data
 makes the labelled train and test timelapses of a recording from its files (core_functionality.setup_data), with the
 standardisation scaler measured on the GPU (estimate_stnd_scaler) and the labels read by load_labels_csv.
 The compute lives in csrc/libaxtrack_hip.so (C ABI: include/axtrack_hip.h); there is no CPU
@@ -19,7 +20,8 @@ from .detections import AxonDetections
 from .hotpath import Detector
 from .render import render_inference
 from .timelapse import Timelapse, estimate_stnd_scaler, load_labels_csv
-from .training import ConvBlockTrainer, ConvStageTrainer, HeadTrainer, fine_tune_head, yolo_targets
+from .training import (ConvBlockTrainer, ConvStageTrainer, ConvTrunkTrainer, HeadTrainer, fine_tune_head, fine_tune_detector,
+                       yolo_targets)
 from .augment import (Transform, transform_from_uniforms, draw_transform, augment_frames, transform_labels,
                       pos_label_rate)
 from .segment import (segment_microchannels, flood_initial_mask, segment_mask, save_final_mask,
@@ -27,7 +29,8 @@ from .segment import (segment_microchannels, flood_initial_mask, segment_mask, s
 
 __all__ = ['setup_inference', 'prepare_input_data', 'inference', 'visualize_inference', 'PKG_DIR', 'DEPLOYED_MODEL_DIR',
            '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse', 'render_inference',
-           'ConvBlockTrainer', 'ConvStageTrainer', 'HeadTrainer', 'fine_tune_head', 'yolo_targets',
+           'ConvBlockTrainer', 'ConvStageTrainer', 'ConvTrunkTrainer', 'HeadTrainer', 'fine_tune_head', 'fine_tune_detector',
+           'yolo_targets',
            'prepare_training_data', 'estimate_stnd_scaler', 'load_labels_csv',
            'Transform', 'transform_from_uniforms', 'draw_transform', 'augment_frames', 'transform_labels', 'pos_label_rate',
            'segment_microchannels', 'flood_initial_mask', 'segment_mask', 'save_final_mask', 'otsu_threshold_from_hist']

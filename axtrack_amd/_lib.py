@@ -122,6 +122,9 @@ SIGNATURES = {
     'axt_conv_trainer_read_stats': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_void_p]),
     'axt_maxpool2_forward': (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     'axt_maxpool2_backward': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    'axt_conv_trainer_create_strided': (c_int, [c_int] * 5 + [c_void_p] * 6 + [c_int, ctypes.POINTER(c_void_p)]),
+    'axt_tile_stacks': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),
     'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),

@@ -1879,7 +1879,8 @@ int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
 // d_feat != nullptr: stop after conv block 10 and copy its output, the input of the first linear layer, to
 // d_feat [n_items, 40960] (axt_cnn_features_frames); d_yolo is not written then. feat_block = 6: stop one block earlier and
 // copy d_act[6], [n_items, 20480]; feat_block = 4: run none of conv blocks 5..7 and copy d_act[4], [n_items, 81920]
-// (axt_cnn_block_features_frames)
+// (axt_cnn_block_features_frames); feat_block = 2: run conv blocks 0..2 only and copy d_act[2], [n_items, 327680], which is
+// chunk-sized, out after every chunk
 int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, int tstep, int n_items, int n_tiles,
                   const TileList &tl, float *d_yolo, hipStream_t st, float *d_feat = nullptr, int feat_block = 7)
 {
@@ -1892,9 +1893,16 @@ int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, 
                 const int rc = run_front_a(d, frames, Hf, Wf, t0, tstep, base + cb + c, n_tiles, tl, nc, c, st);
                 if (rc) return rc;
             }
+            if (d_feat && feat_block == 2) {
+                const size_t per_item = (size_t)80 * 64 * 64;
+                AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)(base + cb) * per_item, d->d_act[2], (size_t)nbb * per_item * sizeof(float),
+                                             hipMemcpyDeviceToDevice, st));
+                continue;
+            }
             const int rc = run_front_b(d, nbb, d->d_act[4] + (size_t)cb * 80 * 32 * 32, st);
             if (rc) return rc;
         }
+        if (d_feat && feat_block == 2) continue;
         if (d_feat) {
             const int rc = feat_block >= 6 ? run_back_conv(d, nb, st, feat_block) : AXT_OK;
             if (rc) return rc;
@@ -2139,7 +2147,8 @@ int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all,
 int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                                   const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream)
 {
-    AXT_REQUIRE(block == 4 || block == 6 || block == 7, "axt_cnn_block_features_frames: block %d is none of 4, 6, 7", block);
+    AXT_REQUIRE(block == 2 || block == 4 || block == 6 || block == 7, "axt_cnn_block_features_frames: block %d is none of 2, 4, 6, 7",
+                block);
     AXT_REQUIRE(det && d_frames && d_feat && h_tile_yx, "null argument");
     AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
     AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",

@@ -7,7 +7,8 @@
 //
 // Both products run over the im2col matrix X(q, r) of the batch, never stored:
 //   q = ci*9 + ky*3 + kx (the order of conv.weight's last three dimensions), r = b*H*W + h*W + w,
-//   X(q, r) = x[row(b)][ci][h+ky-1][w+kx-1], 0 outside the map.
+//   X(q, r) = x[row(b)][ci][h*s+ky-1][w*s+kx-1], 0 outside the input map, with the stride s = 1 or 2 a template parameter
+//   of the three products (s = 1 is the code it was) and (h, w) on the output map of (Hin - 1) / s + 1 rows.
 // Kernels
 //   conv_fwd_k       z[co][r] = sum_q W[co][q] X(q, r) + bias in ascending q (ci, ky, kx): every run of 16 q is one f32 FMA
 //                    chain from zero, the runs' sums are added in ascending order. Then y = gamma (z - mean) inv_sigma + beta,
@@ -29,10 +30,14 @@
 //                    gamma as it stands, by conv_bn_back_k's expressions (DzFromDF), or with batch statistics read from
 //                    the dz buffer that bn_batch_back_k<false> filled (DzStored): one kernel, templated on that source;
 //                    the same chains of 16 in ascending q. 64 ci x 64 r per workgroup. Reads nothing that the step
-//                    writes except the parameters: it runs before the step.
+//                    writes except the parameters: it runs before the step. At stride 2 r walks the input map and a tap
+//                    contributes where (h-ky+1, w-kx+1) are both even and their halves lie in the output map; every other q
+//                    of the ascending walk is staged as +0.0, so the chains keep their order and nothing is scattered.
 //   maxpool2_fwd_k   nn.MaxPool2d(2, 2), one thread per output element
 //   maxpool2_bwd_k   one thread per input element recomputes its window's winner (the first maximum under a strict >) and
 //                    writes the window's gradient or +0.0: every element is written, nothing is scattered
+//   tile_stacks_k    the raw [B][5][512][512] stacks of a batch of (frame, tile) items gathered from the frames, the input of
+//                    conv block 0: one thread per float4 (per float where the rows are not 16-byte aligned)
 // Batch statistics (train-mode BatchNorm), n = B*H*W elements per channel, one workgroup per output channel each:
 //   bn_batch_fwd_k   from the z that conv_fwd_k stashed: mu = sum z / n, then var = sum (z - mu)^2 / n in a second pass (never
 //                    E[z^2] - mu^2), inv = 1 / sqrt(var + 1e-5); running_mean and running_var move by the momentum (var
@@ -61,7 +66,10 @@ constexpr int64_t kMaxPoolElems = (int64_t)1 << 38;     // (one thread each, 256
 constexpr float kSlope = 0.1f;
 constexpr double kBnEps = 1e-5;
 
-struct Geom { int Ci, Co, H, W, HW, K9; };
+// H, W: the output map, on which z, dz and the per-channel kernels work. Hi, Wi: the input map, which only the three
+// products see: H = (Hi - 1) / stride + 1, so with stride 1 the two are one
+struct Geom { int Ci, Co, H, W, HW, K9, Hi, Wi, HWi, stride; };
+constexpr int kMaxInHW = 512, kMaxOutS1 = 128, kMaxOutS2 = 256;   // the limits of axt_conv_trainer_create_strided
 
 // y of BatchNorm in the one form both passes use, so that the backward pass sees the forward's sign
 __device__ inline float bn_y(float z, float mean, float inv_sigma, float gamma, float beta, float *zhat)
@@ -127,13 +135,20 @@ __device__ inline void adam_bias_gamma_beta(int tid, int co, int Co, const float
     mom_v[tid * Co + co] = v;
 }
 
-// x[row][ci][h+ky-1][w+kx-1] with q = ci*9 + ky*3 + kx; (b, h, w) already split; 0 outside the map
+// x[row][ci][h*S+ky-1][w*S+kx-1] with q = ci*9 + ky*3 + kx; (b, h, w) of the output map already split; 0 outside the
+// input map. S: the stride, 1 or 2, at compile time: S = 1 is the code it was.
+template <int S>
 __device__ inline float im2col(const float *__restrict__ x, size_t row, const Geom &g, int q, int h, int w)
 {
     const int ci = q / 9, tap = q - ci * 9, ky = tap / 3, kx = tap - ky * 3;
-    const int hh = h + ky - 1, ww = w + kx - 1;
-    if (hh < 0 || hh >= g.H || ww < 0 || ww >= g.W) return 0.f;
-    return x[(row * g.Ci + ci) * g.HW + hh * g.W + ww];
+    if (S == 1) {
+        const int hh = h + ky - 1, ww = w + kx - 1;
+        if (hh < 0 || hh >= g.H || ww < 0 || ww >= g.W) return 0.f;
+        return x[(row * g.Ci + ci) * g.HW + hh * g.W + ww];
+    }
+    const int hh = h * S + ky - 1, ww = w * S + kx - 1;
+    if (hh < 0 || hh >= g.Hi || ww < 0 || ww >= g.Wi) return 0.f;
+    return x[(row * g.Ci + ci) * g.HWi + hh * g.Wi + ww];
 }
 
 // acc[i][j] += (sum_k As[k][tm*4+i] * Bs[k][tn*4+j]): the tile's 16 products in one FMA chain from zero, k ascending, and
@@ -157,7 +172,8 @@ __device__ inline void tile_fma(const float (*As)[TPAD], const float (*Bs)[TPAD]
         for (int j = 0; j < 4; ++j) total[i][j] += acc[i][j];
 }
 
-// grid (r tiles, co tiles). x: table [., Ci*H*W], rows picked by index (NULL: 0..B-1). z, F: [B][Co][H*W].
+// grid (r tiles, co tiles). x: table [., Ci*Hi*Wi], rows picked by index (NULL: 0..B-1). z, F: [B][Co][H*W].
+template <int S>
 __global__ __launch_bounds__(256) void conv_fwd_k(const float *__restrict__ x, const int *__restrict__ index, int B, Geom g,
                                                   const float *__restrict__ Wt, const float *__restrict__ bias,
                                                   const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -180,7 +196,7 @@ __global__ __launch_bounds__(256) void conv_fwd_k(const float *__restrict__ x, c
             As[k][c] = (co0 + c < g.Co && q0 + k < g.K9) ? Wt[(size_t)(co0 + c) * g.K9 + q0 + k] : 0.f;
         }
         for (int k = tid / TN; k < TK; k += 256 / TN)
-            Bs[k][rl] = (r_ok && q0 + k < g.K9) ? im2col(x, row, g, q0 + k, h, w) : 0.f;
+            Bs[k][rl] = (r_ok && q0 + k < g.K9) ? im2col<S>(x, row, g, q0 + k, h, w) : 0.f;
         __syncthreads();
         tile_fma(As, Bs, tm, tn, acc);
         __syncthreads();
@@ -229,7 +245,8 @@ __global__ __launch_bounds__(256) void conv_bn_back_k(const float *__restrict__ 
     adam_bias_gamma_beta(tid, co, g.Co, s, bias, gamma, beta, mom_m, mom_v, a);
 }
 
-// grid (q tiles, co tiles, S). slab [S][Co][K9].
+// grid (q tiles, co tiles, splits). slab [splits][Co][K9].
+template <int S>
 __global__ __launch_bounds__(256) void conv_wgrad_k(const float *__restrict__ x, const int *__restrict__ index, int B, Geom g,
                                                     const float *__restrict__ dz, int rchunk, float *__restrict__ slab)
 {
@@ -247,7 +264,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_k(const float *__restrict__ x,
         const size_t row = r_ok ? (size_t)(index ? index[b] : b) : 0;
         for (int c = tid / TK; c < TM; c += 256 / TK) {
             As[kl][c] = (r_ok && co0 + c < g.Co) ? dz[((size_t)b * g.Co + co0 + c) * g.HW + p] : 0.f;
-            Bs[kl][c] = (r_ok && q0 + c < g.K9) ? im2col(x, row, g, q0 + c, h, w) : 0.f;
+            Bs[kl][c] = (r_ok && q0 + c < g.K9) ? im2col<S>(x, row, g, q0 + c, h, w) : 0.f;
         }
         __syncthreads();
         tile_fma(As, Bs, tm, tn, acc);
@@ -300,17 +317,21 @@ struct DzStored {
 
 // grid (r tiles, ci tiles). dx[b][ci][h][w] = sum_q Wt[co][ci][ky][kx] dz[b][co][h-ky+1][w-kx+1] in ascending q = co*9 + ky*3
 // + kx, 0 outside the map: conv_fwd_k's product with Co*9 as the depth and the weights read transposed and flipped where they
-// lie. dz: one of the two sources above; dx: [B][Ci][H*W].
-template <class Dz>
+// lie. dz: one of the two sources above; dx: [B][Ci][Hi*Wi].
+// S = 2: r walks the input map, and tap (ky, kx) reaches output (ho, wo) = ((h - ky + 1) / 2, (w - kx + 1) / 2) where both
+// numerators are even and (ho, wo) lies in the output map; every other q of the ascending walk is staged as +0.0, so the
+// chains and their order are those of S = 1 and each dx has one writer.
+template <class Dz, int S>
 __global__ __launch_bounds__(256) void conv_dgrad_k(Dz dz, int B, Geom g, const float *__restrict__ Wt, float *__restrict__ dx)
 {
+    const int HWx = S == 1 ? g.HW : g.HWi, Wx = S == 1 ? g.W : g.Wi;
     __shared__ __attribute__((aligned(16))) float As[TK][TPAD];      // W[co][ci][tap] as [q][ci]
     __shared__ __attribute__((aligned(16))) float Bs[TK][TPAD];      // dz of the shifted position as [q][r]
     const int tid = threadIdx.x, tm = tid / 16, tn = tid % 16;
-    const int r0 = blockIdx.x * TN, ci0 = blockIdx.y * TM, R = B * g.HW, K = g.Co * 9;
+    const int r0 = blockIdx.x * TN, ci0 = blockIdx.y * TM, R = B * HWx, K = g.Co * 9;
     const int rl = tid % TN, r = r0 + rl;
     const bool r_ok = r < R;
-    const int b = r_ok ? r / g.HW : 0, p = r - b * g.HW, h = p / g.W, w = p - h * g.W;
+    const int b = r_ok ? r / HWx : 0, p = r - b * HWx, h = p / Wx, w = p - h * Wx;
     float acc[4][4] = {};
     for (int q0 = 0; q0 < K; q0 += TK) {
         for (int i = tid; i < TM * TK; i += 256) {
@@ -319,8 +340,14 @@ __global__ __launch_bounds__(256) void conv_dgrad_k(Dz dz, int B, Geom g, const 
         }
         for (int k = tid / TN; k < TK; k += 256 / TN) {
             const int q = q0 + k, co = q / 9, tap = q - co * 9, ky = tap / 3, kx = tap - ky * 3;
-            const int hh = h - ky + 1, ww = w - kx + 1;
-            const bool ok = r_ok && q < K && hh >= 0 && hh < g.H && ww >= 0 && ww < g.W;
+            int hh = h - ky + 1, ww = w - kx + 1;
+            bool ok = r_ok && q < K;
+            if (S == 2) {
+                ok = ok && hh >= 0 && ww >= 0 && !((hh | ww) & 1);
+                hh >>= 1;
+                ww >>= 1;
+            }
+            ok = ok && hh >= 0 && hh < g.H && ww >= 0 && ww < g.W;
             Bs[k][rl] = ok ? dz(((size_t)b * g.Co + co) * g.HW + hh * g.W + ww, co) : 0.f;
         }
         __syncthreads();
@@ -334,7 +361,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_k(Dz dz, int B, Geom g, const 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int rr = r0 + tn * 4 + j;
-            if (rr < R) dx[chan_off(rr, g.Ci, g.HW, ci)] = acc[i][j];
+            if (rr < R) dx[chan_off(rr, g.Ci, HWx, ci)] = acc[i][j];
         }
     }
 }
@@ -384,6 +411,41 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_k(const float *__restrict__ 
         if (win == (h - 2 * ho) * 2 + (w - 2 * wo)) g = dout[(n * Ho + ho) * Wo + wo];
     }
     din[i] = g;
+}
+
+// The input of conv block 0 for a batch: out[b][c][y][x] = frames[t0 + f + c][ty*512 + y][tx*512 + x] with item index[b] =
+// f*n_tiles + k and (ty, tx) tile k's, +0.0 beyond H or W and for an item outside [0, n_items). One thread per V output
+// floats: V = 4 where W is a multiple of 4 (a tile's columns start at a multiple of 512, so a float4 lies wholly inside or
+// wholly outside a row and is aligned), else 1.
+constexpr int kStackC = AXT_IN_CH, kStackT = AXT_TILE;
+template <int V>
+__global__ __launch_bounds__(256) void tile_stacks_k(const float *__restrict__ frames, int H, int W, int t0, int n_items,
+                                                     int n_tiles, TileList tl, const int *__restrict__ index, int B,
+                                                     float *__restrict__ out)
+{
+    constexpr int per_row = kStackT / V, per_item = kStackC * kStackT * per_row;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)B * per_item) return;
+    const int b = (int)(i / per_item), rem = (int)(i - (size_t)b * per_item);
+    const int c = rem / (kStackT * per_row), y = rem / per_row % kStackT, x = rem % per_row * V;
+    const int item = index[b];
+    float v[V] = {};
+    if (item >= 0 && item < n_items) {
+        const int f = item / n_tiles, k = item - f * n_tiles;
+        const int yy = tl.yx[2 * k] * kStackT + y, xx = tl.yx[2 * k + 1] * kStackT + x;
+        if (yy < H && xx < W) {
+            const float *src = frames + ((size_t)(t0 + f + c) * H + yy) * W + xx;
+            if constexpr (V == 4) {
+                const float4 s = *reinterpret_cast<const float4 *>(src);
+                v[0] = s.x; v[1] = s.y; v[2] = s.z; v[3] = s.w;
+            } else {
+                v[0] = *src;
+            }
+        }
+    }
+    float *dst = out + i * V;
+    if constexpr (V == 4) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    else dst[0] = v[0];
 }
 
 // ---- batch statistics (train-mode BatchNorm) ----
@@ -459,7 +521,16 @@ __global__ __launch_bounds__(256) void bn_batch_back_k(const float *__restrict__
 }
 
 // split of the reduction over r = B*H*W for the weight gradient: about 1024 workgroups, runs a multiple of the tile depth
-int wgrad_max_split(const Geom &g) { return std::max(1, std::min(64, 1024 / (axt_cdiv(g.K9, TN) * axt_cdiv(g.Co, TM)))); }
+// A map beyond 64 x 64 (axt_conv_trainer_create_strided alone makes one) has so many r that 64 runs would leave a
+// few workgroups with very long chains of tiles: there the runs may number up to H*W / 64, at most 1024, while the slabs
+// stay within 16 M floats. Every shape axt_conv_trainer_create accepts keeps the split it had.
+int wgrad_max_split(const Geom &g)
+{
+    const int base = std::max(1, std::min(64, 1024 / (axt_cdiv(g.K9, TN) * axt_cdiv(g.Co, TM))));
+    if (g.H <= kMaxHW && g.W <= kMaxHW) return base;
+    const int by_slab = (int)(((int64_t)1 << 24) / ((int64_t)g.Co * g.K9));
+    return std::max(base, std::min(std::min(1024, g.HW / 64), by_slab));
+}
 
 void plan_wgrad(const Geom &g, int B, int *S, int *rchunk)
 {
@@ -543,22 +614,18 @@ void axt_conv_trainer_destroy(axt_conv_trainer *t)
     delete t;
 }
 
-int axt_conv_trainer_create(int Ci, int Co, int H, int W, const float *h_weight, const float *h_bias, const float *h_gamma,
-                            const float *h_beta, const float *h_mean, const float *h_var, int max_batch,
-                            axt_conv_trainer **out)
+// what both create entry points do once their arguments are checked. Hi, Wi: the input map.
+static int ct_create(const char *fn, int Ci, int Co, int Hi, int Wi, int stride, const float *h_weight, const float *h_bias,
+                     const float *h_gamma, const float *h_beta, const float *h_mean, const float *h_var, int max_batch,
+                     axt_conv_trainer **out)
 {
-    AXT_REQUIRE(out && h_weight && h_bias && h_gamma && h_beta && h_mean && h_var, "null argument");
-    AXT_REQUIRE(Ci >= 1 && Ci <= kMaxC && Co >= 1 && Co <= kMaxC, "axt_conv_trainer_create: channels %d -> %d not in [1,%d]",
-                Ci, Co, kMaxC);
-    AXT_REQUIRE(H >= 1 && H <= kMaxHW && W >= 1 && W <= kMaxHW, "axt_conv_trainer_create: map %d x %d not in [1,%d]", H, W,
-                kMaxHW);
-    AXT_REQUIRE(max_batch >= 1 && max_batch <= kMaxB, "axt_conv_trainer_create: max_batch %d not in [1,%d]", max_batch, kMaxB);
     axt_conv_trainer *t = new (std::nothrow) axt_conv_trainer;
     if (!t) {
-        axt_set_error("axt_conv_trainer_create: out of host memory");
+        axt_set_error("%s: out of host memory", fn);
         return AXT_ENOMEM;
     }
-    t->g = Geom{Ci, Co, H, W, H * W, Ci * 9};
+    const int H = (Hi - 1) / stride + 1, W = (Wi - 1) / stride + 1;
+    t->g = Geom{Ci, Co, H, W, H * W, Ci * 9, Hi, Wi, Hi * Wi, stride};
     t->max_batch = max_batch;
     t->var0.assign(h_var, h_var + Co);
     const size_t nw = (size_t)Co * Ci * 9, nz = (size_t)max_batch * Co * H * W;
@@ -582,11 +649,41 @@ int axt_conv_trainer_create(int Ci, int Co, int H, int W, const float *h_weight,
         hipMemcpy(t->mean, h_mean, Co * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(t->inv_sigma, is.data(), Co * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
-        axt_set_error("axt_conv_trainer_create: weight upload failed");
+        axt_set_error("%s: weight upload failed", fn);
         return fail(AXT_EHIP);
     }
     *out = t;
     return AXT_OK;
+}
+
+int axt_conv_trainer_create(int Ci, int Co, int H, int W, const float *h_weight, const float *h_bias, const float *h_gamma,
+                            const float *h_beta, const float *h_mean, const float *h_var, int max_batch,
+                            axt_conv_trainer **out)
+{
+    AXT_REQUIRE(out && h_weight && h_bias && h_gamma && h_beta && h_mean && h_var, "null argument");
+    AXT_REQUIRE(Ci >= 1 && Ci <= kMaxC && Co >= 1 && Co <= kMaxC, "axt_conv_trainer_create: channels %d -> %d not in [1,%d]",
+                Ci, Co, kMaxC);
+    AXT_REQUIRE(H >= 1 && H <= kMaxHW && W >= 1 && W <= kMaxHW, "axt_conv_trainer_create: map %d x %d not in [1,%d]", H, W,
+                kMaxHW);
+    AXT_REQUIRE(max_batch >= 1 && max_batch <= kMaxB, "axt_conv_trainer_create: max_batch %d not in [1,%d]", max_batch, kMaxB);
+    return ct_create("axt_conv_trainer_create", Ci, Co, H, W, 1, h_weight, h_bias, h_gamma, h_beta, h_mean, h_var, max_batch,
+                     out);
+}
+
+int axt_conv_trainer_create_strided(int Ci, int Co, int Hin, int Win, int stride, const float *h_weight, const float *h_bias,
+                                    const float *h_gamma, const float *h_beta, const float *h_mean, const float *h_var,
+                                    int max_batch, axt_conv_trainer **out)
+{
+    static const char fn[] = "axt_conv_trainer_create_strided";
+    AXT_REQUIRE(out && h_weight && h_bias && h_gamma && h_beta && h_mean && h_var, "%s: null argument", fn);
+    AXT_REQUIRE(stride == 1 || stride == 2, "%s: stride %d is neither 1 nor 2", fn, stride);
+    AXT_REQUIRE(Ci >= 1 && Ci <= kMaxC && Co >= 1 && Co <= kMaxC, "%s: channels %d -> %d not in [1,%d]", fn, Ci, Co, kMaxC);
+    AXT_REQUIRE(Hin >= 1 && Hin <= kMaxInHW && Win >= 1 && Win <= kMaxInHW, "%s: input map %d x %d not in [1,%d]", fn, Hin, Win,
+                kMaxInHW);
+    const int H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1, lim = stride == 2 ? kMaxOutS2 : kMaxOutS1;
+    AXT_REQUIRE(H <= lim && W <= lim, "%s: output map %d x %d of stride %d exceeds %d", fn, H, W, stride, lim);
+    AXT_REQUIRE(max_batch >= 1 && max_batch <= kMaxB, "%s: max_batch %d not in [1,%d]", fn, max_batch, kMaxB);
+    return ct_create(fn, Ci, Co, Hin, Win, stride, h_weight, h_bias, h_gamma, h_beta, h_mean, h_var, max_batch, out);
 }
 
 size_t axt_conv_trainer_device_bytes(const axt_conv_trainer *t) { return t ? t->bytes : 0; }
@@ -626,8 +723,8 @@ int axt_conv_trainer_forward(axt_conv_trainer *t, const float *d_in, const int32
     AXT_REQUIRE(!t->batch_stats || n >= 2, "axt_conv_trainer_forward: batch statistics need more than %d value per channel "
                 "(B * H * W >= 2)", n);
     const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Co, TM));
-    hipLaunchKernelGGL(conv_fwd_k, grid, dim3(256), 0, (hipStream_t)stream, d_in, d_index, B, g, t->w, t->p3, t->p3 + g.Co,
-                       t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->z, d_feat);
+    hipLaunchKernelGGL(g.stride == 2 ? conv_fwd_k<2> : conv_fwd_k<1>, grid, dim3(256), 0, (hipStream_t)stream, d_in, d_index, B,
+                       g, t->w, t->p3, t->p3 + g.Co, t->p3 + 2 * g.Co, t->mean, t->inv_sigma, t->z, d_feat);
     AXT_LAUNCH_CHECK();
     if (t->batch_stats) {
         const double m = t->momentum;
@@ -662,8 +759,8 @@ int axt_conv_trainer_step(axt_conv_trainer *t, const float *d_in, const int32_t 
     AXT_LAUNCH_CHECK();
     int S, rchunk;
     plan_wgrad(g, B, &S, &rchunk);
-    hipLaunchKernelGGL(conv_wgrad_k, dim3(axt_cdiv(g.K9, TN), axt_cdiv(g.Co, TM), S), dim3(256), 0, st, d_in, d_index, B, g,
-                       t->dz, rchunk, t->slab);
+    hipLaunchKernelGGL(g.stride == 2 ? conv_wgrad_k<2> : conv_wgrad_k<1>, dim3(axt_cdiv(g.K9, TN), axt_cdiv(g.Co, TM), S),
+                       dim3(256), 0, st, d_in, d_index, B, g, t->dz, rchunk, t->slab);
     AXT_LAUNCH_CHECK();
     const int nw = g.Co * g.K9;
     hipLaunchKernelGGL(conv_adam_w_k, dim3(axt_cdiv(nw, 256)), dim3(256), 0, st, t->w, t->mw, t->vw, nw, t->slab, S, a);
@@ -678,16 +775,19 @@ int axt_conv_trainer_input_grad(axt_conv_trainer *t, const float *d_dfeat, int B
     if (int rc = ct_check_stashed(t, B, "axt_conv_trainer_input_grad")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geom &g = t->g;
-    const dim3 grid(axt_cdiv(B * g.HW, TN), axt_cdiv(g.Ci, TM));
+    const dim3 grid(axt_cdiv(B * g.HWi, TN), axt_cdiv(g.Ci, TM));
+    const bool s2 = g.stride == 2;
     if (t->last_batch_stats) {
         // batch form: dz goes through the handle's dz buffer, which _step writes again with the same values from the same
         // inputs
         launch_bn_batch_back<false>(t, d_dfeat, B, AdamArgs{}, st);
         AXT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(conv_dgrad_k<DzStored>, grid, dim3(256), 0, st, DzStored{t->dz}, B, g, t->w, d_dx);
+        const auto kernel = s2 ? conv_dgrad_k<DzStored, 2> : conv_dgrad_k<DzStored, 1>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, DzStored{t->dz}, B, g, t->w, d_dx);
     } else {
         const DzFromDF dz = {d_dfeat, t->z, t->p3 + g.Co, t->p3 + 2 * g.Co, t->mean, t->inv_sigma};
-        hipLaunchKernelGGL(conv_dgrad_k<DzFromDF>, grid, dim3(256), 0, st, dz, B, g, t->w, d_dx);
+        const auto kernel = s2 ? conv_dgrad_k<DzFromDF, 2> : conv_dgrad_k<DzFromDF, 1>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, dz, B, g, t->w, d_dx);
     }
     AXT_LAUNCH_CHECK();
     return AXT_OK;
@@ -738,6 +838,39 @@ int axt_maxpool2_forward(const float *d_in, int64_t n_maps, int H, int W, float 
     const size_t n_out = (size_t)n_maps * (H / 2) * (W / 2);
     hipLaunchKernelGGL(maxpool2_fwd_k, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_in, n_out, H,
                        W, d_out);
+    AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+int axt_tile_stacks(const float *d_frames, int T_all, int H, int W, int t0, int n_frames, const int32_t *h_tile_yx,
+                    int n_tiles, const int32_t *d_index, int B, float *d_out, void *stream)
+{
+    static const char fn[] = "axt_tile_stacks";
+    AXT_REQUIRE(d_frames && h_tile_yx && d_index && d_out, "%s: null argument", fn);
+    AXT_REQUIRE(H >= 1 && W >= 1 && H <= kMaxPoolHW && W <= kMaxPoolHW, "%s: frames of %d x %d not in [1,%d]", fn, H, W,
+                kMaxPoolHW);
+    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "%s: n_tiles %d out of range [1,256]", fn, n_tiles);
+    AXT_REQUIRE(t0 >= 0 && n_frames >= 1 && n_frames <= (1 << 22) && (int64_t)t0 + n_frames + (kStackC - 1) <= T_all,
+                "%s: frames [%d,%d) + context exceed T_all=%d", fn, t0, t0 + n_frames, T_all);
+    AXT_REQUIRE(B >= 1 && B <= 1024, "%s: batch %d not in [1,1024]", fn, B);
+    TileList tl;
+    tl.n = n_tiles;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * kStackT < H && tx * kStackT < W, "%s: tile %d (%d,%d) outside %dx%d", fn, k, ty,
+                    tx, H, W);
+        tl.yx[2 * k] = (short)ty;
+        tl.yx[2 * k + 1] = (short)tx;
+    }
+    const bool vec = W % 4 == 0 && (uintptr_t)d_frames % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+    const size_t n = (size_t)B * kStackC * kStackT * kStackT / (vec ? 4 : 1);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (vec)
+        hipLaunchKernelGGL(tile_stacks_k<4>, grid, dim3(256), 0, (hipStream_t)stream, d_frames, H, W, t0, n_frames * n_tiles,
+                           n_tiles, tl, d_index, B, d_out);
+    else
+        hipLaunchKernelGGL(tile_stacks_k<1>, grid, dim3(256), 0, (hipStream_t)stream, d_frames, H, W, t0, n_frames * n_tiles,
+                           n_tiles, tl, d_index, B, d_out);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
 }

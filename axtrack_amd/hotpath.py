@@ -13,6 +13,8 @@ TILE, S, CELLS = 512, 12, 144
 FEATURES = 160 * 16 * 16                # what the first linear layer reads per tile (model.py:50-53)
 # Detector.features_frames(block=): floats per item after conv block 7 / 6 / 4
 BLOCK_FEATURES = {7: FEATURES, 6: 80 * 16 * 16, 4: 80 * 32 * 32}
+# Detector.trunk_features_frames(block=): floats per item after conv block 2 and its pool
+TRUNK_FEATURES = {2: 80 * 64 * 64}
 CONF_FLOOR = float(np.float32(0.55))   # all_conf_thrs.min() as f32 (AxonDetections.py:76,122)
 MAX_PX_ASSOC_DIST = 500                # AxonDetections.py:77
 AXON_BOX_SIZE = 70                     # AxonDetections.py:78
@@ -183,7 +185,18 @@ class Detector:
         what training.ConvStageTrainer reads; block=7 is the default table."""
         if block not in BLOCK_FEATURES:
             raise ValueError(f'block must be one of {sorted(BLOCK_FEATURES)}, got {block}')
-        width = BLOCK_FEATURES[block]
+        return self._block_table(frames, tile_yx, t0, n_frames, out, block, BLOCK_FEATURES[block])
+
+    def trunk_features_frames(self, frames, tile_yx, block=2, t0=0, n_frames=None, out=None):
+        """features_frames for the taps in front of the last stage: block=2 -> [n_frames * n_tiles, 327680] =
+        [item, 80, 64, 64], conv block 2's output after its pool, the bytes of the detector's own buffer
+        (axt_cnn_block_features_frames); conv blocks 3..7 do not run. What training.ConvTrunkTrainer(first_block=3) reads.
+        The widths are TRUNK_FEATURES; frames, tile_yx, t0, n_frames and out as features_frames takes them."""
+        if block not in TRUNK_FEATURES:
+            raise ValueError(f'block must be one of {sorted(TRUNK_FEATURES)}, got {block}')
+        return self._block_table(frames, tile_yx, t0, n_frames, out, block, TRUNK_FEATURES[block])
+
+    def _block_table(self, frames, tile_yx, t0, n_frames, out, block, width):
         T_all, H, W = frames.shape
         if n_frames is None:
             n_frames = T_all - 4 - t0
@@ -225,6 +238,41 @@ class Detector:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.axt_cnn_back(self._h, n_frames * n_tiles, out.data_ptr(), _stream()), 'axt_cnn_back')
         return out
+
+
+def tile_stacks(frames, tile_yx, index, out=None):
+    """The raw 5-frame stacks of a batch of (frame, tile) items, the input of conv block 0 (axt_tile_stacks): frames f32
+    [T_all, H, W] on the GPU, index: item numbers frame * n_tiles + tile in the order of Detector.features_frames (an i32
+    tensor on the GPU, or host integers, which are checked) -> f32 [B, 5, 512, 512]: channel c of item (f, k) is frame f + c,
+    from the tile's origin, +0.0 beyond H or W. out: a contiguous f32 tensor of at least B stacks to write into."""
+    _require_gpu()
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() == 3 and frames.is_contiguous()
+            and frames.dtype == torch.float32):
+        raise ValueError('frames must be a contiguous f32 tensor [T_all, H, W] on the GPU')
+    T_all, H, W = frames.shape
+    n_frames = T_all - 4
+    if n_frames < 1:
+        raise ValueError(f'{T_all} frames hold no stack of 5')
+    tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+    if isinstance(index, torch.Tensor):
+        index = index.to(frames.device, torch.int32).contiguous().reshape(-1)
+    else:
+        index = np.ascontiguousarray(index, np.int64).reshape(-1)
+        if ((index < 0) | (index >= n_frames * len(tile_yx))).any():
+            raise IndexError(f'item outside the {n_frames * len(tile_yx)} of {n_frames} frames x {len(tile_yx)} tiles')
+        index = torch.from_numpy(index.astype(np.int32)).to(frames.device)
+    B = len(index)
+    if out is None:
+        out = torch.empty((B, 5, TILE, TILE), dtype=torch.float32, device=frames.device)
+    elif not (out.is_contiguous() and out.dtype == torch.float32 and out.device == frames.device
+              and out.numel() >= B * 5 * TILE * TILE):
+        raise ValueError(f'out must be a contiguous f32 tensor of at least [{B}, 5, {TILE}, {TILE}] on {frames.device}')
+    else:
+        out = out.reshape(-1)[:B * 5 * TILE * TILE].view(B, 5, TILE, TILE)
+    with torch.cuda.device(frames.device):
+        _lib.check(_lib.load().axt_tile_stacks(frames.data_ptr(), T_all, H, W, 0, n_frames, tile_yx.ctypes.data, len(tile_yx),
+                                               index.data_ptr(), B, out.data_ptr(), _stream()), 'axt_tile_stacks')
+    return out
 
 
 def preprocess_u16(raw, mask=None, offset=0.0, clip_lower=0.0, log_correct=True, scale=1.0, out=None):

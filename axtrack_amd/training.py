@@ -12,7 +12,11 @@ recomputed from the warped frames, which costs about one trunk pass per epoch.
 The last one to three conv blocks can be trained jointly with the head (csrc/train_conv.hip): ConvBlockTrainer is one
 block, ConvStageTrainer the last stage (conv blocks 5 and 6, the 2 x 2 max-pool, conv block 7), either with BatchNorm's
 running statistics or with train-mode BatchNorm. The cached table is then the trunk's output that many blocks earlier.
-fine_tune_head's docstring says what each option (train_conv_blocks, train_last_conv, bn_batch_stats) does to a step."""
+fine_tune_head's docstring says what each option (train_conv_blocks, train_last_conv, bn_batch_stats) does to a step.
+
+fine_tune_detector goes on to every depth: ConvTrunkTrainer chains any run of the last conv blocks with their pools,
+ConvBlockTrainer(stride=2) is a block of the stride-2 front, and the input is the block-2 table (depths 4, 5) or the raw
+stacks gathered per batch (depths 6..8). Both functions share one step loop (_fine_tune)."""
 import ctypes
 import functools
 import os
@@ -265,11 +269,17 @@ class ConvBlockTrainer(_HandleTrainer):
     or with batch_stats=True as nn.BatchNorm2d in train mode (momentum: its momentum): forward normalises the batch with
     its own mean and biased variance and moves running_mean, running_var (by the unbiased variance) and the batch count;
     step and input_grad take the gradients through the statistics, and conv.bias, whose gradient is then 0 by definition,
-    moves by its weight decay alone. A batch of fewer than 2 values per channel is a ValueError then."""
+    moves by its weight decay alone. A batch of fewer than 2 values per channel is a ValueError then.
+    stride, in_size: a convolution of stride 1 or 2 on input maps of in_size = (Hin, Win) (default: map_size), up to
+    512 x 512 (axt_conv_trainer_create_strided); the tables are then [n, Ci*Hin*Win] in and [B, Co*H*W] out with
+    H = (Hin - 1) // stride + 1. With stride=1 and no in_size the trainer makes the calls it always made, on maps up to
+    64 x 64."""
     _CREATE, _DESTROY, _DEVICE_BYTES = (f'axt_conv_trainer_{f}' for f in ('create', 'destroy', 'device_bytes'))
 
     def __init__(self, state_dict, block_key=LAST_CONV_BLOCK, parameters=None, map_size=(16, 16), max_batch=64,
-                 device='cuda:0', batch_stats=False, momentum=0.1):
+                 device='cuda:0', batch_stats=False, momentum=0.1, stride=1, in_size=None):
+        if isinstance(stride, bool) or stride not in (1, 2):
+            raise ValueError(f'stride must be 1 or 2, got {stride!r}')
         self.block_key = block_key
         self.keys = tuple(f'{block_key}.{k}' for k in CONV_SUFFIXES + CONV_STATS)
         super().__init__(state_dict, self.keys, parameters, max_batch, device)
@@ -277,9 +287,16 @@ class ConvBlockTrainer(_HandleTrainer):
         if w[0].ndim != 4 or w[0].shape[2:] != (3, 3) or any(a.shape != (w[0].shape[0],) for a in w[1:]):
             raise ValueError(f'not a 3x3 conv block: {[a.shape for a in w]}')
         self.Co, self.Ci = int(w[0].shape[0]), int(w[0].shape[1])
-        self.H, self.W = (int(v) for v in map_size)
-        self.in_width, self.out_width = self.Ci * self.H * self.W, self.Co * self.H * self.W
-        self._create(self.Ci, self.Co, self.H, self.W, *[a.ctypes.data for a in w])
+        self.stride = int(stride)
+        if self.stride == 1 and in_size is None:
+            self.H, self.W = self.Hin, self.Win = tuple(int(v) for v in map_size)
+            self._create(self.Ci, self.Co, self.H, self.W, *[a.ctypes.data for a in w])
+        else:
+            self.Hin, self.Win = (int(v) for v in (map_size if in_size is None else in_size))
+            self.H, self.W = (self.Hin - 1) // self.stride + 1, (self.Win - 1) // self.stride + 1
+            self._CREATE = 'axt_conv_trainer_create_strided'
+            self._create(self.Ci, self.Co, self.Hin, self.Win, self.stride, *[a.ctypes.data for a in w])
+        self.in_width, self.out_width = self.Ci * self.Hin * self.Win, self.Co * self.H * self.W
         self.batch_stats = bool(batch_stats)
         self.momentum = float(momentum) if self.batch_stats else momentum       # read with batch statistics only
         if self.batch_stats:                            # a trainer that never asks makes the calls it always made
@@ -290,7 +307,7 @@ class ConvBlockTrainer(_HandleTrainer):
                            'axt_conv_trainer_set_batch_stats')
 
     def forward(self, inputs, index=None):
-        """inputs f32 [n_items, Ci*H*W] on the GPU, index: which rows form the batch (default: all) -> [B, Co*H*W]."""
+        """inputs f32 [n_items, Ci*Hin*Win] on the GPU, index: which rows form the batch (default: all) -> [B, Co*H*W]."""
         self._check_table(inputs, self.in_width, 'inputs')
         index = self._index(index, inputs.shape[0])
         out = torch.empty((len(index), self.out_width), dtype=torch.float32, device=self.device)
@@ -515,6 +532,109 @@ class ConvStageTrainer:
         return sd
 
 
+class ConvTrunkTrainer:
+    """Conv blocks first_block..7 of the state dict as ConvBlockTrainers chained on the device, a 2 x 2 max-pool behind
+    every block whose `pooled` flag is set; the last n_trained of them are trained, the blocks in front run forward only and
+    never step. forward / backward_and_step work on batches picked by index from a table [n_items, in_width] of
+    first_block's inputs: Detector.trunk_features_frames(block=2) for first_block=3, hotpath.tile_stacks' stacks (as
+    [B, 5*512*512]) for first_block=0. forward's output is what HeadTrainer.forward reads.
+    block_keys, strides, pooled: per block first_block..7 its state-dict prefix, its convolution's stride and whether a pool
+    follows it; in_size: the (H, W) of first_block's input maps. Defaults: the deployed architecture's, from hotpath's table
+    of conv blocks, with stride 2 for conv blocks 0 and 1. batch_stats, momentum: train-mode BatchNorm
+    (ConvBlockTrainer's) in the trained blocks; a forward-only block keeps its running statistics."""
+
+    def __init__(self, state_dict, first_block, n_trained, parameters=None, max_batch=64, device='cuda:0', batch_stats=False,
+                 momentum=0.1, block_keys=None, strides=None, pooled=None, in_size=None):
+        from .hotpath import CONV_BLOCKS, CONV_MAP_SIDE, CONV_POOLED, conv_block_key
+        n_all = len(CONV_BLOCKS)
+        if isinstance(first_block, bool) or first_block not in range(n_all):
+            raise ValueError(f'first_block must be in 0..{n_all - 1}, got {first_block!r}')
+        self.numbers = list(range(first_block, n_all))
+        n = len(self.numbers)
+        if isinstance(n_trained, bool) or n_trained not in range(n + 1):
+            raise ValueError(f'n_trained must be in 0..{n} for first_block={first_block}, got {n_trained!r}')
+        if block_keys is None:
+            block_keys = [conv_block_key(i) for i in self.numbers]
+        if strides is None:
+            strides = [2 if i < 2 else 1 for i in self.numbers]
+        if pooled is None:
+            pooled = [CONV_POOLED[i] for i in self.numbers]
+        if in_size is None:
+            in_size = (CONV_MAP_SIDE[first_block] * (2 if first_block < 2 else 1),) * 2
+        if not len(block_keys) == len(strides) == len(pooled) == n:
+            raise ValueError(f'block_keys, strides and pooled describe conv blocks {first_block}..{n_all - 1}: {n} entries each')
+        self.first_block, self.n_trained = int(first_block), int(n_trained)
+        self.trained = [k >= n - self.n_trained for k in range(n)]
+        self.pooled = [bool(p) for p in pooled]
+        self.batch_stats = bool(batch_stats)
+        self.blocks = []
+        h, w = (int(v) for v in in_size)
+        for key, s, pool, tr in zip(block_keys, strides, self.pooled, self.trained):
+            ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+            if pool and (ho < 2 or wo < 2):
+                raise ValueError(f'{key}: maps of {ho} x {wo} leave its max-pool nothing')
+            old = s == 1 and h <= 64 and w <= 64                    # the maps ConvBlockTrainer always took: its own calls
+            self.blocks.append(ConvBlockTrainer(state_dict, key, parameters, map_size=(h, w), max_batch=max_batch,
+                                                device=device, batch_stats=self.batch_stats and tr, momentum=momentum,
+                                                stride=s, in_size=None if old else (h, w)))
+            h, w = (ho // 2, wo // 2) if pool else (ho, wo)
+        for a, b in zip(self.blocks, self.blocks[1:]):
+            if a.Co != b.Ci:
+                raise ValueError(f'{a.block_key} writes {a.Co} channels, {b.block_key} reads {b.Ci}')
+        self.device, self.max_batch = self.blocks[0].device, int(max_batch)
+        self.in_width = self.blocks[0].in_width
+        self.out_width = self.blocks[-1].Co * h * w
+        self._sd = state_dict
+        self._kept = None
+
+    @property
+    def device_bytes(self):
+        return sum(b.device_bytes for b in self.blocks)
+
+    def forward(self, table, batch=None):
+        """table f32 [n_items, in_width] on the GPU, batch: which rows (default: all) -> [B, out_width], the head's input
+        rows. Every block's input and output are kept for backward_and_step."""
+        x, rows, kept = table, batch, []
+        for blk, pool in zip(self.blocks, self.pooled):
+            f = blk.forward(x, rows)
+            out = maxpool2_forward(f, blk.H, blk.W).reshape(f.shape[0], -1) if pool else f
+            kept.append((x, rows, f))
+            x, rows = out, _first_rows(f.shape[0], self.device)
+        self._kept = kept
+        return x
+
+    def backward_and_step(self, table, batch, dfeat, lr=None, eps=ADAM_EPS):
+        """From dfeat [B, out_width], the gradient with respect to forward's output of the same batch: back to front
+        through the trained blocks, per block the gradient of the pool behind it, its input gradient where a trained block
+        lies in front of it, then its Adam step -- so every gradient is taken from weights that have not moved yet. A
+        forward-only block is never reached. table, batch: what forward read. Returns the gradients handed on, named per
+        link by the conv block i whose output they belong to: 'p{i}' with respect to its pooled output, 'f{i}' with respect to
+        its output in front of the pool (or the output itself where no pool follows)."""
+        if self._kept is None or self._kept[-1][2].shape[0] != dfeat.shape[0]:
+            raise ValueError('backward_and_step needs forward() on this batch first')
+        grads, g = {}, dfeat
+        first_trained = len(self.blocks) - self.n_trained
+        for k in range(len(self.blocks) - 1, first_trained - 1, -1):
+            blk, (x, rows, f) = self.blocks[k], self._kept[k]          # (the first block's x, rows are table, batch)
+            if self.pooled[k]:
+                g = grads[f'f{self.numbers[k]}'] = maxpool2_backward(f, g, blk.H, blk.W).reshape(f.shape)
+            dx = blk.input_grad(g) if k > first_trained else None
+            blk.step(x, rows, g, lr=lr, eps=eps)
+            if dx is not None:
+                grads[f"{'p' if self.pooled[k - 1] else 'f'}{self.numbers[k - 1]}"] = g = dx
+        return grads
+
+    def state_dict(self, base=None):
+        """The state dict this trunk was built from (or `base`) with the trained blocks' four tensors each replaced (numpy
+        f32), and with batch_stats their running statistics and batch counts (ConvBlockTrainer.state_dict); everything
+        else, a forward-only block's tensors included, passes through."""
+        sd = dict(self._sd if base is None else base)
+        for blk, trained in zip(self.blocks, self.trained):
+            if trained:
+                sd = blk.state_dict(sd)
+        return sd
+
+
 def save_checkpoint(state_dict, filename):
     """The reference's checkpoint layout (utils.py:258-264) without optimiser state; setup_inference(weights=filename)
     and the reference's load_checkpoint read it."""
@@ -615,8 +735,6 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
     dict and the checkpoints carry them, and the every-tenth-epoch evaluation reads them. A forward-only block
     (train_conv_blocks=2's conv block 5) and the frozen trunk keep their running statistics. With the head alone
     (train_conv_blocks=0) it is a ValueError: nothing would use it. Default False: running statistics, never updated."""
-    import pandas as pd
-    from .hotpath import Detector, BLOCK_FEATURES
     if train_conv_blocks is None:
         depth = 1 if train_last_conv else 0
     else:
@@ -625,17 +743,98 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         depth = int(train_conv_blocks)
         if train_last_conv and depth != 1:
             raise ValueError(f'train_last_conv=True means train_conv_blocks=1, not {depth}')
+    return _fine_tune('fine_tune_head', timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms,
+                      transforms, min_pos_rate, max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum)
+
+
+# fine_tune_detector's depth (how many of the last conv blocks train) -> (the conv block whose output the cached table
+# holds, None: no table, the raw stacks are gathered per batch; the first conv block the trunk trainer runs, None: no trunk)
+DEPTH_INPUT = {0: (7, None), 1: (6, 7), 2: (4, 5), 3: (4, 5), 4: (2, 3), 5: (2, 3), 6: (None, 0), 7: (None, 0), 8: (None, 0)}
+
+
+def fine_tune_detector(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
+                       use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
+                       metrics_every=10, train_conv_blocks=0, bn_batch_stats=False, bn_momentum=0.1):
+    """fine_tune_head for every depth: train the head and the last train_conv_blocks (0..8, default 0) conv blocks of
+    `model` -> (state_dict, history). Every other argument, the history, the checkpoints, the augmentation and the
+    evaluation are fine_tune_head's. Depths 0..3 run exactly what fine_tune_head runs. Beyond (DEPTH_INPUT, ConvTrunkTrainer):
+
+      4  the cached table is conv block 2's output after its pool (Detector.trunk_features_frames(block=2), 1.3 MB per
+         item); conv block 3 runs forward only and comes back as it went in, conv blocks 4..7 train
+      5  the same table; conv blocks 3..7 train
+      6  no table: every batch gathers its raw 5-frame stacks from the frames (hotpath.tile_stacks); conv blocks 0 and 1,
+         the stride-2 front, run forward only, conv blocks 2..7 train
+      7  raw stacks; conv block 0 runs forward only, conv blocks 1..7 train
+      8  raw stacks; all eight conv blocks train, so a detector can be trained from a random start
+
+    A step is the chain's forwards with the three pools, head forward, loss, the head's input gradient, then back to front
+    per trained block the gradient of the pool behind it, its input gradient, its step, and last the head's step: every
+    gradient is taken from weights that have not moved. bn_batch_stats works in the trained blocks at every depth; a
+    forward-only block keeps its running statistics. At depths 6..8 an augmented epoch recomputes no table: the stacks are
+    gathered from the warped frames."""
+    if isinstance(train_conv_blocks, bool) or train_conv_blocks not in DEPTH_INPUT:
+        raise ValueError(f'train_conv_blocks must be in 0..{max(DEPTH_INPUT)}, got {train_conv_blocks!r}')
+    return _fine_tune('fine_tune_detector', timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms,
+                      transforms, min_pos_rate, max_redraws, test_timelapse, metrics_every, int(train_conv_blocks),
+                      bn_batch_stats, bn_momentum)
+
+
+class _TableInput:
+    """The step loop's input at the depths that read a cached table of the frozen trunk's output after conv block `block`:
+    fill() computes it from the epoch's frames, pick() hands a batch's rows to whoever reads them."""
+
+    def __init__(self, detector, block, n_rows=None):
+        from .hotpath import BLOCK_FEATURES, TRUNK_FEATURES
+        self.detector, self.block = detector, block
+        self._tap = detector.features_frames if block in BLOCK_FEATURES else detector.trunk_features_frames
+        width = BLOCK_FEATURES[block] if block in BLOCK_FEATURES else TRUNK_FEATURES[block]
+        # augmented epochs keep different tiles: one table for all tiles (n_rows), of which an epoch uses the first rows
+        self.out = None if n_rows is None else torch.empty((n_rows, width), dtype=torch.float32, device=detector.device)
+
+    def fill(self, frames, tile_yx):
+        self.table = self._tap(frames, tile_yx, out=self.out, block=self.block)
+        return self.table.shape[0]
+
+    def pick(self, batch):
+        return self.table, batch
+
+
+class _StackInput:
+    """The step loop's input at the depths that train the front: nothing is cached (a stack is 5.2 MB per item), pick()
+    gathers the batch's raw stacks from the epoch's frames into one buffer, of which the trunk reads rows 0..B-1."""
+
+    def __init__(self, max_batch, device):
+        from .hotpath import TILE
+        self.buf = torch.empty((max_batch, 5 * TILE * TILE), dtype=torch.float32, device=device)
+
+    def fill(self, frames, tile_yx):
+        self.frames, self.tile_yx = frames, np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+        return (frames.shape[0] - 4) * len(self.tile_yx)
+
+    def pick(self, batch):
+        from .hotpath import tile_stacks
+        stacks = tile_stacks(self.frames, self.tile_yx, batch, out=self.buf)
+        return stacks.view(len(batch), -1), _first_rows(len(batch), self.buf.device)
+
+
+def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms, transforms, min_pos_rate,
+               max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum):
+    """fine_tune_head and fine_tune_detector behind their own checks of the depth: the rest of the checks, the set-up and
+    the one step loop. The trunk (none, one block, the last stage, or a longer chain) and the input it reads (a cached
+    table, or stacks gathered per batch) are chosen by the depth; the loop is the same for all."""
+    import pandas as pd
+    from .hotpath import Detector
     if bn_batch_stats and depth == 0:
         raise ValueError('bn_batch_stats=True needs trained conv blocks (train_conv_blocks >= 1): the head has no BatchNorm')
     if bn_batch_stats and not 0 < float(bn_momentum) <= 1:
         raise ValueError(f'bn_momentum must be in (0, 1], got {bn_momentum!r}')
-    block = (7, 6, 4, 4)[depth]                         # which conv block's output the cached table holds
+    block, first_block = DEPTH_INPUT[depth]             # which conv block's output the cached table holds; the trunk's first
     for tl in (timelapse, test_timelapse):
         if getattr(tl, 'frame_sharded', False):
             raise NotImplementedError('fine-tuning on a frame-sharded timelapse is not implemented: train in a single '
                                       'process on the whole timelapse')
     if model is None:
-        raise ValueError('fine_tune_head needs the model to start from: a Detector or a state dict')
+        raise ValueError(f'{name} needs the model to start from: a Detector or a state dict')
     explicit_labels = labels is not None
     if labels is None:
         labels = getattr(timelapse, 'labels', None)
@@ -666,9 +865,8 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         unknown = [k for k in (use_transforms or []) if k not in augment.TRANSFORM_KEYS]
         if unknown:
             raise ValueError(f'unknown augmentation keys {unknown}; known: {augment.TRANSFORM_KEYS}')
-        # the kept tiles change with every draw: one feature table for all tiles, of which an epoch uses the first rows
-        table = torch.empty((len(timelapse) * timelapse.ytiles * timelapse.xtiles, BLOCK_FEATURES[block]),
-                            dtype=torch.float32, device=timelapse.device)
+        n_rows = len(timelapse) * timelapse.ytiles * timelapse.xtiles
+        source = _TableInput(detector, block, n_rows) if block is not None else _StackInput(bs, timelapse.device)
         warped = torch.empty_like(timelapse.frames)
         label_xy = augment.label_floats(labels)
         label_xy = (*label_xy, np.full(len(labels), label_xy[0].shape[1], np.int32))
@@ -679,11 +877,18 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         trainer = HeadTrainer(sd, P, max_batch=bs, device=timelapse.device)
     else:
         tile_yx = timelapse.tile_yx
-        features = detector.features_frames(timelapse.frames, tile_yx, block=block)
+        n_items = len(timelapse) * len(np.reshape(tile_yx, (-1, 2)))
+        source = _TableInput(detector, block) if block is not None else _StackInput(min(bs, n_items), timelapse.device)
+        n_items = source.fill(timelapse.frames, tile_yx)
         targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
-        trainer = HeadTrainer(sd, P, max_batch=min(bs, features.shape[0]), device=timelapse.device)
-    # the trained conv blocks in front of the head: the stage, one block, or none. Their step calls take the same arguments.
-    if depth >= 2:
+        trainer = HeadTrainer(sd, P, max_batch=min(bs, n_items), device=timelapse.device)
+    # the trained conv blocks in front of the head: a chain from first_block on, the stage, one block, or none. Their step
+    # calls take the same arguments.
+    if depth >= 4:
+        trunk = ConvTrunkTrainer(sd, first_block, depth, P, max_batch=trainer.max_batch, device=timelapse.device,
+                                 batch_stats=bn_batch_stats, momentum=bn_momentum)
+        trunk_step = trunk.backward_and_step
+    elif depth >= 2:
         trunk = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device,
                                  batch_stats=bn_batch_stats, momentum=bn_momentum)
         trunk_step = trunk.backward_and_step
@@ -707,23 +912,24 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
             tf, warped, tile_yx, lab = _augmented_epoch(timelapse.frames, label_xy, None if transforms is None else
                                                         transforms[epoch], draw, min_pos_rate, max_redraws, warped)
             used.append(tf)
-            features = detector.features_frames(warped, tile_yx, out=table, block=block)
+            n_items = source.fill(warped, tile_yx)
             targets = yolo_targets(lab, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         lr = learning_rate(P['LR'], P['LR_DECAYRATE'], epoch)
         rows = []
-        for batch in epoch_batches(features.shape[0], bs, P['SHUFFLE'], P['DROP_LAST'], rng):
+        for batch in epoch_batches(n_items, bs, P['SHUFFLE'], P['DROP_LAST'], rng):
             # what the head reads: the trunk's output for this batch, of which it takes rows 0..B-1, or the cached table
+            features, rows_in = source.pick(batch)
             if trunk:
-                feats, head_rows = trunk.forward(features, batch), _first_rows(len(batch), trainer.device)
+                feats, head_rows = trunk.forward(features, rows_in), _first_rows(len(batch), trainer.device)
             else:
-                feats, head_rows = features, batch
+                feats, head_rows = features, rows_in
             yolo = trainer.forward(feats, head_rows)
             comp, dy = trainer.loss(yolo, targets, batch)
             # the order: the head's input gradient is taken from the head's weights before they move, so before any step;
             # then the trunk steps (back to front, each block's input gradient before its own step), then the head
             if trunk:
                 dfeat = trainer.input_grad(dy)
-                trunk_step(features, batch, dfeat, lr=lr)
+                trunk_step(features, rows_in, dfeat, lr=lr)
             trainer.step(feats, head_rows, dy, lr=lr)
             rows.append([comp[k] for k in COMPONENTS])
         history[epoch] = np.mean(np.array(rows, np.float64).reshape(-1, 5), axis=0)

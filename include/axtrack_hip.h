@@ -110,8 +110,8 @@ int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all,
  * axt_cnn_features_frames' arguments and chunking. block = 7: exactly axt_cnn_features_frames. block = 6: stops before conv
  * block 7 (ConvNet.ConvBlock_10); d_feat f32 [n_frames*n_tiles, 20480] is [item, 80, 16, 16] NCHW, the output of
  * ConvBlock_8 after its max-pool. block = 4: stops before conv block 5 (ConvNet.ConvBlock_7); d_feat f32
- * [n_frames*n_tiles, 81920] is [item, 80, 32, 32] NCHW, the output of ConvBlock_5 after its max-pool. Any other block:
- * AXT_EINVAL. */
+ * [n_frames*n_tiles, 81920] is [item, 80, 32, 32] NCHW, the output of ConvBlock_5 after its max-pool. block = 2
+ * (axtrack_hip_trunk.h): stops before conv block 3; [item, 80, 64, 64]. Any other block: AXT_EINVAL. */
 int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                                   const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream);
 
@@ -663,6 +663,11 @@ int axt_conv_trainer_step(axt_conv_trainer *tr, const float *d_in, const int32_t
 /* Fine-tuning of the whole last conv stage (conv blocks 5, 6, the max-pool, conv block 7) with the head: the conv trainer's
  * input gradient, and the 2 x 2 max-pool with its gradient. Declared in a header of their own, part of this interface. */
 #include "axtrack_hip_stage.h"
+
+/* Fine-tuning of every conv block: a conv trainer with a stride of 1 or 2 on larger maps, the batch gather of the raw
+ * 5-frame tile stacks, and block = 2 of axt_cnn_block_features_frames. Declared in a header of their own, part of this
+ * interface. */
+#include "axtrack_hip_trunk.h"
 
 /* Training augmentation of a whole timelapse in one launch (data_utils.transform_X: translate, then flip, then rotate;
  * DESIGN.md 6.8e). d_in f32 [T, H, W]; d_out the same shape, not overlapping d_in (AXT_EINVAL: the warp is a gather).
