@@ -125,6 +125,10 @@ SIGNATURES = {
     'axt_conv_trainer_create_strided': (c_int, [c_int] * 5 + [c_void_p] * 6 + [c_int, ctypes.POINTER(c_void_p)]),
     'axt_tile_stacks': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                 c_void_p]),
+    'axt_detector_load_conv_block': (c_int, [c_void_p, c_int] + [c_void_p] * 7),
+    'axt_detector_load_linear': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'axt_conv_trainer_export': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    'axt_head_trainer_export': (c_int, [c_void_p, c_void_p, c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),
     'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),

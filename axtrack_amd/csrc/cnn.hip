@@ -19,6 +19,7 @@
 // Numerics: f32 MFMA on gfx950 is a k-ordered chain of f32 FMAs (exact f32, no reduced precision).
 // BatchNorm is folded in f64 at pack time and rounded once to f32.
 #include "axt_common.h"
+#include "repack.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -1449,6 +1450,8 @@ struct axt_detector {
     unsigned *d_wb3[8] = {};    // conv blocks 2..6 packed for conv3x3_bf16x3 (allocated on the first switch to that arithmetic)
     std::vector<float> h_wfold[8];   // their BN-folded f32 weights [cout][cin][3][3], kept on the host for that packing
     float *d_wwino[8] = {};     // conv blocks 2..6 packed for conv3x3_wino (allocated on the first switch to that arithmetic)
+    float *d_wfold[8] = {};     // the folded weights on the device, from the block's first device load on (axt_detector_load_conv_block):
+                                // h_wfold of that block is stale then, and set_arith packs from here with repack.hip's kernels
     int fuse01 = 1;             // conv blocks 0 and 1 in one kernel (conv_s2_fused); axt_detector_set_fused_front, AXT_FUSE_S2=0 at create
     int arith = 0;              // stride-1 blocks: 0 direct f32 MFMA | 1 bf16x3 (blocks 2..8) | 2 f32 Winograd F(2x2,3x3) (set by create)
     float *d_bconv[8] = {};     // folded bias
@@ -1994,25 +1997,103 @@ int axt_detector_create(const float *const *h_tensors, int n_tensors, int max_ba
 int axt_detector_set_arith(axt_detector *d, int mode)
 {
     AXT_REQUIRE(d != nullptr && mode >= 0 && mode <= 2, "axt_detector_set_arith: mode must be 0 (direct f32), 1 (bf16x3) or 2 (f32 Winograd)");
+    // A block that was loaded on the device (d_wfold) packs from that copy with the kernels of repack.hip, on the null
+    // stream behind whatever stream the load ran on; the others from h_wfold on the host, as ever. Either way the images
+    // are complete when the call returns.
+    const int last = mode == 1 ? 6 : 7;
+    const bool missing = (mode == 1 && !d->d_wb3[2]) || (mode == 2 && !d->d_wwino[2]);
+    bool on_device = false;
+    for (int li = 2; missing && li <= last; ++li) on_device |= d->d_wfold[li] != nullptr;
+    if (on_device) AXT_CHECK_HIP(hipDeviceSynchronize());
     if (mode == 1 && !d->d_wb3[2]) {
         std::vector<uint16_t> pk;
         for (int li = 2; li <= 6; ++li) {
-            pack_bf16x3(kConv[li].cin, d->h_wfold[li], pk);
-            const int rc = dev_alloc(d, &d->d_wb3[li], pk.size() / 2);
+            const int rc = dev_alloc(d, &d->d_wb3[li], axt_repack_b3_bf16(kConv[li].cin) / 2);
             if (rc) return rc;
+            if (d->d_wfold[li]) {
+                if (int rp = axt_repack_b3(d->d_wfold[li], kConv[li].cin, d->d_wb3[li], nullptr)) return rp;
+                continue;
+            }
+            pack_bf16x3(kConv[li].cin, d->h_wfold[li], pk);
             AXT_CHECK_HIP(hipMemcpy(d->d_wb3[li], pk.data(), pk.size() * 2, hipMemcpyHostToDevice));
         }
     }
     if (mode == 2 && !d->d_wwino[2]) {
         std::vector<float> pk;
         for (int li = 2; li <= 7; ++li) {
-            pack_wino(kConv[li].cin, kConv[li].cout, d->h_wfold[li], pk);
-            const int rc = dev_alloc(d, &d->d_wwino[li], pk.size());
+            const int rc = dev_alloc(d, &d->d_wwino[li], axt_repack_wino_floats(kConv[li].cin, kConv[li].cout));
             if (rc) return rc;
+            if (d->d_wfold[li]) {
+                if (int rp = axt_repack_wino(d->d_wfold[li], kConv[li].cin, kConv[li].cout, d->d_wwino[li], nullptr)) return rp;
+                continue;
+            }
+            pack_wino(kConv[li].cin, kConv[li].cout, d->h_wfold[li], pk);
             AXT_CHECK_HIP(hipMemcpy(d->d_wwino[li], pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
         }
     }
+    if (on_device) AXT_CHECK_HIP(hipStreamSynchronize(nullptr));
     d->arith = mode;
+    return AXT_OK;
+}
+
+// ---- device-side weight loads (repack.hip) ------------------------------------------------------------
+static_assert(GeoW::UBUF == kRepackWinoChunk && GeoW::CCH == 8, "repack.hip's Winograd image is conv3x3_wino's");
+static_assert(GeoB3::WCHUNK_B == 2 * kRepackB3Chunk && GeoB3::CCH == 16 && GeoB3::KS == 5, "repack.hip's bf16x3 image is conv3x3_bf16x3's");
+
+}  // extern "C"
+
+int axt_detector_conv_spec(int li, int *cin, int *cout, int *stride)
+{
+    AXT_REQUIRE(li >= 0 && li < 8 && cin && cout && stride, "conv block %d not in 0..7", li);
+    *cin = kConv[li].cin;
+    *cout = kConv[li].cout;
+    *stride = kConv[li].stride;
+    return AXT_OK;
+}
+
+int axt_detector_linear_spec(int layer, int *fin, int *fout)
+{
+    AXT_REQUIRE(layer >= 0 && layer < 3 && fin && fout, "linear layer %d not in 0..2", layer);
+    *fin = layer == 0 ? kFeat : kFc;
+    *fout = layer == 2 ? kOut : kFc;
+    return AXT_OK;
+}
+
+extern "C" {
+
+int axt_detector_load_conv_block(axt_detector *d, int li, const float *d_weight, const float *d_bias, const float *d_gamma,
+                                 const float *d_beta, const float *d_mean, const float *d_var, void *stream)
+{
+    static const char fn[] = "axt_detector_load_conv_block";
+    AXT_REQUIRE(d && d_weight && d_bias && d_gamma && d_beta && d_mean && d_var, "%s: null argument", fn);
+    AXT_REQUIRE(li >= 0 && li < 8, "%s: conv block %d not in 0..7", fn, li);
+    hipStream_t st = (hipStream_t)stream;
+    const ConvSpec &cs = kConv[li];
+    const ConvPlan &pl = kPlan[li];
+    int rc;
+    if (!d->d_wfold[li] && (rc = dev_alloc(d, &d->d_wfold[li], (size_t)cs.cout * cs.cin * 9))) return rc;
+    std::vector<float>().swap(d->h_wfold[li]);          // stale from here on
+    if ((rc = axt_repack_fold(d_weight, d_bias, d_gamma, d_beta, d_mean, d_var, cs.cin, cs.cout, d->d_wfold[li], d->d_bconv[li],
+                              st)))
+        return rc;
+    rc = cs.stride == 2 ? axt_repack_direct_s2(d->d_wfold[li], cs.cin, cs.cout, d->d_wconv[li], st)
+                        : axt_repack_direct_s1(d->d_wfold[li], cs.cin, cs.cout, pl.cch, pl.nt, npadw(pl.nt), pl.ngroups,
+                                               d->d_wconv[li], st);
+    if (rc) return rc;
+    if (d->d_wwino[li] && (rc = axt_repack_wino(d->d_wfold[li], cs.cin, cs.cout, d->d_wwino[li], st))) return rc;
+    if (d->d_wb3[li] && (rc = axt_repack_b3(d->d_wfold[li], cs.cin, d->d_wb3[li], st))) return rc;
+    return AXT_OK;
+}
+
+int axt_detector_load_linear(axt_detector *d, int layer, const float *d_weight, const float *d_bias, void *stream)
+{
+    static const char fn[] = "axt_detector_load_linear";
+    AXT_REQUIRE(d && d_weight && d_bias, "%s: null argument", fn);
+    AXT_REQUIRE(layer >= 0 && layer < 3, "%s: linear layer %d not in 0..2", fn, layer);
+    hipStream_t st = (hipStream_t)stream;
+    const int fin = layer == 0 ? kFeat : kFc, fout = layer == 2 ? kOut : kFc, fpad = layer == 2 ? kOutPad : kFc;
+    if (int rc = axt_repack_linear(d_weight, fin, fout, fpad, d->d_wfc[layer], st)) return rc;
+    AXT_CHECK_HIP(hipMemcpyAsync(d->d_bfc[layer], d_bias, (size_t)fout * sizeof(float), hipMemcpyDeviceToDevice, st));
     return AXT_OK;
 }
 
@@ -2029,6 +2110,7 @@ void axt_detector_destroy(axt_detector *d)
     for (int i = 0; i < 8; ++i) {
         (void)hipFree(d->d_wb3[i]);
         (void)hipFree(d->d_wwino[i]);
+        (void)hipFree(d->d_wfold[i]);
         (void)hipFree(d->d_wconv[i]);
         (void)hipFree(d->d_bconv[i]);
         (void)hipFree(d->d_act[i]);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "axt_common.h"
+#include "repack.h"
 
 namespace {
 
@@ -629,6 +630,21 @@ int axt_head_trainer_input_grad(axt_head_trainer *t, const float *d_dy, int B, f
     const size_t n = (size_t)B * K0;
     hipLaunchKernelGGL(head_sum_slabs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t->ig_slab, S, n, d_dfeat);
     AXT_LAUNCH_CHECK();
+    return AXT_OK;
+}
+
+int axt_head_trainer_export(axt_head_trainer *t, axt_detector *det, void *stream)
+{
+    static const char fn[] = "axt_head_trainer_export";
+    AXT_REQUIRE(t && det, "%s: null argument", fn);
+    for (int l = 0; l < 3; ++l) {
+        int fin, fout;
+        if (int rc = axt_detector_linear_spec(l, &fin, &fout)) return rc;
+        AXT_REQUIRE(t->dims[l] == fin && t->dims[l + 1] == fout, "%s: the trainer's layer %d is %d -> %d, the detector's %d -> %d",
+                    fn, l, t->dims[l], t->dims[l + 1], fin, fout);
+    }
+    for (int l = 0; l < 3; ++l)
+        if (int rc = axt_detector_load_linear(det, l, t->w[l], t->b[l], stream)) return rc;
     return AXT_OK;
 }
 

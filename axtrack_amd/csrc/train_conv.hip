@@ -56,6 +56,7 @@
 
 #include "adam.h"
 #include "axt_common.h"
+#include "repack.h"
 
 namespace {
 
@@ -559,6 +560,7 @@ struct axt_conv_trainer {
     int64_t forwards = 0;                                   // forwards in batch mode: what num_batches_tracked grows by
     std::vector<float> var0;                                // running_var as created, until run_var takes over
     float *run_var = nullptr, *bstats = nullptr;            // [Co]; [3][Co]: the last batch's mean, biased variance, inv
+    float *var_dev = nullptr;                               // var0 on the device for axt_conv_trainer_export while run_var is not there
 };
 
 namespace {
@@ -885,6 +887,26 @@ int axt_maxpool2_backward(const float *d_in, const float *d_dout, int64_t n_maps
                        n_in, H, W, d_din);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
+}
+
+int axt_conv_trainer_export(axt_conv_trainer *t, axt_detector *det, int li, void *stream)
+{
+    static const char fn[] = "axt_conv_trainer_export";
+    AXT_REQUIRE(t && det, "%s: null argument", fn);
+    AXT_REQUIRE(li >= 0 && li < 8, "%s: conv block %d not in 0..7", fn, li);
+    int cin, cout, stride;
+    if (int rc = axt_detector_conv_spec(li, &cin, &cout, &stride)) return rc;
+    const Geom &g = t->g;
+    AXT_REQUIRE(g.Ci == cin && g.Co == cout && g.stride == stride, "%s: the trainer is %d -> %d channels at stride %d, conv "
+                "block %d is %d -> %d at stride %d", fn, g.Ci, g.Co, g.stride, li, cin, cout, stride);
+    if (!t->run_var && !t->var_dev) {
+        float *v = nullptr;
+        if (int rc = ct_alloc(t, &v, g.Co, false)) return rc;
+        AXT_CHECK_HIP(hipMemcpy(v, t->var0.data(), (size_t)g.Co * sizeof(float), hipMemcpyHostToDevice));
+        t->var_dev = v;
+    }
+    return axt_detector_load_conv_block(det, li, t->w, t->p3, t->p3 + g.Co, t->p3 + 2 * g.Co, t->mean,
+                                        t->run_var ? t->run_var : t->var_dev, stream);
 }
 
 }  // extern "C"

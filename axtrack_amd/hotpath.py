@@ -36,6 +36,10 @@ CONV_BLOCKS = (0, 1, 2, 4, 5, 7, 8, 10)
 # max-pools follows it (training.ConvStageTrainer takes keys and sizes from here)
 CONV_MAP_SIDE = (256, 128, 128, 64, 64, 32, 32, 16)
 CONV_POOLED = (False, False, True, False, True, False, True, False)
+# (input, output) channels per conv block 0..7, and (in, out) of the linear layers fcs.1 / 3 / 5: what the device loads
+# (Detector.load_conv_block, load_linear) check their tensors against
+CONV_CHANNELS = ((5, 20), (20, 40), (40, 80), (80, 80), (80, 80), (80, 80), (80, 80), (80, 160))
+LINEAR_SHAPES = ((FEATURES, 1024), (1024, 1024), (1024, CELLS * 3))
 
 
 def conv_block_key(i):
@@ -107,6 +111,73 @@ class Detector:
         h, self._h = getattr(self, '_h', None), None
         if h:
             self._lib.axt_detector_destroy(h)
+
+    def _check_device_tensors(self, what, tensors, shapes):
+        """Everything a device load asks of its tensors, before any launch: contiguous f32 CUDA tensors of these shapes on
+        the detector's device."""
+        for (name, t), shape in zip(tensors, shapes):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f'{what}: {name} must be a torch tensor on {self.device}, got {type(t).__name__}')
+            if t.device != self.device:
+                raise ValueError(f'{what}: {name} is on {t.device}, the detector on {self.device}')
+            if t.dtype != torch.float32:
+                raise ValueError(f'{what}: {name} must be float32, got {t.dtype}')
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f'{what}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
+            if not t.is_contiguous():
+                raise ValueError(f'{what}: {name} must be contiguous')
+
+    def load_conv_block(self, i, weight, bias, bn_weight, bn_bias, running_mean, running_var):
+        """Replace conv block i (0..7 of the package's numbering) by these tensors of the state-dict layout -- conv.weight
+        [Co, Ci, 3, 3] and conv.bias, batchnorm.weight, batchnorm.bias, running_mean, running_var [Co], contiguous f32 on
+        the detector's device -- without leaving the device (axt_detector_load_conv_block): BatchNorm is folded and every
+        packed image the block has is rewritten by kernels, on the current stream. The detector then computes, byte for
+        byte, what one created from the same tensors computes, in every arithmetic. state_dict_source becomes None."""
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < len(CONV_BLOCKS):
+            raise IndexError(f'conv block must be in 0..{len(CONV_BLOCKS) - 1}, got {i!r}')
+        ci, co = CONV_CHANNELS[i]
+        names = ('weight', 'bias', 'bn_weight', 'bn_bias', 'running_mean', 'running_var')
+        tensors = (weight, bias, bn_weight, bn_bias, running_mean, running_var)
+        self._check_device_tensors(f'load_conv_block({i})', zip(names, tensors), [(co, ci, 3, 3)] + [(co,)] * 5)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_detector_load_conv_block(self._h, int(i), *[t.data_ptr() for t in tensors], _stream()),
+                       'axt_detector_load_conv_block')
+        self.state_dict_source = None
+
+    def load_linear(self, layer, weight, bias):
+        """Replace linear layer 0..2 (fcs.1, fcs.3, fcs.5) by weight [out, in] and bias [out], contiguous f32 on the
+        detector's device, without leaving the device (axt_detector_load_linear): a tiled transpose into the GEMM's
+        layout on the current stream. state_dict_source becomes None."""
+        if isinstance(layer, bool) or not isinstance(layer, (int, np.integer)) or not 0 <= layer < 3:
+            raise IndexError(f'linear layer must be in 0..2, got {layer!r}')
+        fin, fout = LINEAR_SHAPES[layer]
+        self._check_device_tensors(f'load_linear({layer})', zip(('weight', 'bias'), (weight, bias)), [(fout, fin), (fout,)])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_detector_load_linear(self._h, int(layer), weight.data_ptr(), bias.data_ptr(), _stream()),
+                       'axt_detector_load_linear')
+        self.state_dict_source = None
+
+    def load_state_dict(self, sd):
+        """load_conv_block for the eight conv blocks and load_linear for the three linear layers from a state dict whose
+        tensors are already on the detector's device (contiguous f32): no host copy. Every tensor is checked before the
+        first launch."""
+        keys = state_dict_tensor_order()
+        for k in keys:
+            if k not in sd:
+                raise KeyError(f'state_dict lacks {k}')
+        conv = [[sd[k] for k in keys[6 * i:6 * i + 6]] for i in range(len(CONV_BLOCKS))]
+        fcs = [[sd[k] for k in keys[48 + 2 * l:50 + 2 * l]] for l in range(3)]
+        names = ('weight', 'bias', 'bn_weight', 'bn_bias', 'running_mean', 'running_var')
+        for i, t in enumerate(conv):
+            ci, co = CONV_CHANNELS[i]
+            self._check_device_tensors(f'load_state_dict: conv block {i}', zip(names, t), [(co, ci, 3, 3)] + [(co,)] * 5)
+        for l, t in enumerate(fcs):
+            fin, fout = LINEAR_SHAPES[l]
+            self._check_device_tensors(f'load_state_dict: linear {l}', zip(names, t), [(fout, fin), (fout,)])
+        for i, t in enumerate(conv):
+            self.load_conv_block(i, *t)
+        for l, t in enumerate(fcs):
+            self.load_linear(l, *t)
 
     @property
     def device_bytes(self):

@@ -16,7 +16,10 @@ fine_tune_head's docstring says what each option (train_conv_blocks, train_last_
 
 fine_tune_detector goes on to every depth: ConvTrunkTrainer chains any run of the last conv blocks with their pools,
 ConvBlockTrainer(stride=2) is a block of the stride-2 front, and the input is the block-2 table (depths 4, 5) or the raw
-stacks gathered per batch (depths 6..8). Both functions share one step loop (_fine_tune)."""
+stacks gathered per batch (depths 6..8). Both functions share one step loop (_fine_tune).
+
+Every trainer can put its weights of the moment into a live Detector without leaving the device (export_to;
+csrc/repack.hip), which is what test_loss=True does after every epoch to take the loss on a test set."""
 import ctypes
 import functools
 import os
@@ -106,6 +109,15 @@ def _first_rows(B, device):
     """Rows 0..B-1 as an i32 tensor on `device`: the index with which a trainer reads the whole output of the one in front
     of it. One tensor per batch size (at most max_batch of them) for every trainer and the step loop."""
     return torch.arange(B, dtype=torch.int32, device=device)
+
+
+def _check_export(trainer, detector):
+    """What every export_to asks before any launch: a live Detector on the trainer's device."""
+    from .hotpath import Detector
+    if not isinstance(detector, Detector) or not getattr(detector, '_h', None):
+        raise TypeError(f'export_to takes a live hotpath.Detector, got {type(detector).__name__}')
+    if detector.device != trainer.device:
+        raise ValueError(f'the trainer is on {trainer.device}, the detector on {detector.device}')
 
 
 class _HandleTrainer:
@@ -248,6 +260,15 @@ class HeadTrainer(_HandleTrainer):
                                                                ctypes.byref(step)), 'axt_head_trainer_read_moments')
         return (*out, int(step.value))
 
+    def export_to(self, detector):
+        """The three linear layers as they stand into a live Detector on the same device, without a host copy
+        (axt_head_trainer_export: Detector.load_linear from the trainer's own device tensors, on the current stream). The
+        detector then computes what Detector(self.state_dict()) computes in these layers, byte for byte."""
+        _check_export(self, detector)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.axt_head_trainer_export(self._h, detector._h, _stream()), 'axt_head_trainer_export')
+        detector.state_dict_source = None
+
     def state_dict(self):
         """The state dict this trainer was built from with the six fcs.* tensors replaced by the trained ones (numpy f32)."""
         sd = dict(self._sd)
@@ -380,6 +401,29 @@ class ConvBlockTrainer(_HandleTrainer):
                            'axt_conv_trainer_read_stats')
         return dict(running_mean=rm, running_var=rv, num_batches_tracked=int(n.value), batch_mean=bm if n.value else None,
                     batch_var=bv if n.value else None)
+
+    def export_to(self, detector, block=None):
+        """The block as it stands into conv block `block` (0..7 of the package's numbering; default: the one block_key
+        names) of a live Detector on the same device, without a host copy (axt_conv_trainer_export:
+        Detector.load_conv_block from the trainer's own device tensors, on the current stream): the four trained tensors
+        and the running statistics, the moved ones with batch_stats. The detector then computes what
+        Detector(self.state_dict()) computes in this block, byte for byte, in every arithmetic. A trainer whose channels or
+        stride are not that block's is refused."""
+        from .hotpath import CONV_BLOCKS, conv_block_key
+        _check_export(self, detector)
+        if block is None:
+            known = [conv_block_key(i) for i in range(len(CONV_BLOCKS))]
+            if self.block_key not in known:
+                raise ValueError(f'{self.block_key} is no conv block of the detector: say which block (0..7) to export to')
+            block = known.index(self.block_key)
+        if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or not 0 <= block < len(CONV_BLOCKS):
+            raise IndexError(f'conv block must be in 0..{len(CONV_BLOCKS) - 1}, got {block!r}')
+        with torch.cuda.device(self.device):
+            rc = self._lib.axt_conv_trainer_export(self._h, detector._h, int(block), _stream())
+        if rc == -22:
+            raise ValueError(self._lib.axt_last_error().decode())
+        _lib.check(rc, 'axt_conv_trainer_export')
+        detector.state_dict_source = None
 
     def state_dict(self, base=None):
         """The state dict this trainer was built from (or `base`) with the block's four trained tensors replaced (numpy
@@ -521,6 +565,13 @@ class ConvStageTrainer:
             b5.step(table, batch, grads['f5'], lr=lr, eps=eps)
         return grads
 
+    def export_to(self, detector):
+        """ConvBlockTrainer.export_to for the trained blocks, each into the conv block its key names; a forward-only block did
+        not change and is left alone."""
+        for blk, trained in zip(self.blocks, self.trained):
+            if trained:
+                blk.export_to(detector)
+
     def state_dict(self, base=None):
         """The state dict this stage was built from (or `base`) with the trained blocks' four tensors each replaced
         (numpy f32), and with batch_stats their running statistics and batch counts (ConvBlockTrainer.state_dict);
@@ -624,6 +675,13 @@ class ConvTrunkTrainer:
                 grads[f"{'p' if self.pooled[k - 1] else 'f'}{self.numbers[k - 1]}"] = g = dx
         return grads
 
+    def export_to(self, detector):
+        """ConvBlockTrainer.export_to for the trained blocks, each into the conv block its key names; a forward-only block did
+        not change and is left alone."""
+        for blk, trained in zip(self.blocks, self.trained):
+            if trained:
+                blk.export_to(detector)
+
     def state_dict(self, base=None):
         """The state dict this trunk was built from (or `base`) with the trained blocks' four tensors each replaced (numpy
         f32), and with batch_stats their running statistics and batch counts (ConvBlockTrainer.state_dict); everything
@@ -670,8 +728,9 @@ def _augmented_epoch(frames, labels, transform, draw, min_pos_rate, max_redraws,
     return tf, warped, tiles, lab
 
 
-def _epoch_metrics(sd, timelapse, labels, parameters, subset):
-    """one_epoch's every-tenth-epoch evaluation (core_functionality.py:150-161) of the detector with state dict `sd` on the
+def _epoch_metrics(sd, timelapse, labels, parameters, subset, detector=None):
+    """one_epoch's every-tenth-epoch evaluation (core_functionality.py:150-161) of the detector with state dict `sd` (or of
+    `detector`, a live one that holds these weights already: the test-loss detector of _fine_tune) on the
     detection frames `subset` of a labelled timelapse: detect, sum compute_TP_FP_FN('all', t) over the frames (one launch:
     detection_confusion), precision / recall / F1 at the 13 thresholds as compute_prc_rcl_F1's Series."""
     from . import params as _params
@@ -679,7 +738,8 @@ def _epoch_metrics(sd, timelapse, labels, parameters, subset):
     from .hotpath import Detector
     P = _params.load_parameters()
     P.update(parameters or {})
-    detector = Detector(sd, max_batch=32, device=timelapse.device)
+    if detector is None:
+        detector = Detector(sd, max_batch=32, device=timelapse.device)
     dets = AxonDetections(detector, timelapse, P, None, timepoint_subset=subset)
     if labels is not None:
         dets.set_groundtruth([labels[t] for t in subset])
@@ -689,7 +749,8 @@ def _epoch_metrics(sd, timelapse, labels, parameters, subset):
 
 def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
                    use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
-                   metrics_every=10, train_conv_blocks=None, bn_batch_stats=False, bn_momentum=0.1, train_last_conv=False):
+                   metrics_every=10, train_conv_blocks=None, bn_batch_stats=False, bn_momentum=0.1, test_loss=False,
+                   train_last_conv=False):
     """Train fcs.1/3/5 of `model` (a Detector, or a state dict) on the labelled timelapse for `epochs` epochs of
     one_epoch / run_epoch (core_functionality.py:109-165) -> (state_dict, history). labels: per detection frame (x, y) or
     (x, y, ids), as AxonDetections.set_groundtruth takes them. history: DataFrame, one column per epoch, rows the
@@ -734,7 +795,20 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
     weight decay alone), and every forward moves running_mean, running_var and num_batches_tracked; the returned state
     dict and the checkpoints carry them, and the every-tenth-epoch evaluation reads them. A forward-only block
     (train_conv_blocks=2's conv block 5) and the frozen trunk keep their running statistics. With the head alone
-    (train_conv_blocks=0) it is a ValueError: nothing would use it. Default False: running statistics, never updated."""
+    (train_conv_blocks=0) it is a ValueError: nothing would use it. Default False: running statistics, never updated.
+
+    test_loss: also the loss on the test set after every epoch, as the reference's optimize() runs one_epoch on its test
+    data with model.eval() (experiment.py). Needs a labelled test_timelapse (ValueError otherwise). One evaluation Detector
+    is created before the first epoch; after every training epoch the trainers export their weights of that moment into it
+    on the device (export_to: no host copy, no repacking on the host), it runs its ordinary inference forward -- eval mode
+    by construction: the running statistics, the ones bn_batch_stats has moved included -- over all frames and kept tiles
+    of the test set, and HeadTrainer.loss is taken on batches of BATCH_SIZE in order, unshuffled, DROP_LAST honoured,
+    against yolo_targets of the test labels (made once). The result is history.attrs['test_loss']: a DataFrame with
+    history's five rows and one column per epoch, each the mean over the test batches. The test set is never augmented
+    (the reference passes USE_TRANSFORMS to its test set too). It reads weights only: history, the
+    returned state dict and the checkpoints are what they are without it. The every-tenth-epoch evaluation then uses the
+    same detector for the test set instead of building one. A test batch may not be larger than the trainer's own
+    (min(BATCH_SIZE, training items)): ValueError."""
     if train_conv_blocks is None:
         depth = 1 if train_last_conv else 0
     else:
@@ -744,7 +818,8 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
         if train_last_conv and depth != 1:
             raise ValueError(f'train_last_conv=True means train_conv_blocks=1, not {depth}')
     return _fine_tune('fine_tune_head', timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms,
-                      transforms, min_pos_rate, max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum)
+                      transforms, min_pos_rate, max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum,
+                      test_loss)
 
 
 # fine_tune_detector's depth (how many of the last conv blocks train) -> (the conv block whose output the cached table
@@ -754,7 +829,7 @@ DEPTH_INPUT = {0: (7, None), 1: (6, 7), 2: (4, 5), 3: (4, 5), 4: (2, 3), 5: (2, 
 
 def fine_tune_detector(timelapse, labels=None, model=None, parameters=None, epochs=1, dest_dir=None, seed=None,
                        use_transforms=None, transforms=None, min_pos_rate=0.65, max_redraws=50, test_timelapse=None,
-                       metrics_every=10, train_conv_blocks=0, bn_batch_stats=False, bn_momentum=0.1):
+                       metrics_every=10, train_conv_blocks=0, bn_batch_stats=False, bn_momentum=0.1, test_loss=False):
     """fine_tune_head for every depth: train the head and the last train_conv_blocks (0..8, default 0) conv blocks of
     `model` -> (state_dict, history). Every other argument, the history, the checkpoints, the augmentation and the
     evaluation are fine_tune_head's. Depths 0..3 run exactly what fine_tune_head runs. Beyond (DEPTH_INPUT, ConvTrunkTrainer):
@@ -771,12 +846,12 @@ def fine_tune_detector(timelapse, labels=None, model=None, parameters=None, epoc
     per trained block the gradient of the pool behind it, its input gradient, its step, and last the head's step: every
     gradient is taken from weights that have not moved. bn_batch_stats works in the trained blocks at every depth; a
     forward-only block keeps its running statistics. At depths 6..8 an augmented epoch recomputes no table: the stacks are
-    gathered from the warped frames."""
+    gathered from the warped frames. test_loss: fine_tune_head's, at every depth."""
     if isinstance(train_conv_blocks, bool) or train_conv_blocks not in DEPTH_INPUT:
         raise ValueError(f'train_conv_blocks must be in 0..{max(DEPTH_INPUT)}, got {train_conv_blocks!r}')
     return _fine_tune('fine_tune_detector', timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms,
                       transforms, min_pos_rate, max_redraws, test_timelapse, metrics_every, int(train_conv_blocks),
-                      bn_batch_stats, bn_momentum)
+                      bn_batch_stats, bn_momentum, test_loss)
 
 
 class _TableInput:
@@ -818,7 +893,7 @@ class _StackInput:
 
 
 def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms, transforms, min_pos_rate,
-               max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum):
+               max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum, test_loss=False):
     """fine_tune_head and fine_tune_detector behind their own checks of the depth: the rest of the checks, the set-up and
     the one step loop. The trunk (none, one block, the last stage, or a longer chain) and the input it reads (a cached
     table, or stacks gathered per batch) are chosen by the depth; the loop is the same for all."""
@@ -843,6 +918,8 @@ def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, see
     with_metrics = test_timelapse is not None and bool(metrics_every)
     if with_metrics and not getattr(test_timelapse, 'labelled', False):
         raise ValueError('test_timelapse carries no labels (prepare_training_data makes labelled timelapses)')
+    if test_loss and (test_timelapse is None or not getattr(test_timelapse, 'labelled', False)):
+        raise ValueError('test_loss=True needs a labelled test_timelapse (prepare_training_data makes labelled timelapses)')
     if len(labels) != len(timelapse):
         raise ValueError(f'{len(labels)} label frames for {len(timelapse)} detection frames')
     augmented = bool(use_transforms) or transforms is not None
@@ -903,6 +980,34 @@ def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, see
         """The state dict of this moment: the head's tensors, and the conv blocks' where they are trained."""
         return trunk.state_dict(trainer.state_dict()) if trunk else trainer.state_dict()
 
+    eval_detector = None
+    if test_loss:
+        # one detector for every epoch's look at the test set: the trainers export into it on the device
+        test_timelapse.make_resident()
+        test_tiles = test_timelapse.tile_yx
+        test_targets = yolo_targets(test_timelapse.labels, test_tiles, device=timelapse.device).reshape(-1, S, S, 4)
+        test_batches = epoch_batches(test_targets.shape[0], bs, False, P['DROP_LAST'], None)
+        if not test_batches:
+            raise ValueError(f'DROP_LAST leaves no batch of {bs} among the {test_targets.shape[0]} test items')
+        if len(test_batches[0]) > trainer.max_batch:
+            raise ValueError(f'a test batch of {len(test_batches[0])} items is larger than the training batches '
+                             f'({trainer.max_batch}): the train set holds less than one batch')
+        eval_detector = Detector(sd, max_batch=32, device=timelapse.device)
+        test_history = {}
+
+    def test_epoch():
+        """The loss components of the weights of this moment on the test set: export, inference forward, loss per batch."""
+        trainer.export_to(eval_detector)
+        if trunk:
+            trunk.export_to(eval_detector)
+        eval_detector.set_arith('f32')                  # (the evaluation below may have switched it: CNN_ARITH)
+        yolo = eval_detector.detect_frames(test_timelapse.frames, test_tiles).reshape(-1, S, S, 3)
+        rows = []
+        for batch in test_batches:                      # in order: a batch is a run of rows
+            comp, _ = trainer.loss(yolo[int(batch[0]):int(batch[-1]) + 1], test_targets, batch)
+            rows.append([comp[k] for k in COMPONENTS])
+        return np.mean(np.array(rows, np.float64).reshape(-1, 5), axis=0)
+
     rng = np.random.default_rng(seed)
     checkpoints = (parameters or {}).get('MODEL_CHECKPOINTS') or [epochs - 1]
     history, metrics = {}, {}
@@ -936,16 +1041,20 @@ def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, see
         if dest_dir is not None and epoch in checkpoints:
             os.makedirs(dest_dir, exist_ok=True)
             save_checkpoint(current(), f'{dest_dir}/E{epoch:04}.pth')
+        if test_loss:
+            test_history[epoch] = test_epoch()
         if with_metrics and epoch % int(metrics_every) == 0:
             now = current()
             tstart = int(m_rng.integers(0, 10)) % len(timelapse)
             metrics[(epoch, 'train')] = _epoch_metrics(now, timelapse, labels if explicit_labels else None, parameters,
                                                        list(range(tstart, len(timelapse), 10)))
             metrics[(epoch, 'test')] = _epoch_metrics(now, test_timelapse, None, parameters,
-                                                      list(range(len(test_timelapse))))
+                                                      list(range(len(test_timelapse))), detector=eval_detector)
     history = pd.DataFrame(history, index=list(COMPONENTS))
     if with_metrics:
         history.attrs['metrics'] = pd.DataFrame(metrics)
     if augmented:
         history.attrs['transforms'] = used
+    if test_loss:
+        history.attrs['test_loss'] = pd.DataFrame(test_history, index=list(COMPONENTS))
     return current(), history

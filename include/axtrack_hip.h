@@ -669,6 +669,10 @@ int axt_conv_trainer_step(axt_conv_trainer *tr, const float *d_in, const int32_t
  * interface. */
 #include "axtrack_hip_trunk.h"
 
+/* Weights into a live detector on the device: one conv block or one linear layer from device tensors, and the trainers'
+ * exports of what they hold. Declared in a header of their own, part of this interface. */
+#include "axtrack_hip_repack.h"
+
 /* Training augmentation of a whole timelapse in one launch (data_utils.transform_X: translate, then flip, then rotate;
  * DESIGN.md 6.8e). d_in f32 [T, H, W]; d_out the same shape, not overlapping d_in (AXT_EINVAL: the warp is a gather).
  * Output pixel (y, x) of every frame reads the source that the inverses give in reverse order:
