@@ -33,7 +33,7 @@ def _require_gpu():
 # deployed_model/params.txt:34, model.py:85-103)
 CONV_BLOCKS = (0, 1, 2, 4, 5, 7, 8, 10)
 # per conv block 0..7 of the package's numbering: the side of the square map its convolution writes, and whether one of the
-# max-pools follows it (training.ConvStageTrainer takes keys and sizes from here)
+# max-pools follows it (training.ConvTrunkTrainer takes keys, sizes and pools from here)
 CONV_MAP_SIDE = (256, 128, 128, 64, 64, 32, 32, 16)
 CONV_POOLED = (False, False, True, False, True, False, True, False)
 # (input, output) channels per conv block 0..7, and (in, out) of the linear layers fcs.1 / 3 / 5: what the device loads
@@ -253,7 +253,7 @@ class Detector:
         first n_frames * n_tiles rows are returned) instead of a new one. block=6: the trunk one conv block earlier,
         [n_frames * n_tiles, 20480] = [item, 80, 16, 16], what training.ConvBlockTrainer reads
         (axt_cnn_block_features_frames); block=4: three conv blocks earlier, [n_frames * n_tiles, 81920] = [item, 80, 32, 32],
-        what training.ConvStageTrainer reads; block=7 is the default table."""
+        what a training.ConvTrunkTrainer from conv block 5 on (ConvStageTrainer) reads; block=7 is the default table."""
         if block not in BLOCK_FEATURES:
             raise ValueError(f'block must be one of {sorted(BLOCK_FEATURES)}, got {block}')
         return self._block_table(frames, tile_yx, t0, n_frames, out, block, BLOCK_FEATURES[block])

@@ -10,13 +10,14 @@ translate / flip / rotate of frames and labels every epoch, the prepare_data res
 recomputed from the warped frames, which costs about one trunk pass per epoch.
 
 The last one to three conv blocks can be trained jointly with the head (csrc/train_conv.hip): ConvBlockTrainer is one
-block, ConvStageTrainer the last stage (conv blocks 5 and 6, the 2 x 2 max-pool, conv block 7), either with BatchNorm's
-running statistics or with train-mode BatchNorm. The cached table is then the trunk's output that many blocks earlier.
+block, ConvTrunkTrainer chains any run of the last conv blocks with their pools, either with BatchNorm's running
+statistics or with train-mode BatchNorm; ConvStageTrainer is its three-block case, the last stage (conv blocks 5 and 6,
+the 2 x 2 max-pool, conv block 7). The cached table is then the trunk's output that many blocks earlier.
 fine_tune_head's docstring says what each option (train_conv_blocks, train_last_conv, bn_batch_stats) does to a step.
 
-fine_tune_detector goes on to every depth: ConvTrunkTrainer chains any run of the last conv blocks with their pools,
-ConvBlockTrainer(stride=2) is a block of the stride-2 front, and the input is the block-2 table (depths 4, 5) or the raw
-stacks gathered per batch (depths 6..8). Both functions share one step loop (_fine_tune).
+fine_tune_detector goes on to every depth: ConvBlockTrainer(stride=2) is a block of the stride-2 front, and the input is
+the block-2 table (depths 4, 5) or the raw stacks gathered per batch (depths 6..8). Both functions share one step loop
+(_fine_tune), which builds one ConvTrunkTrainer at every depth of 1 or more.
 
 Every trainer can put its weights of the moment into a live Detector without leaving the device (export_to;
 csrc/repack.hip), which is what test_loss=True does after every epoch to take the loss on a test set."""
@@ -484,105 +485,6 @@ def maxpool2_backward(x, dout, H, W):
     return din
 
 
-STAGE_BLOCKS = (5, 6, 7)                            # the last conv stage: conv blocks 5 and 6, the max-pool, conv block 7
-
-
-class ConvStageTrainer:
-    """The last conv stage of the state dict -- conv block 5, conv block 6, the 2 x 2 max-pool, conv block 7 -- as three
-    ConvBlockTrainers chained on the device, of which the last `depth` (1..3) are trained; a block in front of them runs
-    forward only and never steps. forward / backward_and_step work on batches picked by index from a table
-    [n_items, Ci*H*W] of the stage's inputs (Detector.features_frames(block=4)); forward's output is what
-    HeadTrainer.forward reads. block_keys, map_size: the three blocks' state-dict prefixes and the (H, W) of the maps the
-    first two run on (the third runs on the pooled (H // 2, W // 2)); default: the deployed architecture's, from
-    hotpath's table of conv blocks. batch_stats, momentum: train-mode BatchNorm (ConvBlockTrainer's) in the trained blocks;
-    a forward-only block keeps its running statistics."""
-
-    def __init__(self, state_dict, depth=3, parameters=None, max_batch=64, device='cuda:0', block_keys=None, map_size=None,
-                 batch_stats=False, momentum=0.1):
-        from .hotpath import CONV_MAP_SIDE, CONV_POOLED, conv_block_key
-        if depth not in (1, 2, 3):
-            raise ValueError(f'depth must be 1, 2 or 3, got {depth!r}')
-        if block_keys is None:
-            assert [CONV_POOLED[i] for i in STAGE_BLOCKS] == [False, True, False]
-            block_keys = [conv_block_key(i) for i in STAGE_BLOCKS]
-            map_size = (CONV_MAP_SIDE[STAGE_BLOCKS[0]],) * 2
-        if len(block_keys) != 3 or map_size is None:
-            raise ValueError('a stage is three blocks (block_keys) on maps of map_size = (H, W)')
-        self.depth = int(depth)
-        self.H, self.W = (int(v) for v in map_size)
-        if self.H < 2 or self.W < 2:
-            raise ValueError(f'maps of {self.H} x {self.W} leave the max-pool nothing')
-        sizes = [(self.H, self.W), (self.H, self.W), (self.H // 2, self.W // 2)]
-        self.trained = [i >= 3 - self.depth for i in range(3)]
-        self.batch_stats = bool(batch_stats)
-        self.blocks = [ConvBlockTrainer(state_dict, k, parameters, map_size=s, max_batch=max_batch, device=device,
-                                        batch_stats=self.batch_stats and tr, momentum=momentum)
-                       for k, s, tr in zip(block_keys, sizes, self.trained)]
-        for a, b in zip(self.blocks, self.blocks[1:]):
-            if a.Co != b.Ci:
-                raise ValueError(f'{a.block_key} writes {a.Co} channels, {b.block_key} reads {b.Ci}')
-        self.device, self.max_batch = self.blocks[0].device, int(max_batch)
-        self.in_width, self.out_width = self.blocks[0].in_width, self.blocks[2].out_width
-        self._sd = state_dict
-        self._kept = None
-
-    @property
-    def device_bytes(self):
-        return sum(b.device_bytes for b in self.blocks)
-
-    def forward(self, table, batch=None):
-        """table f32 [n_items, Ci*H*W] on the GPU, batch: which rows (default: all) -> [B, Co*(H//2)*(W//2)], the head's
-        input rows. The outputs in between are kept for backward_and_step."""
-        b5, b6, b7 = self.blocks
-        f5 = b5.forward(table, batch)
-        rows = _first_rows(f5.shape[0], self.device)
-        f6 = b6.forward(f5, rows)
-        pooled = maxpool2_forward(f6, self.H, self.W).reshape(f5.shape[0], b7.in_width)
-        f7 = b7.forward(pooled, rows)
-        self._kept = (f5, f6, pooled, f7)
-        return f7
-
-    def backward_and_step(self, table, batch, dfeat, lr=None, eps=ADAM_EPS):
-        """From dfeat [B, out_width], the gradient with respect to forward's output of the same batch
-        (HeadTrainer.input_grad): back to front, per trained block its input gradient where a trained block lies in front
-        of it, the pool's gradient between conv blocks 7 and 6, then the block's Adam step -- so every gradient is taken
-        from weights that have not moved yet. Returns the gradients handed on: {'pooled', 'f6', 'f5'} where formed."""
-        if self._kept is None or self._kept[3].shape[0] != dfeat.shape[0]:
-            raise ValueError('backward_and_step needs forward() on this batch first')
-        b5, b6, b7 = self.blocks
-        f5, f6, pooled, _ = self._kept
-        rows = _first_rows(dfeat.shape[0], self.device)
-        grads = {}
-        if self.trained[1]:
-            grads['pooled'] = b7.input_grad(dfeat)
-        b7.step(pooled, rows, dfeat, lr=lr, eps=eps)
-        if self.trained[1]:
-            grads['f6'] = maxpool2_backward(f6, grads['pooled'], self.H, self.W)
-            if self.trained[0]:
-                grads['f5'] = b6.input_grad(grads['f6'])
-            b6.step(f5, rows, grads['f6'], lr=lr, eps=eps)
-        if self.trained[0]:
-            b5.step(table, batch, grads['f5'], lr=lr, eps=eps)
-        return grads
-
-    def export_to(self, detector):
-        """ConvBlockTrainer.export_to for the trained blocks, each into the conv block its key names; a forward-only block did
-        not change and is left alone."""
-        for blk, trained in zip(self.blocks, self.trained):
-            if trained:
-                blk.export_to(detector)
-
-    def state_dict(self, base=None):
-        """The state dict this stage was built from (or `base`) with the trained blocks' four tensors each replaced
-        (numpy f32), and with batch_stats their running statistics and batch counts (ConvBlockTrainer.state_dict);
-        everything else, a forward-only block's tensors included, passes through."""
-        sd = dict(self._sd if base is None else base)
-        for blk, trained in zip(self.blocks, self.trained):
-            if trained:
-                sd = blk.state_dict(sd)
-        return sd
-
-
 class ConvTrunkTrainer:
     """Conv blocks first_block..7 of the state dict as ConvBlockTrainers chained on the device, a 2 x 2 max-pool behind
     every block whose `pooled` flag is set; the last n_trained of them are trained, the blocks in front run forward only and
@@ -693,6 +595,34 @@ class ConvTrunkTrainer:
         return sd
 
 
+STAGE_BLOCKS = (5, 6, 7)                            # the last conv stage: conv blocks 5 and 6, the max-pool, conv block 7
+
+
+class ConvStageTrainer(ConvTrunkTrainer):
+    """The last conv stage of the state dict -- conv block 5, conv block 6, the 2 x 2 max-pool, conv block 7 -- as the
+    three-block case of ConvTrunkTrainer: stride 1 throughout, one pool behind the second block, the last `depth` (1..3)
+    blocks trained. The table [n_items, Ci*H*W] is Detector.features_frames(block=4); forward, backward_and_step (whose
+    gradients are 'p6', 'f6', 'f5'), export_to, state_dict and device_bytes are the trunk's, contract included.
+    block_keys, map_size: the three blocks' state-dict prefixes and the (H, W) of the maps the first two run on (the third
+    runs on the pooled (H // 2, W // 2)); default: the deployed architecture's, from hotpath's table of conv blocks."""
+
+    def __init__(self, state_dict, depth=3, parameters=None, max_batch=64, device='cuda:0', block_keys=None, map_size=None,
+                 batch_stats=False, momentum=0.1):
+        from .hotpath import CONV_MAP_SIDE
+        if depth not in (1, 2, 3):
+            raise ValueError(f'depth must be 1, 2 or 3, got {depth!r}')
+        if block_keys is None:
+            map_size = (CONV_MAP_SIDE[STAGE_BLOCKS[0]],) * 2
+        elif len(block_keys) != 3 or map_size is None:
+            raise ValueError('a stage is three blocks (block_keys) on maps of map_size = (H, W)')
+        self.depth = int(depth)
+        self.H, self.W = (int(v) for v in map_size)
+        if self.H < 2 or self.W < 2:
+            raise ValueError(f'maps of {self.H} x {self.W} leave the max-pool nothing')
+        super().__init__(state_dict, STAGE_BLOCKS[0], self.depth, parameters, max_batch, device, batch_stats, momentum,
+                         block_keys=block_keys, strides=(1, 1, 1), pooled=(False, True, False), in_size=map_size)
+
+
 def save_checkpoint(state_dict, filename):
     """The reference's checkpoint layout (utils.py:258-264) without optimiser state; setup_inference(weights=filename)
     and the reference's load_checkpoint read it."""
@@ -782,10 +712,10 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
 
     train_conv_blocks: how many of the last conv blocks to train with the head, 0..3 (None: 1 with train_last_conv, else
     0; train_last_conv=True with another number than 1 is a ValueError). 0 is the head alone, 1 is train_last_conv. 3
-    trains the whole last stage (ConvStageTrainer: conv blocks 5 and 6 on 32 x 32 maps, the max-pool, conv block 7) on the
-    cached table Detector.features_frames(block=4); a step is the three forwards with the pool, head forward, loss, the
-    head's input gradient, then back to front each block's input gradient, the pool's gradient and the block's step, and
-    the head's step. 2 reads the same table (conv block 5's output is not offered as one) and runs conv block 5 forward
+    trains the whole last stage (ConvTrunkTrainer from conv block 5 on, the chain that ConvStageTrainer is: conv blocks 5
+    and 6 on 32 x 32 maps, the max-pool, conv block 7) on the cached table Detector.features_frames(block=4); a step is
+    the three forwards with the pool, head forward, loss, the head's input gradient, then back to front each block's
+    input gradient, the pool's gradient and the block's step, and the head's step. 2 reads the same table (conv block 5's output is not offered as one) and runs conv block 5 forward
     only: its tensors come back as they went in. Every trained block takes the head's learning rate, Adam eps and weight
     decay and keeps its running statistics. Conv blocks 0-4 stay frozen.
 
@@ -823,7 +753,8 @@ def fine_tune_head(timelapse, labels=None, model=None, parameters=None, epochs=1
 
 
 # fine_tune_detector's depth (how many of the last conv blocks train) -> (the conv block whose output the cached table
-# holds, None: no table, the raw stacks are gathered per batch; the first conv block the trunk trainer runs, None: no trunk)
+# holds, None: no table, the raw stacks are gathered per batch; the first conv block the trunk trainer runs, read at every
+# depth of 1 or more, None: no trunk)
 DEPTH_INPUT = {0: (7, None), 1: (6, 7), 2: (4, 5), 3: (4, 5), 4: (2, 3), 5: (2, 3), 6: (None, 0), 7: (None, 0), 8: (None, 0)}
 
 
@@ -832,7 +763,8 @@ def fine_tune_detector(timelapse, labels=None, model=None, parameters=None, epoc
                        metrics_every=10, train_conv_blocks=0, bn_batch_stats=False, bn_momentum=0.1, test_loss=False):
     """fine_tune_head for every depth: train the head and the last train_conv_blocks (0..8, default 0) conv blocks of
     `model` -> (state_dict, history). Every other argument, the history, the checkpoints, the augmentation and the
-    evaluation are fine_tune_head's. Depths 0..3 run exactly what fine_tune_head runs. Beyond (DEPTH_INPUT, ConvTrunkTrainer):
+    evaluation are fine_tune_head's. Depths 0..3 run exactly what fine_tune_head runs; every depth of 1 or more is one
+    ConvTrunkTrainer from the first block DEPTH_INPUT names. Beyond 3:
 
       4  the cached table is conv block 2's output after its pool (Detector.trunk_features_frames(block=2), 1.3 MB per
          item); conv block 3 runs forward only and comes back as it went in, conv blocks 4..7 train
@@ -895,8 +827,8 @@ class _StackInput:
 def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, seed, use_transforms, transforms, min_pos_rate,
                max_redraws, test_timelapse, metrics_every, depth, bn_batch_stats, bn_momentum, test_loss=False):
     """fine_tune_head and fine_tune_detector behind their own checks of the depth: the rest of the checks, the set-up and
-    the one step loop. The trunk (none, one block, the last stage, or a longer chain) and the input it reads (a cached
-    table, or stacks gathered per batch) are chosen by the depth; the loop is the same for all."""
+    the one step loop. The trunk (none, or one chain of conv blocks) and the input it reads (a cached table, or stacks
+    gathered per batch) are chosen by the depth (DEPTH_INPUT); the loop is the same for all."""
     import pandas as pd
     from .hotpath import Detector
     if bn_batch_stats and depth == 0:
@@ -959,22 +891,9 @@ def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, see
         n_items = source.fill(timelapse.frames, tile_yx)
         targets = yolo_targets(labels, tile_yx, device=timelapse.device).reshape(-1, S, S, 4)
         trainer = HeadTrainer(sd, P, max_batch=min(bs, n_items), device=timelapse.device)
-    # the trained conv blocks in front of the head: a chain from first_block on, the stage, one block, or none. Their step
-    # calls take the same arguments.
-    if depth >= 4:
-        trunk = ConvTrunkTrainer(sd, first_block, depth, P, max_batch=trainer.max_batch, device=timelapse.device,
-                                 batch_stats=bn_batch_stats, momentum=bn_momentum)
-        trunk_step = trunk.backward_and_step
-    elif depth >= 2:
-        trunk = ConvStageTrainer(sd, depth, P, max_batch=trainer.max_batch, device=timelapse.device,
-                                 batch_stats=bn_batch_stats, momentum=bn_momentum)
-        trunk_step = trunk.backward_and_step
-    elif depth == 1:
-        trunk = ConvBlockTrainer(sd, LAST_CONV_BLOCK, P, max_batch=trainer.max_batch, device=timelapse.device,
-                                 batch_stats=bn_batch_stats, momentum=bn_momentum)
-        trunk_step = trunk.step
-    else:
-        trunk = None
+    # the conv blocks in front of the head: one chain from first_block on, its last `depth` blocks trained, or none
+    trunk = ConvTrunkTrainer(sd, first_block, depth, P, max_batch=trainer.max_batch, device=timelapse.device,
+                             batch_stats=bn_batch_stats, momentum=bn_momentum) if depth else None
 
     def current():
         """The state dict of this moment: the head's tensors, and the conv blocks' where they are trained."""
@@ -1034,7 +953,7 @@ def _fine_tune(name, timelapse, labels, model, parameters, epochs, dest_dir, see
             # then the trunk steps (back to front, each block's input gradient before its own step), then the head
             if trunk:
                 dfeat = trainer.input_grad(dy)
-                trunk_step(features, rows_in, dfeat, lr=lr)
+                trunk.backward_and_step(features, rows_in, dfeat, lr=lr)
             trainer.step(feats, head_rows, dy, lr=lr)
             rows.append([comp[k] for k in COMPONENTS])
         history[epoch] = np.mean(np.array(rows, np.float64).reshape(-1, 5), axis=0)

@@ -41,8 +41,7 @@ def main():
     frames = torch.from_numpy(synth.synth_frames(5, 512, 512, seed=3)).to(DEV)
     for depth in (0, 3, 8):
         head = training.HeadTrainer(sd, max_batch=2, device=DEV)
-        trunk = (None if depth == 0 else training.ConvStageTrainer(sd, 3, max_batch=2, device=DEV) if depth == 3
-                 else training.ConvTrunkTrainer(sd, 0, 8, max_batch=2, device=DEV))
+        trunk = training.ConvTrunkTrainer(sd, training.DEPTH_INPUT[depth][1], depth, max_batch=2, device=DEV) if depth else None
         live = Detector(sd, max_batch=32, device=DEV)
 
         def export():

@@ -51,7 +51,7 @@ def prime(mode):
     head, stage, st = MODES[mode]['head'], MODES[mode]['stage'], MODES[mode]['st']
     b5, b6, b7 = stage.blocks
     st['f7'] = stage.forward(x4, batches[0])
-    st['f5'], st['f6'], st['pooled'], _ = stage._kept
+    (_, _, st['f5']), (_, _, st['f6']), (st['pooled'], _, _) = stage._kept
     _, dy = head.loss(head.forward(st['f7'], ident), tgt, batches[0], read=False)
     st['dfeat'] = head.input_grad(dy)
     st['dpooled'] = b7.input_grad(st['dfeat'])

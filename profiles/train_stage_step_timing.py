@@ -47,7 +47,7 @@ st = {}
 def prime():
     idx = batches[0]
     st['f7'] = stage.forward(x4, idx)
-    st['f5'], st['f6'], st['pooled'], _ = stage._kept
+    (_, _, st['f5']), (_, _, st['f6']), (st['pooled'], _, _) = stage._kept
     y = head.forward(st['f7'], ident)
     _, st['dy'] = head.loss(y, tgt, idx, read=False)
     st['dfeat'] = head.input_grad(st['dy'])

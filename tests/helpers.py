@@ -198,3 +198,9 @@ def cnn_activation(detector, which, slot0, n):
     rc, out = cnn_activation_rc(detector, which, slot0, n)
     assert rc == 0, f'axt_debug_cnn_activation(buffer {which}, slots [{slot0},{slot0 + n})) returned {rc}'
     return out
+
+
+def stage_kept(st):
+    """(f5, f6, pooled, f7) of a ConvStageTrainer's last forward, from the chain's per-block (input, rows, output)."""
+    (_, _, f5), (_, _, f6), (pooled, _, f7) = st._kept
+    return f5, f6, pooled, f7

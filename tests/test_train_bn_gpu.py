@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 import train_bn_reference as br
 import train_conv_reference as cr
 import train_reference as tr
@@ -228,7 +229,7 @@ def _run_stage(st, ht, table, targets, batches, lrs, eps=EPS):
     outs, snaps = [], []
     for idx, lr in zip(batches, lrs):
         Fo = st.forward(d_table, idx)
-        f5, f6, pooled, _ = st._kept
+        f5, f6, pooled, _ = helpers.stage_kept(st)
         stats = [b.stats() for b in st.blocks]
         y = ht.forward(Fo)
         _, dy = ht.loss(y, d_tgt, idx)
@@ -236,7 +237,7 @@ def _run_stage(st, ht, table, targets, batches, lrs, eps=EPS):
         grads = st.backward_and_step(d_table, idx, dfeat, lr=lr, eps=eps)
         ht.step(Fo, None, dy, lr=lr, eps=eps)
         out = dict(F5=f5, F6=f6, pooled=pooled, F=Fo, dfeat=dfeat)
-        out.update({k: grads[g] for k, g in (('dpooled', 'pooled'), ('dF6', 'f6'), ('dx6', 'f5')) if g in grads})
+        out.update({k: grads[g] for k, g in (('dpooled', 'p6'), ('dF6', 'f6'), ('dx6', 'f5')) if g in grads})
         out = {k: v.cpu().numpy() for k, v in out.items()}
         for name, s, trained in zip(sr.BLOCKS, stats, st.trained):
             if trained:
@@ -277,8 +278,8 @@ def test_depth_two_leaves_block_five_and_its_statistics_alone():
     ev, _ = _stage_trainers(convs, head_w, shape, max_batch=3, depth=2, batch_stats=False)
     for s, idx in enumerate(batches):
         ev.forward(torch.from_numpy(table).to(DEV), idx)
-        assert ev._kept[0].cpu().numpy().tobytes() == outs[s]['F5'].tobytes()
-    assert ev._kept[1].cpu().numpy().tobytes() != outs[-1]['F6'].tobytes()
+        assert helpers.stage_kept(ev)[0].cpu().numpy().tobytes() == outs[s]['F5'].tobytes()
+    assert helpers.stage_kept(ev)[1].cpu().numpy().tobytes() != outs[-1]['F6'].tobytes()
     sd = st.state_dict(ht.state_dict())
     assert all(sd[f'b5.{k}'] is st._sd[f'b5.{k}'] for k in ALL) and 'b5.batchnorm.num_batches_tracked' not in sd
     assert int(sd['b6.batchnorm.num_batches_tracked']) == int(sd['b7.batchnorm.num_batches_tracked']) == 3

@@ -3,7 +3,8 @@ maxpool2_bwd_k; axtrack_amd/training.py: ConvStageTrainer, fine_tune_head(train_
 tests/train_stage_reference.py under train_stage_reference.judge_restarted: the outputs of the three blocks and the pool,
 the gradients handed back through the stage, and the updates and Adam moments of every trained tensor, each no further from
 the f64 reference than a small multiple of what plain f32 on the CPU is on the same input. The pool and its gradient are
-compared with torch's CPU max_pool2d bit for bit.
+compared with torch's CPU max_pool2d bit for bit. The stage is ConvTrunkTrainer's three-block case: the chain's loop against
+the same ConvBlockTrainer and pool calls written out by hand, byte for byte (test_the_stage_is_its_blocks_called_by_hand).
 
 The tile edges of conv_dgrad_k, each with a case on either side (test_input_grad_tile_edges):
   input channels     64 per workgroup (the kernel's output rows)                      Ci = 64 | 65
@@ -21,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import helpers
 import train_conv_reference as cr
 import train_reference as tr
 import train_stage_reference as sr
@@ -76,14 +78,14 @@ def _run_gpu(st, ht, table, targets, batches, lrs, eps=EPS):
     outs, snaps = [], []
     for idx, lr in zip(batches, lrs):
         Fo = st.forward(d_table, idx)
-        f5, f6, pooled, _ = st._kept
+        f5, f6, pooled, _ = helpers.stage_kept(st)
         y = ht.forward(Fo)
         _, dy = ht.loss(y, d_tgt, idx)
         dfeat = ht.input_grad(dy)
         grads = st.backward_and_step(d_table, idx, dfeat, lr=lr, eps=eps)
         ht.step(Fo, None, dy, lr=lr, eps=eps)
         out = dict(F5=f5, F6=f6, pooled=pooled, F=Fo, dfeat=dfeat)
-        out.update({k: grads[g] for k, g in (('dpooled', 'pooled'), ('dF6', 'f6'), ('dx6', 'f5')) if g in grads})
+        out.update({k: grads[g] for k, g in (('dpooled', 'p6'), ('dF6', 'f6'), ('dx6', 'f5')) if g in grads})
         out = {k: v.cpu().numpy() for k, v in out.items()}
         want_p, want_g = _cpu_pool(out['F6'], out.get('dpooled'), len(idx), st.blocks[1].Co, st.H, st.W)
         assert out['pooled'].tobytes() == want_p.tobytes(), 'the pooled maps are not torch\'s'
@@ -154,8 +156,72 @@ def test_depth_two_leaves_the_first_block_alone(stage_cases):
     assert np.abs(sd['b6.conv.weight'] - convs[1][0]).max() > LR / 2
 
 
+# ------------------------------------------------------------------------------------------------ the chain is its blocks
+def _block_state(blk):
+    """Everything a ConvBlockTrainer holds, as bytes: the tensors, the Adam moments with their step counts, BatchNorm's
+    statistics with the batch count."""
+    mom = [blk.moments(i) for i in range(4)]
+    st = blk.stats()
+    arrays = blk.weights() + [a for m in mom for a in m[:2]] + [np.array([m[2] for m in mom] + [st['num_batches_tracked']])]
+    arrays += [st[k] for k in ('running_mean', 'running_var', 'batch_mean', 'batch_var') if st[k] is not None]
+    return [a.tobytes() for a in arrays]
+
+
+@pytest.mark.parametrize('batch_stats', [False, True])
+@pytest.mark.parametrize('depth', [1, 2, 3])
+def test_the_stage_is_its_blocks_called_by_hand(stage_cases, depth, batch_stats):
+    """ConvStageTrainer.forward / backward_and_step against three ConvBlockTrainers of the same state dict driven by the
+    sequence the chain stands for, written out with no loop: after each of three steps (rows repeated and out of order, a
+    learning rate per step, a seeded random dfeat) the output, every gradient handed on, and every block's tensors, moments,
+    step counts and statistics are the same bytes. A forward-only block runs with its running statistics in both."""
+    convs, head_w, shape, table, _ = stage_cases['unequal']
+    (_, H, W), B = shape, 3
+    P = dict(LR=LR, WEIGHT_DECAY=WD)
+    sd = _state_dict(convs, head_w)
+    st = training.ConvStageTrainer(sd, depth, P, max_batch=B, device=DEV, block_keys=KEYS, map_size=(H, W),
+                                   batch_stats=batch_stats)
+    b5, b6, b7 = (training.ConvBlockTrainer(sd, key, P, map_size=size, max_batch=B, device=DEV,
+                                            batch_stats=batch_stats and i >= 3 - depth)
+                  for i, (key, size) in enumerate(zip(KEYS, [(H, W), (H, W), (H // 2, W // 2)])))
+    assert [b.batch_stats for b in st.blocks] == [b.batch_stats for b in (b5, b6, b7)]
+    d_table = torch.from_numpy(table).to(DEV)
+    rows = torch.arange(B, dtype=torch.int32, device=DEV)
+    rng = np.random.default_rng(depth)
+    same = lambda a, b: a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    for step, idx in enumerate(_batches(B, len(table))):
+        lr = LR * 0.9 ** step
+        dfeat = torch.from_numpy(rng.normal(0, 1, (B, st.out_width)).astype(np.float32)).to(DEV)
+        out = st.forward(d_table, idx)
+        grads = st.backward_and_step(d_table, idx, dfeat, lr=lr, eps=EPS)
+        # the same by hand
+        f5 = b5.forward(d_table, idx)
+        f6 = b6.forward(f5, rows)
+        pooled = training.maxpool2_forward(f6, H, W).reshape(B, b7.in_width)
+        f7 = b7.forward(pooled, rows)
+        want = {}
+        if depth >= 2:
+            want['p6'] = b7.input_grad(dfeat)
+        b7.step(pooled, rows, dfeat, lr=lr, eps=EPS)
+        if depth >= 2:
+            want['f6'] = training.maxpool2_backward(f6, want['p6'], H, W)
+            if depth >= 3:
+                want['f5'] = b6.input_grad(want['f6'])
+            b6.step(f5, rows, want['f6'], lr=lr, eps=EPS)
+        if depth >= 3:
+            b5.step(d_table, idx, want['f5'], lr=lr, eps=EPS)
+        assert same(out, f7) and out.abs().max().item() > 0, f'step {step}: the output'
+        assert list(grads) == list(want) == ['p6', 'f6', 'f5'][:(0, 2, 3)[depth - 1]]
+        for k in want:
+            assert grads[k].numel() == want[k].numel() and same(grads[k], want[k]), f'step {step}: gradient {k}'
+        for name, mine, theirs in zip(KEYS, st.blocks, (b5, b6, b7)):
+            assert _block_state(mine) == _block_state(theirs), f'step {step}: {name}'
+    steps = [b.moments(0)[2] for b in st.blocks]
+    assert steps == [3 if i >= 3 - depth else 0 for i in range(3)]
+    assert [b.stats()['num_batches_tracked'] for b in st.blocks] == (steps if batch_stats else [0, 0, 0])
+
+
 # ------------------------------------------------------------------------------------------------ the data gradient alone
-EDGES = [(64, 7, 4, 4, 4),       # Ci = 64: one whole tile of input channels; 9 Co = 63; r = 64
+EDGES =[(64, 7, 4, 4, 4),       # Ci = 64: one whole tile of input channels; 9 Co = 63; r = 64
          (65, 8, 5, 13, 1),      # Ci = 65; 9 Co = 72; r = 65: one past each
          (3, 16, 3, 5, 2),       # 9 Co = 144: nine whole depth tiles
          (5, 3, 7, 9, 64)]       # r = 4032: 63 whole tiles, the largest batch
@@ -281,7 +347,6 @@ def deployed(weights):
 
 def test_block_four_features(deployed):
     """block=4 is the detector's buffer 4 byte for byte; blocks 6 and 7 return what they return without it in between."""
-    import helpers
     det, frames = deployed
     x6, x7 = (det.features_frames(frames, [(0, 0)], block=b).cpu().numpy() for b in (6, 7))
     x4 = det.features_frames(frames, [(0, 0)], block=4)
@@ -308,7 +373,7 @@ def test_stage_forward_at_the_initial_weights_is_the_detectors(deployed, weights
     st = training.ConvStageTrainer(weights, 3, max_batch=2, device=DEV)
     assert [(b.Ci, b.Co, b.H, b.W) for b in st.blocks] == [(80, 80, 32, 32), (80, 80, 32, 32), (80, 160, 16, 16)]
     st.forward(x4)
-    f5, f6, pooled, f7 = (a.cpu().numpy() for a in st._kept)
+    f5, f6, pooled, f7 = (a.cpu().numpy() for a in helpers.stage_kept(st))
     h4, f5, pooled, f7 = x4.cpu().numpy().reshape(2, 80, 32, 32), f5.reshape(2, 80, 32, 32), pooled.reshape(2, 80, 16, 16), \
         f7.reshape(2, 160, 16, 16)
     for layer, got, inp in ((5, f5, h4), (6, pooled, f5), (7, f7, pooled)):

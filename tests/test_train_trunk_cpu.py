@@ -121,6 +121,49 @@ def test_chain_step_is_autograd_and_adam(first, n_trained, batch_stats):
                 assert snaps[0][k]['cw'][i].tobytes() == convs[k][i].astype(np.float64).tobytes() and snaps[0][k]['t'] == 0
 
 
+@pytest.mark.parametrize('depth', [1, 2, 3])
+def test_chain_step_is_the_stage_references_step(depth):
+    """The two references agree on the stage: chain_step on strides (1, 1, 1), pooled (F, T, F), fed the dfeat that
+    train_stage_reference.stage_step forms, reproduces that step on CASES['unequal'] in f64.
+    Bit for bit, where both compute a quantity the same way (test_stride_one_is_the_references_below: the forward and a
+    block's parameter gradients; the pool is one function for both): F5, F6, pooled, F, and the last block's four updated
+    tensors, whose gradients come from the same dfeat.
+    Within tolerance, where the data gradient is an einsum over shifted maps in one and a gather per tap in the other:
+    dpooled, dF6 (the pool's routing of dpooled), dx6 at test_block_gradients_are_autograds' 1e-10 for dx, and the updates
+    of the blocks in front, which take those gradients, at test_chain_step_is_autograd_and_adam's 1e-7."""
+    import train_stage_reference as sr
+    dims, heads = sr.CASES['unequal']
+    convs, head, shape, table, targets = sr.synth_stage(dims, heads, seed=100, n=40)
+    idx = torch.tensor([7, 31, 7])
+    X = torch.from_numpy(table).double().reshape(len(table), *shape)[idx]
+    T = torch.from_numpy(targets).double().reshape(-1, tr.S, tr.S, 4)[idx]
+    lr, wd, eps = 1e-2, 0.05, 1e-3
+    stage = sr.new_state(convs, head, torch.float64)
+    want = sr.stage_step(stage, X, T, (49.5, 1.0, 49.5), lr, wd, depth, eps=eps)
+    chain = tk.new_state(convs, torch.float64)
+    spec = [(1, pooled, k >= 3 - depth) for k, pooled in enumerate((False, True, False))]
+    got = tk.chain_step(chain, spec, X, want['dfeat'], lr, wd, eps=eps)
+    same = lambda a, b: a.shape == b.shape and a.numpy().tobytes() == b.numpy().tobytes()
+    for mine, theirs in (('F0', 'F5'), ('F1', 'F6'), ('P1', 'pooled'), ('F2', 'F')):
+        assert same(got[mine], want[theirs]) and want[theirs].abs().max() > 0, theirs
+    handed_on = [('dP1', 'dpooled'), ('dF1', 'dF6'), ('dF0', 'dx6')][:(0, 2, 3)[depth - 1]]
+    assert {k for k in got if k.startswith('d')} == {m for m, _ in handed_on}
+    assert {k for k in want if k in ('dpooled', 'dF6', 'dx6')} == {t for _, t in handed_on}
+    for mine, theirs in handed_on:
+        assert want[theirs].abs().max() > 0
+        _close(got[mine], want[theirs], theirs, 1e-10)
+    for k, (name, conv) in enumerate(zip(sr.BLOCKS, convs)):
+        for i, tensor in enumerate(cr.CONV_TENSORS):
+            a, b, start = chain[k]['cw'][i], stage[name]['cw'][i], torch.from_numpy(conv[i]).double()
+            if k < 3 - depth:
+                assert same(a, start) and same(b, start) and chain[k]['t'] == 0, f'{name} {tensor} runs forward only'
+            elif k == 2:
+                assert same(a, b) and not same(a, start), f'{name} {tensor}'
+            else:
+                assert not same(b, start)
+                _close(a - start, b - start, f'{name} {tensor}', 1e-7)
+
+
 # ------------------------------------------------------------------------------------------------ the judge and the faults
 FAULT_CASES = {'window0': ((5, 20, 8, 9, 3), 2), 'size_up': ((20, 40, 6, 6, 1), 2), 'no_parity': ((5, 20, 7, 10, 2), 2),
                'parity_shift': ((5, 20, 7, 10, 2), 2), 'hw_swapped': ((5, 20, 7, 10, 2), 2)}
