@@ -9,7 +9,8 @@ trains the detector's three linear layers on labelled frames with the convolutio
 reference's translate / flip / rotate augmentation redrawn every epoch if asked (augment.py); fine_tune_detector trains
 any number of the conv blocks with it, down to the whole network; prepare_training_data
 makes the labelled train and test timelapses of a recording from its files (core_functionality.setup_data), with the
-standardisation scaler measured on the GPU (estimate_stnd_scaler) and the labels read by load_labels_csv.
+standardisation scaler measured on the GPU (estimate_stnd_scaler) and the labels read by load_labels_csv; read_tiff reads a
+TIFF timelapse without a third-party reader, its strips decoded on the GPU (tiff.py), and every file-name argument takes .tif.
 The compute lives in csrc/libaxtrack_hip.so (C ABI: include/axtrack_hip.h); there is no CPU
 fallback -- importing works anywhere, running needs the GPU and the built library.
 """
@@ -20,6 +21,7 @@ from .detections import AxonDetections
 from .hotpath import Detector
 from .render import render_inference
 from .timelapse import Timelapse, estimate_stnd_scaler, load_labels_csv
+from .tiff import read_tiff, tiff_info, TiffError, TiffUnsupported
 from .training import (ConvBlockTrainer, ConvStageTrainer, ConvTrunkTrainer, HeadTrainer, fine_tune_head, fine_tune_detector,
                        yolo_targets)
 from .augment import (Transform, transform_from_uniforms, draw_transform, augment_frames, transform_labels,
@@ -32,5 +34,6 @@ __all__ = ['setup_inference', 'prepare_input_data', 'inference', 'visualize_infe
            'ConvBlockTrainer', 'ConvStageTrainer', 'ConvTrunkTrainer', 'HeadTrainer', 'fine_tune_head', 'fine_tune_detector',
            'yolo_targets',
            'prepare_training_data', 'estimate_stnd_scaler', 'load_labels_csv',
+           'read_tiff', 'tiff_info', 'TiffError', 'TiffUnsupported',
            'Transform', 'transform_from_uniforms', 'draw_transform', 'augment_frames', 'transform_labels', 'pos_label_rate',
            'segment_microchannels', 'flood_initial_mask', 'segment_mask', 'save_final_mask', 'otsu_threshold_from_hist']

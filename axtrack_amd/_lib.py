@@ -129,6 +129,8 @@ SIGNATURES = {
     'axt_detector_load_linear': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'axt_conv_trainer_export': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'axt_head_trainer_export': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'axt_tiff_decode_u16': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                    c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),
     'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),

@@ -10,7 +10,7 @@
 //   x = log2(1 + x)              skimage.exposure.adjust_log(x, gain=1) (:255-258)
 //   x = x / scale                :312 (the mean is not subtracted)
 //
-// skimage and tifffile are absent from the reference tree and from this image: img_as_float32 and adjust_log are
+// skimage is absent from the reference tree and from this image (TIFF files are read by tiff.py / tiff.hip, not tifffile): img_as_float32 and adjust_log are
 // restated from their published behaviour -- PARITY UNPINNED for those two steps.
 // Algorithmic traffic: 2 B in (+ 1 B of mask, cache-resident) and 4 B out per pixel; 8 pixels per lane
 // (16-byte load, two 16-byte stores).

@@ -986,3 +986,58 @@ class McfShard:
         h, self._h = getattr(self, '_h', None), None
         if h:
             self._lib.axt_mcf_shard_free(h)
+
+
+# ------------------------------------------------------------------ TIFF strips (csrc/tiff.hip, include/axtrack_hip_tiff.h)
+TIFF_STATUS_TEXT = {1: 'the input ends before the rows are complete', 2: 'an invalid LZW code',
+                    3: 'the data decodes to more than the rows of the strip', 4: 'the segment descriptor is out of range'}
+
+
+def tiff_decode_launch(d_src, segs, W, compression, predictor, big_endian, out, status):
+    """axt_tiff_decode_u16 on the current stream, nothing waited for. d_src: uint8 device tensor; segs: TIFF_SEGMENT_DTYPE
+    records (host; uploaded here from pinned memory) or a device uint8 tensor that already holds them; out: contiguous
+    2-byte device tensor, the records' dst_offset counted in its elements; status: int32 device tensor [n_segs]. Returns
+    the device copy of the records, which the caller keeps until the stream has passed the launch."""
+    from .tiff import TIFF_SEGMENT_DTYPE
+    assert d_src.dtype == torch.uint8 and d_src.is_contiguous() and out.is_contiguous() and out.element_size() == 2
+    if isinstance(segs, torch.Tensor):
+        d_segs, n = segs, segs.numel() // TIFF_SEGMENT_DTYPE.itemsize
+    else:
+        segs = np.ascontiguousarray(segs, TIFF_SEGMENT_DTYPE)
+        n = len(segs)
+        pinned = torch.empty(max(segs.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+        pinned.numpy()[:segs.nbytes] = segs.view(np.uint8)
+        d_segs = pinned.to(out.device, non_blocking=True)
+        d_segs._axt_pinned = pinned                                       # (alive as long as the device copy)
+    assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() >= n and status.device == out.device
+    assert d_src.device == out.device
+    lib = _lib.load()
+    with torch.cuda.device(out.device):
+        _lib.check(lib.axt_tiff_decode_u16(d_src.data_ptr(), d_src.numel(), d_segs.data_ptr(), n, int(W), int(compression),
+                                           int(predictor), int(bool(big_endian)), out.data_ptr(), out.numel(),
+                                           status.data_ptr(), _stream()), 'axt_tiff_decode_u16')
+    return d_segs
+
+
+def tiff_raise_on_status(status, frame=None, row0=None, what='the TIFF data'):
+    """Read the statuses (one copy to the host, which waits for the stream) and raise TiffError for the first failing
+    segment, naming its frame and row where the caller knows them."""
+    from .tiff import TiffError
+    st = status.cpu().numpy()
+    bad = np.flatnonzero(st)
+    if len(bad):
+        k = int(bad[0])
+        where = f'segment {k}' if frame is None else f'the strip of frame {int(frame[k])}, row {int(row0[k])} (segment {k})'
+        raise TiffError(f'{what}: {where} does not decode: {TIFF_STATUS_TEXT.get(int(st[k]), "status " + str(int(st[k])))} '
+                        f'(status {int(st[k])}; {len(bad)} of {len(st)} segments fail)')
+
+
+def tiff_decode_u16(d_src, segs, W, compression, predictor, big_endian, out, frame=None, row0=None):
+    """Decode strips that are already on the device into `out` and check them: tiff_decode_launch, then the statuses read
+    once. Raises tiff.TiffError naming the first failing segment's frame and row. Returns out."""
+    n = len(segs)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)
+    keep = tiff_decode_launch(d_src, segs, W, compression, predictor, big_endian, out, status)
+    tiff_raise_on_status(status[:n], frame, row0)
+    del keep
+    return out

@@ -7,8 +7,8 @@
 
 Same names, argument meaning and return values as the reference, so examples/test.py runs
 against this package by changing its import. Differences are confined to where the reference
-depends on assets or packages that are not redistributable (weights file, tifffile):
-`setup_inference` takes the weights explicitly, `prepare_input_data` also accepts arrays.
+depends on assets that are not redistributable (the weights file): `setup_inference` takes the weights explicitly.
+`prepare_input_data` also accepts arrays, and reads .tif files with the package's own reader (tiff.py), not tifffile.
 """
 import glob
 import os
@@ -21,6 +21,7 @@ import torch
 from . import params as _params
 from .detections import AxonDetections
 from .hotpath import Detector
+from . import tiff as _tiff
 from .timelapse import (Timelapse, preprocess, pad_mask, estimate_stnd_scaler, frame_scales, load_labels_csv,
                         contiguous_runs)
 
@@ -93,11 +94,8 @@ def prepare_input_data(imseq_fname, parameters, dest_dir, inference_data_dir, st
         if path.endswith('.npy'):
             imseq = np.load(path)
         else:
-            try:
-                from tifffile import imread
-            except ImportError as e:
-                raise ImportError('reading .tif needs tifffile; pass a numpy array or a .npy file instead') from e
-            imseq = imread(path)
+            # the native reader (tiff.py): the stack stays on the device, int16-viewed raw counts, as preprocess takes it
+            imseq = _tiff.read_stack(path, device=parameters['DEVICE'], to_host=False)
     else:
         imseq = np.asarray(imseq_fname)
     mask = None
@@ -120,29 +118,31 @@ def prepare_input_data(imseq_fname, parameters, dest_dir, inference_data_dir, st
     if use_cached_datasets == 'to':
         timelapse.to_cache(dest_dir)
     if check_preproc:
+        if isinstance(imseq, torch.Tensor):                              # (the statistics are sampled on the host)
+            imseq = imseq.cpu().numpy().view(np.uint16)
         fname = save_preproc_metrics(dest_dir, name, imseq, mask_raw, input_metadata, parameters, stnd_scaler)     # (before padding, as the 'Original' step of the reference is taken after it: zero margins only add zeros)
         warnings.warn(f'check_preproc: the preprocessing statistics are in {fname}; the comparison plot against the training '
                       f'data (ml_plotting.plot_preprocessed_input_data, train_preproc_data.csv) is out of scope of axtrack_amd')
     return timelapse
 
 
-def _read_stack(source, what):
-    """A .npy file, a .tif file where tifffile exists, or the array itself."""
+def _read_stack(source, what, device='cuda:0'):
+    """A .npy file, a .tif / .tiff file through the native reader (tiff.py; tifffile only for what that refuses, where
+    it is importable), or the array itself. `what` names the file's role in an error."""
     if not isinstance(source, str):
         return np.asarray(source)
     if source.endswith('.npy'):
         return np.load(source)
     try:
-        from tifffile import imread
-    except ImportError as e:
-        raise ImportError(f'reading {what} {source} needs tifffile; pass a numpy array or a .npy file instead') from e
-    return imread(source)
+        return _tiff.read_stack(source, device=device)
+    except _tiff.TiffUnsupported as e:
+        raise _tiff.TiffUnsupported(f'{what} {source}: {e}') from e
 
 
 def prepare_training_data(parameters, skip_test=False, **overrides):
     """core_functionality.setup_data (:15-59): the labelled train and test timelapses of one recording -> (train, test), test
     None with skip_test. Keys read from `parameters` (each can be overridden by keyword): TIMELAPSE_FILE (.npy, a uint16
-    array [T,H,W], or .tif where tifffile exists), LABELS_FILE (the reference's axon_anchor_labels.csv), MASK_FILE (.npy, an
+    array [T,H,W], or .tif through the native reader), LABELS_FILE (the reference's axon_anchor_labels.csv), MASK_FILE (.npy, .tif of 0 / non-0 samples, an
     array, None or a name ending in 'None'), TRAIN_TIMEPOINTS, TEST_TIMEPOINTS (input frame numbers), OFFSET, CLIP_LOWERLIM,
     PAD (top, right, bottom, left), LOG_CORRECT, STANDARDIZE, STANDARDIZE_FRAMEWISE, TEMPORAL_CONTEXT, TILESIZE, CACHE, DEVICE.
 
@@ -156,12 +156,14 @@ def prepare_training_data(parameters, skip_test=False, **overrides):
     P = dict(parameters)
     P.update(overrides)
     device, context = P.get('DEVICE', 'cuda:0'), int(P.get('TEMPORAL_CONTEXT', 2))
-    imseq = _read_stack(P['TIMELAPSE_FILE'], 'the timelapse')
+    imseq = _read_stack(P['TIMELAPSE_FILE'], 'the timelapse', device)
     if imseq.ndim != 3:
         raise ValueError(f'the timelapse must be [T,H,W], got {imseq.shape}')
     T = imseq.shape[0]
     mask = P.get('MASK_FILE')
-    mask = None if mask is None or (isinstance(mask, str) and mask.endswith('None')) else _read_stack(mask, 'the mask')
+    mask = None if mask is None or (isinstance(mask, str) and mask.endswith('None')) else _read_stack(mask, 'the mask', device)
+    if mask is not None and np.ndim(mask) == 3 and len(mask) == 1 and T != 1:
+        mask = mask[0]                                                    # (a mask file of one page is the static mask)
     pad = P.get('PAD')
     pad = [int(v) for v in pad] if pad is not None and any(pad) else None
     H = imseq.shape[1] + (pad[0] + pad[2] if pad else 0)

@@ -114,7 +114,11 @@ def flood_initial_mask(initial_mask, floodpoint, connectivity=2):
 
 
 def segment_mask(transm_chnl, floodpoint, gaussion_sigma=1, bin_closing_dim=4, connectivity=2):
-    """segment_microchannels and flood_initial_mask in one call: the final mask, bool [H, W]."""
+    """segment_microchannels and flood_initial_mask in one call: the final mask, bool [H, W]. transm_chnl may also be the
+    name of a .npy or .tif / .tiff file (the latter through the package's own reader, tiff.py; page 0 is segmented)."""
+    if isinstance(transm_chnl, str):
+        from . import tiff
+        transm_chnl = tiff.read_stack(transm_chnl) if tiff.is_tiff_name(transm_chnl) else np.load(transm_chnl)
     a, _, _ = _check_image(transm_chnl, gaussion_sigma, bin_closing_dim)
     _check_seed(a.shape, floodpoint, connectivity)
     return flood_initial_mask(segment_microchannels(a, gaussion_sigma, bin_closing_dim), floodpoint, connectivity)

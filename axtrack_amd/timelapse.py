@@ -147,17 +147,44 @@ class Timelapse:
         cls.__init__(self, frames, name=name, mask=mask, device=device, **kw)
         self.frames = frames                                            # (the constructor keeps the same storage)
         self._host_raw = a if a.is_pinned() else a.pin_memory()
+        self._source = _HostFrames(self._host_raw)
+        self._set_streaming(mask, offset, clip, log_correct, scale, chunk_frames, dev)
+        return self
+
+    def _set_streaming(self, mask, offset, clip, log_correct, scale, chunk_frames, dev):
         off = 0.0 if not offset else (offset / 2 ** 16 if isinstance(offset, int) else float(offset))
         lo = 0.0 if not clip else (clip / 2 ** 16 if isinstance(clip, int) else float(clip))
         m = None if mask is None else torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
         self._pre = (m, off, lo, bool(log_correct), float(scale))
         self._chunk = max(int(chunk_frames), 2 * self.temporal_context + 1)
         self._pending = True
+
+    @classmethod
+    def from_tiff(cls, path, name='timelapse', mask=None, offset=121, clip=55, log_correct=True, scale=0.015176106,
+                  chunk_frames=96, device='cuda:0', **kw):
+        """The streaming twin of from_host_u16 for a TIFF file (tiff.py): nothing is read yet but the tags. In
+        stream_chunks each 64-frame piece is "H2D of that piece's strip bytes, still compressed, then the decode launch into
+        the raw buffer" on the copy stream, followed by the piece's event; everything downstream of the raw buffer is the
+        same. The strips' statuses are read once after the last chunk: a strip that does not decode raises TiffError
+        there. A file this reader refuses raises TiffUnsupported here."""
+        from .tiff import tiff_info
+        if mask is not None and np.asarray(mask).ndim != 2:
+            raise ValueError('from_tiff takes a static [H,W] mask; a mask per frame goes through prepare_input_data')
+        info = tiff_info(path)
+        self = cls.__new__(cls)
+        dev = torch.device(device)
+        frames = torch.empty(info.shape, dtype=torch.float32, device=dev)
+        cls.__init__(self, frames, name=name, mask=mask, device=device, **kw)
+        self.frames = frames
+        self._host_raw = None
+        self._source = _TiffStrips(info, dev)
+        self._set_streaming(mask, offset, clip, log_correct, scale, chunk_frames, dev)
         return self
 
     def stream_chunks(self):
-        """Generator over the chunks of a host-resident timelapse. All H2D copies are enqueued at once on a copy stream, in
-        pieces of 16 frames into a device buffer for the raw timelapse (2 bytes per pixel; no staging buffer to recycle), each
+        """Generator over the chunks of a host-resident timelapse (from_host_u16) or of one still in its TIFF file (from_tiff:
+        where this says "copy", read "copy of the strips' bytes and their decode launch"). All H2D copies are enqueued at once on a copy stream, in
+        pieces of 16 frames (64 from a TIFF file) into a device buffer for the raw timelapse (2 bytes per pixel; no staging buffer to recycle), each
         followed by an event. The compute (current) stream then takes the frames in chunks that GROW -- 16, 32, 48, 64, 80 frames,
         then `chunk_frames` -- so that the first kernels start after ~0.17 ms of copying while later chunks are large enough
         for full launches (PCIe delivers a 512x512 frame in 10.6 us, the detector needs ~14 us for it: the copies stay ahead
@@ -167,7 +194,8 @@ class Timelapse:
         from . import hotpath as hp
         dev = self.frames.device
         T, H, W = self.frames.shape
-        piece = 16
+        source = self._source                            # where the raw pieces come from: host frames, or a TIFF file's strips
+        piece = source.piece
         ramp = tuple(int(v) for v in os.environ.get('AXT_STREAM_RAMP', '16,32,48,64,80').split(','))      # tuning knob (bench experiments)
         copy_stream = _copy_stream(dev)
         compute = torch.cuda.current_stream(dev)
@@ -179,7 +207,7 @@ class Timelapse:
             with torch.cuda.stream(copy_stream):
                 while len(landed) * piece < min(upto, T):
                     a0 = len(landed) * piece
-                    d_raw[a0:a0 + piece].copy_(self._host_raw[a0:a0 + piece], non_blocking=True)
+                    source.enqueue(d_raw, a0, min(a0 + piece, T))
                     landed.append(copy_stream.record_event())
         m, off, lo, logc, scale = self._pre
         a, k = 0, 0
@@ -187,7 +215,7 @@ class Timelapse:
         while a < T:
             n = sizes(k)
             b = min(a + n, T)
-            if T - b < piece:
+            if T - b < 16:                               # (no tail chunk of a few frames)
                 b = T
             # the copies of this chunk and of the next one are in the copy queue before this chunk's kernels are enqueued (all
             # of them up front would keep the host busy for ~0.5 ms before the first kernel launch)
@@ -209,8 +237,9 @@ class Timelapse:
             yield a, b, occ
             a, k = b, k + 1
         d_raw.record_stream(copy_stream)
+        source.finish()                                  # (a TIFF source reads its statuses here, once; raises on a bad strip)
         self._pending = False
-        self._host_raw = None
+        self._host_raw = self._source = None
 
     def make_resident(self):
         """A host-resident timelapse (from_host_u16) holds an UNINITIALISED frame buffer until its chunks have been streamed:
@@ -258,6 +287,57 @@ class Timelapse:
         return self.frames.device
 
 
+class _HostFrames:
+    """Piece source of stream_chunks: raw frames in pinned host memory, 16 frames a piece. enqueue() runs on the copy stream."""
+    piece = 16
+
+    def __init__(self, host_raw):
+        self.host_raw = host_raw
+
+    def enqueue(self, d_raw, a0, a1):
+        d_raw[a0:a1].copy_(self.host_raw[a0:a1], non_blocking=True)
+
+    def finish(self):
+        pass
+
+
+class _TiffStrips:
+    """Piece source of stream_chunks: the strips of a TIFF file (tiff.SegmentPacker). A piece is the H2D copy of its strips'
+    packed bytes and the decode launch into the raw buffer, both on the copy stream; a little-endian uncompressed file
+    without predictor is the copy alone. The pinned buffers live until finish(), which reads every status once.
+    64 frames a piece: one wave decodes one strip, and a launch over the few hundred strips of 16 frames leaves most of
+    the device idle for as long as one strip takes (the decode against the number of segments)."""
+    piece = 64
+
+    def __init__(self, info, dev):
+        from .tiff import SegmentPacker
+        self.info, self.packer, self.keep = info, SegmentPacker(info), []
+        self.status = torch.zeros(max(info.n_segments, 1), dtype=torch.int32, device=dev)
+
+    def enqueue(self, d_raw, a0, a1):
+        from . import hotpath as hp
+        info, packer = self.info, self.packer
+        view, host, segs, total = packer.pack(a0, a1)
+        chunk = d_raw[a0:a1]
+        self.keep.append(host)
+        if packer.plain and total == chunk.numel() * 2 and np.array_equal(segs['src_offset'], segs['dst_offset'] * 2):
+            chunk.view(torch.uint8).view(-1).copy_(host[:total], non_blocking=True)
+            return
+        d_src = host.to(d_raw.device, non_blocking=True)
+        s0, s1 = packer.segments(a0, a1)
+        d_segs = hp.tiff_decode_launch(d_src, segs, info.shape[2], packer.device_compression, info.predictor,
+                                       info.byteorder == '>', chunk, self.status[s0:s1])
+        self.keep += [d_src, d_segs]
+
+    def finish(self):
+        from . import hotpath as hp
+        info = self.info
+        try:
+            hp.tiff_raise_on_status(self.status[:info.n_segments], info.frame, info.row0, info.path)
+        finally:
+            self.keep = []
+
+
 _PINNED = {}
 _COPY_STREAMS = {}
 
@@ -280,20 +360,28 @@ def _pinned_bytes(n):
 def _raw_on_device(imseq, mask, offset, clip, device):
     """What preprocess and estimate_stnd_scaler hand to the kernels: (raw counts on the device as int16 bits [T,H,W], the
     static mask as a u8 tensor or None, offset and clip in [0,1] units). A mask per frame zeroes the raw counts."""
-    a = np.asarray(imseq)
-    if a.dtype != np.uint16:
-        raise TypeError(f'raw timelapses are uint16 (got {a.dtype}); pass preprocessed float32 frames to Timelapse directly')
-    if a.ndim != 3:
-        raise ValueError(f'raw timelapses are [T,H,W], got {a.shape}')
-    raw = torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(device)
+    if isinstance(imseq, torch.Tensor):          # read_tiff's output: already raw counts, on a device or not; no host round trip
+        a = imseq.view(torch.int16) if imseq.dtype == torch.uint16 else imseq
+        if a.dtype != torch.int16:
+            raise TypeError(f'raw timelapses are uint16 (got {imseq.dtype}); pass preprocessed float32 frames to Timelapse directly')
+        if a.dim() != 3:
+            raise ValueError(f'raw timelapses are [T,H,W], got {tuple(a.shape)}')
+        raw = a.to(device)
+    else:
+        a = np.asarray(imseq)
+        if a.dtype != np.uint16:
+            raise TypeError(f'raw timelapses are uint16 (got {a.dtype}); pass preprocessed float32 frames to Timelapse directly')
+        if a.ndim != 3:
+            raise ValueError(f'raw timelapses are [T,H,W], got {a.shape}')
+        raw = torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(device)
     off = 0.0 if not offset else (offset / 2 ** 16 if isinstance(offset, int) else float(offset))
     lo = 0.0 if not clip else (clip / 2 ** 16 if isinstance(clip, int) else float(clip))
     m = None
     if mask is not None:
         mk = np.asarray(mask).astype(bool)
         if mk.ndim == 3:                      # a mask per frame: zero the raw counts, which is what masking the floats does
-            if mk.shape != a.shape:
-                raise ValueError(f'a time-varying mask must match the timelapse {a.shape}, got {mk.shape}')
+            if mk.shape != tuple(a.shape):
+                raise ValueError(f'a time-varying mask must match the timelapse {tuple(a.shape)}, got {mk.shape}')
             raw = raw * torch.from_numpy(mk).to(device=device, dtype=torch.int16)
         else:
             m = torch.from_numpy(np.ascontiguousarray(mk.astype(np.uint8)))

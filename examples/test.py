@@ -2,7 +2,8 @@
 
 The reference's example assets (example_timelapse.tif, its mask, the trained weights) are external downloads
 that are not redistributable; this script therefore feeds a synthetic raw uint16 timelapse and seeded weights.
-With the real assets, pass weights='deployed_model/' and the .tif / .npy file names instead."""
+With the real assets, pass weights='deployed_model/' and the .tif / .npy file names instead.
+A .tif name works without tifffile: the package reads TIFF itself (axtrack_amd.read_tiff)."""
 import os
 import sys
 import tempfile
