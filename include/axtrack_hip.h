@@ -532,7 +532,8 @@ int axt_detection_confusion(const float *d_conf, const int32_t *d_x, const int32
  * metrics of axtrack_amd/mot_metrics.py for n_assoc associations of the same detections at once.
  * d_track i32 [n_assoc, n_frames, cap] (-1 = no identity; identities in [0, nh)); d_x, d_y, d_count the shared
  * detections; labels d_gid (dense identities in [0, no)), d_gx, d_gy i32 [n_frames, gcap], d_gcount i32 [n_frames].
- * Identities are unique within a frame on both sides; identities out of range take no part. A pair is admissible
+ * Identities are unique within a frame on both sides; identities out of range take no part. The counts are clamped:
+ * a frame uses max(min(d_count[f], cap), 0) detection slots and max(min(d_gcount[f], gcap), 0) label slots. A pair is admissible
  * when dx^2 + dy^2 <= max_dist^2. Limits: cap, gcap <= 1024, max_dist <= 255, no, nh <= 2^24 (AXT_EINVAL beyond).
  * Outputs: d_counts i64 [n_assoc, 10] = n_match, n_switch, n_miss, n_fp, sum of matched d2, n_obj, n_pred,
  * n_unique_objects, n_fragmentations, idtp; d_tallies i32 [n_assoc, no, 2] = frames present, frames not missed.

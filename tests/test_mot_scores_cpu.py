@@ -116,6 +116,105 @@ def test_identity_derivation_max_weight_matching_equals_the_padded_problem():
             assert idtp / n_obj == pytest.approx(want.idr, abs=1e-12)
 
 
+# ------------------------------------------------------------------ the integer solver and the limit cases
+@pytest.mark.parametrize('name', list(mr.limit_cases()))
+def test_limit_cases_have_the_route_facts_they_claim(name):
+    case = mr.limit_cases()[name]
+    assert case.facts, name
+    missing = [f for f in case.facts if f not in mr.facts_of(case)]
+    assert not missing, (name, missing)
+
+
+def test_the_restated_sizes_are_those_the_design_tabulates():
+    """The restated lsap_bytes / clear_lds_bytes at the sizes DESIGN.md 6.8g tabulates; the library's own scratch answer
+    pins lsap_bytes on both sides of the identity boundary."""
+    assert mr.clear_lds_bytes(1024, 1024) == 94208
+    assert [mr.clear_lds_bytes(n, n) for n in (712, 713)] == [65504, 65688]
+    assert mr.clear_lds_bytes(712, 712) <= mr.DEFAULT_DYNAMIC_LDS < mr.clear_lds_bytes(713, 713)
+    assert (mr.clear_lds_bytes(400, 1024), mr.clear_lds_bytes(1024, 400)) == (68624, 62384)
+    assert (mr.lsap_bytes(896, 2048), mr.lsap_bytes(897, 2048)) == (65536, 65560) and mr.IDENTITY_LDS_LIMIT == 65536
+    lib = _lib.load()
+    for no, nh in ((896, 2048), (897, 2048), (1, 1), (7, 21)):
+        assert mr.lsap_bytes(no, nh) == mr.identity_state_bytes(no, nh)
+        assert _query(lib, K=3, no=no, nh=nh) == (0, 3 * mr.scratch_bytes(no, nh)), (no, nh)
+
+
+def test_both_solvers_choose_the_same_pairs_on_every_frame_of_every_old_scene():
+    scenes = list(mr.named_cases().values()) + mr.hand_cases() + mr.association_scenes()
+    n_frames = 0
+    for s in scenes:
+        for k in range(s['tracks'].shape[0]):
+            a, b = mr.reference(s, k, solver='f64'), mr.reference(s, k, solver='int')
+            assert a['events'] == b['events'] and a['counts'].tolist() == b['counts'].tolist()
+            assert a['step2'].keys() == b['step2'].keys()
+            for f in a['step2']:
+                assert sorted(a['step2'][f]['pairs']) == sorted(b['step2'][f]['pairs']) and a['step2'][f]['cost'] == b['step2'][f]['cost']
+                assert (b['step2'][f]['solver'], a['step2'][f]['solver']) in (('int', 'f64'), ('none', 'none'))
+            n_frames += len(a['step2'])
+    assert n_frames > 100
+    # the broken models still run (on SciPy: the sum-first model has no dummy formulation) and still differ
+    for rule in mr.RULES:
+        assert mr.reference(mr.named_cases()['cardinality'], broken=rule)['counts'] is not None
+
+
+def _dense_problem(n, m, seed):
+    rng = np.random.default_rng(seed)
+    lp, dp = rng.integers(0, 181, (n, 2)), rng.integers(0, 181, (m, 2))
+    d2 = ((lp[:, None, :] - dp[None, :, :]) ** 2).sum(2).astype(np.int64)
+    cost = mm.pair_cost_int(d2, np.arange(n)[:, None], np.arange(m)[None, :])
+    return cost, d2 <= 255 ** 2, (min(n, m) + 1) << mr.PENALTY_SHIFT
+
+
+@pytest.mark.parametrize('n, m', [(9, 9), (12, 7), (7, 12)])
+def test_the_certificate_holds_for_the_optimum_and_rejects_a_swapped_pair(n, m):
+    cost, ok, dummy = _dense_problem(n, m, n * m)
+    assert ok.all()
+    col4row, u, v = mr.solve_int(cost, ok, dummy)
+    assert mr.certificate_holds(cost, ok, dummy, col4row, u, v)
+    assert (col4row >= 0).sum() == min(n, m)
+    # brute force on the small side: no assignment of the same cardinality is cheaper
+    r, c = linear_sum_assignment(cost.astype(np.float64))            # < 2^53: 12 pairs below 2^43
+    assert sorted(zip(r.tolist(), c.tolist())) == sorted((i, int(j)) for i, j in enumerate(col4row) if j >= 0)
+    rows = np.nonzero(col4row >= 0)[0]
+    swapped = col4row.copy()
+    swapped[rows[0]], swapped[rows[1]] = col4row[rows[1]], col4row[rows[0]]
+    assert not mr.certificate_holds(cost, ok, dummy, swapped, u, v)
+    # nor does it accept: a column taken twice, a row moved to its dummy, a pair that is not admissible, duals off by one
+    twice = col4row.copy(); twice[rows[0]] = col4row[rows[1]]
+    assert not mr.certificate_holds(cost, ok, dummy, twice, u, v)
+    dropped = col4row.copy(); dropped[rows[0]] = -2
+    assert not mr.certificate_holds(cost, ok, dummy, dropped, u, v)
+    refused = ok.copy(); refused[rows[0], col4row[rows[0]]] = False
+    assert not mr.certificate_holds(cost, refused, dummy, col4row, u, v)
+    bumped = u.copy(); bumped[rows[0]] += 1
+    assert not mr.certificate_holds(cost, ok, dummy, col4row, bumped, v)
+
+
+def test_the_integer_solver_refuses_arithmetic_beyond_2_to_the_62():
+    cost, ok, dummy = _dense_problem(6, 3, 1)
+    with pytest.raises(AssertionError):
+        mr.solve_int(cost, ok, 1 << 62)
+
+
+def test_reading_a_mismatch_tells_a_worse_matching_from_a_tie():
+    s = mr.named_cases()['cardinality']
+    ref = mr.reference(s)
+    assert 'agree' in mr.explain_mismatch(s, 0, ref, ref['events'])
+    worse = {(0, 1, 0, 0), (0, 3, 1, -1)}                   # the closer pair alone: one pair fewer than the optimum
+    assert 'not the optimum' in mr.explain_mismatch(s, 0, ref, worse)
+    assert mr.matching_cost(s, 0, 0, ref['step2'][0]['pairs']) == (2, ref['step2'][0]['cost'])
+
+
+def test_size_query_at_and_beyond_the_stated_limits():
+    lib = _lib.load()
+    AXT_EINVAL = -22
+    assert _query(lib, cap=mr.MOT_MAX_SIDE, gcap=mr.MOT_MAX_SIDE, max_dist=mr.MOT_MAX_DIST)[0] == 0
+    for kw in (dict(cap=1025), dict(gcap=1025), dict(max_dist=256), dict(no=2 ** 24 + 1), dict(nh=2 ** 24 + 1)):
+        assert _query(lib, **kw)[0] == AXT_EINVAL, kw
+        assert b'axt_mot_scores' in lib.axt_last_error()
+    assert _query(lib, no=2 ** 24, nh=1)[0] == 0 and _query(lib, no=1, nh=2 ** 24)[0] == 0
+
+
 def _query(lib, K=1, F=4, cap=8, gcap=8, no=3, nh=5, max_dist=23):
     need = ctypes.c_size_t(0)
     rc = lib.axt_mot_scores(None, K, None, None, None, F, cap, None, None, None, None, gcap, no, nh, max_dist, None, None,

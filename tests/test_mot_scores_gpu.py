@@ -1,6 +1,9 @@
 """The device tracking scorer (axt_mot_scores) against the CPU reference of tests/mot_reference.py --
-counts, tallies and the event log, exactly -- and AxonDetections.get_tracking_metrics / score_associations /
+counts, tallies and the event log, exactly, on the named cases and on the limit cases (every stated limit, both sides of
+every route threshold) -- and AxonDetections.get_tracking_metrics / score_associations /
 search_MCF_params(scoring='gpu') against axtrack_amd.mot_metrics on the tie-free scenes."""
+import functools
+
 import numpy as np
 import pandas as pd
 import pytest
@@ -63,6 +66,57 @@ def test_tie_free_battery_equals_mot_metrics():
     for s, k in mr.tie_free_battery():
         counts, tallies = run(s, [k], events=False)
         assert_scores_equal(mm.scores_from_counts(counts[0], tallies[0]), mm.summarize(mr.host_events(s, k)[0]))
+
+
+# ------------------------------------------------------------------ the limits and both sides of every route threshold
+def assert_equals_the_reference(s, out, ks, ref_of, name):
+    """Counts, tallies, event log and FP slots of the associations ks (rows 0.. of out) against the reference, exactly. A
+    log that differs is first read as a matching: its cardinality and integer cost against the reference's optimum."""
+    counts, tallies, kind, part, fp = out
+    for row, k in enumerate(ks):
+        ref = ref_of(k)
+        ev, fps = log_sets(kind, part, fp, row)
+        assert ev == ref['events'], (name, mr.explain_mismatch(s, k, ref, ev))
+        assert fps == ref['fp'], (name, k)
+        assert counts[row].tolist() == ref['counts'].tolist(), (name, k, mm.MOT_COUNTS)
+        assert tallies[row].tolist() == ref['tallies'].tolist(), (name, k)
+        assert (part[row][kind[row] == 0] == -1).all() and (part[row][kind[row] == 3] == -1).all()
+
+
+@functools.lru_cache(maxsize=None)
+def first_run(name):
+    """One call per limit case, shared by the tests below and left unchanged by them."""
+    return run(mr.limit_cases()[name].scene)
+
+
+@pytest.mark.parametrize('name', list(mr.limit_cases()))
+def test_limit_case_equals_the_reference_exactly(name):
+    """Every call returns AXT_OK (hp.mot_scores raises otherwise): the launches with 65 504 and 65 688 bytes of dynamic
+    LDS, with 94 208, and the identity matching with exactly 65 536 bytes and no attribute set."""
+    s = mr.limit_cases()[name].scene
+    K = s['tracks'].shape[0]
+    assert_equals_the_reference(s, first_run(name), range(K), lambda k: mr.limit_reference(name, k), name)
+
+
+@pytest.mark.parametrize('name', list(mr.limit_cases()))
+def test_limit_case_twice_gives_the_same_bytes(name):
+    for a, b in zip(first_run(name), run(mr.limit_cases()[name].scene)):
+        assert a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize('name', ['many_associations', 'lds_edge_713'])
+def test_a_batch_of_k_gives_the_bytes_of_k_single_calls(name):
+    s = mr.limit_cases()[name].scene
+    batch = first_run(name)
+    for k in range(s['tracks'].shape[0]):
+        for a, b in zip(batch, run(s, [k])):
+            assert a[k].tobytes() == b[0].tobytes(), (name, k)
+
+
+def test_without_the_event_log_the_counts_are_the_same_at_1024_x_1024():
+    name = 'dense_1024x1024_md255'
+    counts, tallies = run(mr.limit_cases()[name].scene, events=False)
+    assert counts.tobytes() == first_run(name)[0].tobytes() and tallies.tobytes() == first_run(name)[1].tobytes()
 
 
 # ------------------------------------------------------------------ AxonDetections
