@@ -3,7 +3,8 @@
 Drop-in for the reference's public API on that path (reference __init__.py:1-16):
 setup_inference, prepare_input_data, inference -> AxonDetections.IDed_dets_all; PKG_DIR, _compute_astar_path;
 visualize_inference exists and says that matplotlib / video plotting is out of scope; render_inference draws the
-annotated frames on the GPU and writes PNG frames or one animated PNG; segment_mask makes the microchannel mask of
+annotated frames on the GPU and writes PNG frames, one animated PNG, or an MJPEG AVI video whose frames jpeg_encode
+compresses on the GPU (jpeg.py; write_mjpeg_avi is the container); segment_mask makes the microchannel mask of
 prepare_input_data(mask_fname=...) from a transmission image (data_prep_nbs/00_segment_bg.ipynb); fine_tune_head
 trains the detector's three linear layers on labelled frames with the convolutional trunk frozen (training.py), with the
 reference's translate / flip / rotate augmentation redrawn every epoch if asked (augment.py); fine_tune_detector trains
@@ -20,6 +21,7 @@ from .utils import _compute_astar_path
 from .detections import AxonDetections
 from .hotpath import Detector
 from .render import render_inference
+from .jpeg import jpeg_encode, write_mjpeg_avi
 from .timelapse import Timelapse, estimate_stnd_scaler, load_labels_csv
 from .tiff import read_tiff, tiff_info, TiffError, TiffUnsupported
 from .training import (ConvBlockTrainer, ConvStageTrainer, ConvTrunkTrainer, HeadTrainer, fine_tune_head, fine_tune_detector,
@@ -30,7 +32,7 @@ from .segment import (segment_microchannels, flood_initial_mask, segment_mask, s
                       otsu_threshold_from_hist)
 
 __all__ = ['setup_inference', 'prepare_input_data', 'inference', 'visualize_inference', 'PKG_DIR', 'DEPLOYED_MODEL_DIR',
-           '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse', 'render_inference',
+           '_compute_astar_path', 'AxonDetections', 'Detector', 'Timelapse', 'render_inference', 'jpeg_encode', 'write_mjpeg_avi',
            'ConvBlockTrainer', 'ConvStageTrainer', 'ConvTrunkTrainer', 'HeadTrainer', 'fine_tune_head', 'fine_tune_detector',
            'yolo_targets',
            'prepare_training_data', 'estimate_stnd_scaler', 'load_labels_csv',

@@ -131,6 +131,10 @@ SIGNATURES = {
     'axt_head_trainer_export': (c_int, [c_void_p, c_void_p, c_void_p]),
     'axt_tiff_decode_u16': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p,
                                     c_void_p]),
+    'axt_jpeg_scan_bound': (c_int64, [c_int, c_int]),
+    'axt_jpeg_scratch_bytes': (c_int64, [c_int, c_int, c_int]),
+    'axt_jpeg_encode_rgb8': (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_void_p]),
     'axt_augment_frame_chunk': (c_int, []),
     'axt_augment_frames': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),

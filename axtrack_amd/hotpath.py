@@ -1041,3 +1041,31 @@ def tiff_decode_u16(d_src, segs, W, compression, predictor, big_endian, out, fra
     tiff_raise_on_status(status[:n], frame, row0)
     del keep
     return out
+
+
+# ------------------------------------------------------------------ JPEG scan segments (csrc/jpeg.hip, include/axtrack_hip_jpeg.h)
+def jpeg_scan_bound(H, W):
+    """Worst-case bytes of one frame's scan segment (axt_jpeg_scan_bound)."""
+    return int(_lib.check(_lib.load().axt_jpeg_scan_bound(int(H), int(W)), 'axt_jpeg_scan_bound'))
+
+
+def jpeg_scratch_bytes(n_frames, H, W):
+    return int(_lib.check(_lib.load().axt_jpeg_scratch_bytes(int(n_frames), int(H), int(W)), 'axt_jpeg_scratch_bytes'))
+
+
+def jpeg_encode_launch(rgb, quality, scan, scan_bytes, status, scratch):
+    """axt_jpeg_encode_rgb8 on the current stream, nothing waited for. rgb: uint8 device tensor [N, H, W, 3] whose frames
+    are contiguous (the frame stride may exceed 3 H W); scan: uint8 [N, capacity]; scan_bytes: int64 [N]; status: int32
+    [N]; scratch: uint8, at least jpeg_scratch_bytes(N, H, W)."""
+    _require_gpu()
+    N, H, W, C = rgb.shape
+    assert rgb.dtype == torch.uint8 and C == 3 and (N == 0 or rgb[0].is_contiguous()) and (N <= 1 or rgb.stride(0) >= 3 * H * W)
+    assert scan.dtype == torch.uint8 and scan.is_contiguous() and scan.shape[0] == N
+    assert scan_bytes.dtype == torch.int64 and scan_bytes.numel() >= N and status.dtype == torch.int32 and status.numel() >= N
+    assert scratch.dtype == torch.uint8 and scratch.is_contiguous()
+    assert all(t.device == rgb.device for t in (scan, scan_bytes, status, scratch))
+    stride = rgb.stride(0) if N > 1 else 3 * H * W
+    with torch.cuda.device(rgb.device):
+        _lib.check(_lib.load().axt_jpeg_encode_rgb8(rgb.data_ptr(), N, H, W, int(stride), int(quality), scan.data_ptr(),
+                                                    int(scan.shape[1]), scan_bytes.data_ptr(), status.data_ptr(),
+                                                    scratch.data_ptr(), scratch.numel(), _stream()), 'axt_jpeg_encode_rgb8')

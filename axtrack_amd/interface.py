@@ -250,7 +250,7 @@ def visualize_inference(axon_dets, which_dets='IDed', **kwargs):
         'What it draws is available: axon_dets.IDed_dets_all, axon_dets.get_frame_dets(which, t), axon_dets.dataset.mask; '
         "the caches written by inference(..., *_cache='to') are in the reference's layouts, so the reference's own "
         'visualize_inference can read them. axtrack_amd.render_inference draws the annotated frames on the GPU and '
-        'writes PNG frames or one animated PNG.')
+        'writes PNG frames, one animated PNG, or with video=True an MJPEG AVI.')
 
 
 def inference(timelapse, model, dest_dir, parameters, detections_cache='to', astar_paths_cache='to',

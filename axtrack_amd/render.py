@@ -411,17 +411,23 @@ _FRAME_BYTES_PER_CHUNK = 256 << 20
 
 
 def render_inference(axon_dets, which_dets='IDed', dest_dir=None, animated=False, fps=6, anim_fname_postfix='',
-                     t_y_x_slice=(None, None, None), **kwargs):
+                     t_y_x_slice=(None, None, None), video=False, quality=90, **kwargs):
     """visualize_inference / video_plotting.draw_all (interface.py:217-320, video_plotting.py:17-113) on the GPU: renders
     the frames with AxonDetections.render_frames in chunks of frames (at most 256 MB of RGB on the device at once) and
     writes '{dest_dir}/{name}_frame{t:03}of{T:03}.png' per frame, or with animated=True one animated PNG
-    '{dest_dir}/{name}_dets{anim_fname_postfix}.png' at fps frames per second. dest_dir: default the detections'
-    directory. The drawing keywords are those of render_frames. Returns the list of paths written."""
+    '{dest_dir}/{name}_dets{anim_fname_postfix}.png' at fps frames per second, or with video=True one MJPEG AVI
+    '{dest_dir}/{name}_dets{anim_fname_postfix}.avi' (the reference's video name with this container's extension) whose
+    frames are JPEG-encoded on the GPU at `quality` (jpeg.py). dest_dir: default the detections' directory. The drawing
+    keywords are those of render_frames. Returns the list of paths written."""
+    if video and animated:
+        raise ValueError('video=True writes an MJPEG AVI, animated=True an animated PNG: ask for one of them')
+    if video and not 1 <= int(quality) <= 100:
+        raise ValueError(f'quality must lie in 1..100, got {quality!r}')
     for k, default in _UNSUPPORTED.items():
         if k in kwargs:
             v = kwargs.pop(k)
             if not (v is default or v == default):
-                raise ValueError(f'{k}={v!r} has no meaning in axtrack_amd.render_inference (frames and APNG only; '
+                raise ValueError(f'{k}={v!r} has no meaning in axtrack_amd.render_inference (frames, APNG and MJPEG AVI only; '
                                  f'DESIGN.md section 9)')
     allowed = {'draw_grid', 'draw_scalebar', 'draw_axon_reconstructions', 'draw_true_dets', 'draw_brightened_bg',
                'axon_subset', 'description', 'annotate', 'draw_target_paths'}
@@ -441,6 +447,13 @@ def render_inference(axon_dets, which_dets='IDed', dest_dir=None, animated=False
     xmin, xmax = (0, ds.sizex) if t_y_x_slice[2] is None else tuple(t_y_x_slice[2])
     per = max(1, _FRAME_BYTES_PER_CHUNK // max(1, 3 * (ymax - ymin) * (xmax - xmin)))
     name = axon_dets.name
+    if video:
+        from .jpeg import jpeg_encode, write_mjpeg_avi
+        jpegs = []
+        for a in range(tmin, tmax, per):
+            jpegs += jpeg_encode(render_frames(axon_dets, which_dets, t_y_x_slice, _frames=np.arange(a, min(a + per, tmax)), **kwargs),
+                                 quality)
+        return [write_mjpeg_avi(f'{dest_dir}/{name}_dets{anim_fname_postfix}.avi', jpegs, ymax - ymin, xmax - xmin, fps)]
     paths, payloads = [], []
     with ThreadPoolExecutor(max_workers=_POOL_THREADS) as pool:
         for a in range(tmin, tmax, per):

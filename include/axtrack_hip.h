@@ -678,6 +678,10 @@ int axt_conv_trainer_step(axt_conv_trainer *tr, const float *d_in, const int32_t
  * axt_preprocess_u16 reads. Declared in a header of its own, part of this interface. */
 #include "axtrack_hip_tiff.h"
 
+/* uint8 RGB frames, as axt_render_frames writes them, into baseline JPEG scan segments: the frames of the MJPEG video
+ * (DESIGN.md 6.8i). Declared in a header of its own, part of this interface. */
+#include "axtrack_hip_jpeg.h"
+
 /* Training augmentation of a whole timelapse in one launch (data_utils.transform_X: translate, then flip, then rotate;
  * DESIGN.md 6.8e). d_in f32 [T, H, W]; d_out the same shape, not overlapping d_in (AXT_EINVAL: the warp is a gather).
  * Output pixel (y, x) of every frame reads the source that the inverses give in reverse order:
