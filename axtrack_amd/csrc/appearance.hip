@@ -13,6 +13,8 @@
 
 namespace {
 
+constexpr int kMaxBox = 32768;       // box * box fits the int the crop is walked with; y - box / 2 cannot wrap for stitched coordinates
+
 __global__ __launch_bounds__(64) void box_hist_kernel(const float *__restrict__ frames, int H, int W, int t_offset,
                                                       const int *__restrict__ x, const int *__restrict__ y,
                                                       const int *__restrict__ count, int cap, int box,
@@ -64,8 +66,13 @@ extern "C" int axt_box_histograms(const float *d_frames, int T_all, int H, int W
                                   float *d_hist, double *d_hist_sum, void *stream)
 {
     AXT_REQUIRE(d_frames && d_x && d_y && d_count && d_hist && d_hist_sum, "axt_box_histograms: null argument");
-    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && box >= 1 && t_offset >= 0 && t_offset + n_frames <= T_all,
-                "axt_box_histograms: frames [%d,%d) outside the timelapse of %d", t_offset, t_offset + n_frames, T_all);
+    AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL, "axt_box_histograms: bad frame size %d x %d", H, W);
+    // (a crop of box x box pixels is indexed in int; the frames are the grid's second dimension)
+    AXT_REQUIRE(box >= 1 && box <= kMaxBox, "axt_box_histograms: box %d out of range (1..%d)", box, kMaxBox);
+    AXT_REQUIRE(cap >= 1 && n_frames >= 1 && n_frames <= 65535, "axt_box_histograms: cap %d below 1 or n_frames %d outside 1..65535", cap,
+                n_frames);
+    AXT_REQUIRE(t_offset >= 0 && T_all >= 1 && n_frames <= T_all && t_offset <= T_all - n_frames,
+                "axt_box_histograms: %d frames from %d on outside the timelapse of %d", n_frames, t_offset, T_all);
     hipLaunchKernelGGL(box_hist_kernel, dim3(cap, n_frames), dim3(64), 0, (hipStream_t)stream, d_frames, H, W, t_offset, d_x,
                        d_y, d_count, cap, box, d_hist, d_hist_sum);
     AXT_LAUNCH_CHECK();

@@ -233,6 +233,17 @@ __global__ void row_ptr_kernel(const int *__restrict__ cnt, const int *__restric
     if (threadIdx.x == 0) row_ptr[n_det] = carry;
 }
 
+// the scalar arguments axt_path_cost and axt_path_cells share (cells are y*W + x in i32, lengths i16)
+int path_args_check(const char *fn, int na, int nb, const axt_grid *grid, int H, int W, int max_dist)
+{
+    AXT_REQUIRE(na >= 0 && nb >= 0 && (long)na * nb <= 0x7fffffffL, "%s: na %d / nb %d negative, or more than 2^31 - 1 pairs", fn, na, nb);
+    AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL, "%s: bad grid size %d x %d", fn, H, W);
+    AXT_REQUIRE(max_dist > 0 && max_dist < 32768, "%s: max_dist %d out of range (1..32767)", fn, max_dist);
+    AXT_REQUIRE(!grid || (grid->H == H && grid->W == W), "%s: the grid is %d x %d, not %d x %d", fn, grid ? grid->H : 0,
+                grid ? grid->W : 0, H, W);
+    return AXT_OK;
+}
+
 }  // namespace
 
 int axt_frame_offsets(const int32_t *d_count, int n_frames, int cap, int32_t *d_off, hipStream_t st)
@@ -247,9 +258,11 @@ extern "C" {
 int axt_obs_costs(const float *d_conf, const int32_t *d_count, int n_frames, int cap, int method, double max_conf_cost,
                   double *d_cost, void *stream)
 {
-    AXT_REQUIRE(d_conf && d_count && d_cost, "null argument");
-    AXT_REQUIRE(method == 0 || method == 1, "method must be 0 (scale_to_max) or 1 (ceil)");
-    if (n_frames <= 0) return AXT_OK;
+    AXT_REQUIRE(d_conf && d_count && d_cost, "axt_obs_costs: null argument");
+    AXT_REQUIRE(method == 0 || method == 1, "axt_obs_costs: method %d must be 0 (scale_to_max) or 1 (ceil)", method);
+    AXT_REQUIRE(n_frames >= 0 && cap >= 1, "axt_obs_costs: n_frames %d negative or cap %d below 1", n_frames, cap);
+    AXT_REQUIRE(std::isfinite(max_conf_cost), "axt_obs_costs: max_conf_cost %g is not finite", max_conf_cost);
+    if (n_frames == 0) return AXT_OK;
     hipStream_t st = (hipStream_t)stream;
     unsigned int *mx = nullptr;
     AXT_CHECK_HIP(hipMallocAsync((void **)&mx, sizeof(unsigned int), st));
@@ -266,9 +279,9 @@ int axt_obs_costs(const float *d_conf, const int32_t *d_count, int n_frames, int
 int axt_path_cost(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_t *d_xb, const int32_t *d_yb, int nb,
                   const axt_grid *grid, int H, int W, int max_dist, int conn8, int32_t *d_D, void *stream)
 {
-    AXT_REQUIRE(na >= 0 && nb >= 0 && H > 0 && W > 0 && max_dist > 0 && max_dist < 32768, "bad argument");
+    if (int rc = path_args_check("axt_path_cost", na, nb, grid, H, W, max_dist)) return rc;
     if ((long)na * nb == 0) return AXT_OK;
-    AXT_REQUIRE(d_xa && d_ya && d_xb && d_yb && d_D, "null argument");
+    AXT_REQUIRE(d_xa && d_ya && d_xb && d_yb && d_D, "axt_path_cost: null argument");
     hipStream_t st = (hipStream_t)stream;
     if (grid) return axt_path_cost_masked(d_xa, d_ya, na, d_xb, d_yb, nb, grid->d_mask, H, W, max_dist, conn8, d_D, st, nullptr);
     const long n = (long)na * nb;
@@ -281,10 +294,10 @@ int axt_path_cost(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_
 int axt_path_cells(const int32_t *d_xa, const int32_t *d_ya, int na, const int32_t *d_xb, const int32_t *d_yb, int nb,
                    const axt_grid *grid, int H, int W, int max_dist, int conn8, int32_t *d_D, int32_t *d_cells, void *stream)
 {
-    AXT_REQUIRE(na >= 0 && nb >= 0 && H > 0 && W > 0 && max_dist > 0 && max_dist < 32768, "bad argument");
+    if (int rc = path_args_check("axt_path_cells", na, nb, grid, H, W, max_dist)) return rc;
     AXT_REQUIRE(grid, "axt_path_cells: needs a masked grid (on an all-ones mask every monotone staircase is a shortest path)");
     if ((long)na * nb == 0) return AXT_OK;
-    AXT_REQUIRE(d_xa && d_ya && d_xb && d_yb && d_D && d_cells, "null argument");
+    AXT_REQUIRE(d_xa && d_ya && d_xb && d_yb && d_D && d_cells, "axt_path_cells: null argument");
     return axt_path_cost_masked(d_xa, d_ya, na, d_xb, d_yb, nb, grid->d_mask, H, W, max_dist, conn8, d_D,
                                 (hipStream_t)stream, d_cells);
 }
@@ -295,13 +308,33 @@ int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_coun
                    int64_t *d_row_ptr, int32_t *d_work, int32_t *d_col, int16_t *d_len, uint8_t *d_gap,
                    const int64_t *d_cost_units, int64_t *d_cost, int64_t *n_arcs, const int16_t *d_len_table, void *stream)
 {
-    AXT_REQUIRE(d_x && d_y && d_count && h_dmax && d_row_ptr && d_work && n_arcs, "null argument");
-    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && max_gap >= 1 && max_gap <= 8, "bad argument");
+    static const char fn[] = "axt_build_arcs";
+    AXT_REQUIRE(d_x && d_y && d_count && h_dmax && d_row_ptr && d_work && n_arcs, "%s: null argument", fn);
+    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && max_gap >= 1 && max_gap <= 8, "%s: bad argument (n_frames %d, cap %d, max_gap %d not in 1..8)",
+                fn, n_frames, cap, max_gap);
+    // detections are numbered in int, and the masked-grid search keeps a row of cap targets per source in LDS
+    AXT_REQUIRE((size_t)n_frames * (size_t)cap * (size_t)max_gap <= (size_t)0x7fffffff, "%s: n_frames %d x cap %d x max_gap %d exceeds 2^31 - 1",
+                fn, n_frames, cap, max_gap);
+    AXT_REQUIRE(max_dist >= 1 && max_dist < 32768, "%s: max_dist %d out of range (1..32767)", fn, max_dist);
     const bool vis = d_hist != nullptr;
+    if (!d_len_table) {
+        AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL, "%s: bad grid size %d x %d", fn, H, W);
+        AXT_REQUIRE(!grid || (grid->H == H && grid->W == W), "%s: the grid is not %d x %d", fn, H, W);
+    }
+    // lengths from a table (the caller's, or a grid's searches) can reach h_dmax and index the units table with it; the
+    // closed form never exceeds max_dist
+    const bool table_lengths = d_len_table != nullptr || grid != nullptr;
+    for (int g = 0; g < max_gap; ++g) {
+        AXT_REQUIRE(h_dmax[g] >= 0 && h_dmax[g] < 32768, "%s: h_dmax[%d] = %d out of range (0..32767)", fn, g, h_dmax[g]);
+        AXT_REQUIRE(!(table_lengths && d_cost_units && !vis) || h_dmax[g] <= max_dist,
+                    "%s: h_dmax[%d] = %d exceeds max_dist %d: the units table has max_dist + 1 entries per gap", fn, g, h_dmax[g], max_dist);
+    }
     VisParams vp{};
     if (vis) {
         AXT_REQUIRE(d_hist_sum, "axt_build_arcs: null histogram sums");
         AXT_REQUIRE(vis_weight > 0.0 && vis_weight <= 1.0, "axt_build_arcs: weight %g outside (0,1]", vis_weight);
+        AXT_REQUIRE(std::isfinite(miss_rate) && miss_rate >= 0.0, "axt_build_arcs: miss_rate %g is not a finite number >= 0", miss_rate);
+        AXT_REQUIRE(edge_cost_thr == edge_cost_thr, "axt_build_arcs: edge_cost_thr is not a number");
         vp.hist = d_hist;
         vp.hsum = d_hist_sum;
         vp.w = vis_weight;
@@ -359,8 +392,8 @@ int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_coun
         *n_arcs = total;
         return AXT_OK;
     }
-    AXT_REQUIRE(d_len && d_gap, "null argument");
-    AXT_REQUIRE(vis || (d_cost == nullptr) == (d_cost_units == nullptr), "d_cost and d_cost_units go together");
+    AXT_REQUIRE(d_len && d_gap, "axt_build_arcs: null argument");
+    AXT_REQUIRE(vis || (d_cost == nullptr) == (d_cost_units == nullptr), "axt_build_arcs: d_cost and d_cost_units go together");
     if (table && vis) launch(arcs_open_kernel<true, true, true>);
     else if (table) launch(arcs_open_kernel<true, true, false>);
     else if (vis) launch(arcs_open_kernel<true, false, true>);

@@ -108,14 +108,16 @@ extern "C" int axt_augment_frames(const float *d_in, int T, int H, int W, int dy
                                   int rotate, float m00, float m01, float m10, float m11, float *d_out, uint8_t *d_occ,
                                   void *stream)
 {
-    AXT_REQUIRE(d_in && d_out, "null argument");
-    AXT_REQUIRE(T >= 1 && H >= 1 && W >= 1, "bad shape T=%d H=%d W=%d", T, H, W);
-    AXT_REQUIRE((long long)H * W <= 0x7fffffffLL, "a frame of %d x %d pixels: the pixel index must fit 31 bits", H, W);
-    const size_t n = (size_t)T * H * W;
-    AXT_REQUIRE(d_out + n <= d_in || d_in + n <= d_out, "d_out overlaps d_in: the warp is a gather and cannot run in place");
+    AXT_REQUIRE(d_in && d_out, "axt_augment_frames: null argument");
+    AXT_REQUIRE(T >= 1 && H >= 1 && W >= 1, "axt_augment_frames: bad shape T=%d H=%d W=%d", T, H, W);
+    AXT_REQUIRE((long long)H * W <= 0x7fffffffLL, "axt_augment_frames: a frame of %d x %d pixels: the pixel index must fit 31 bits", H, W);
+    AXT_REQUIRE(!rotate || (std::isfinite(m00) && std::isfinite(m01) && std::isfinite(m10) && std::isfinite(m11)),
+                "axt_augment_frames: the rotation matrix (%g %g / %g %g) is not finite", (double)m00, (double)m01, (double)m10, (double)m11);
     const dim3 block(64, kAugRows), grid(axt_cdiv(W, 64 * kAugPx), axt_cdiv(H, kAugRows), axt_cdiv(T, kAugFrameChunk));
-    AXT_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "timelapse too large for one launch (H <= %d, T <= %d)",
+    AXT_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "axt_augment_frames: timelapse too large for one launch (H <= %d, T <= %d)",
                 65535 * kAugRows, 65535 * kAugFrameChunk);
+    const size_t n = (size_t)T * H * W;
+    AXT_REQUIRE(d_out + n <= d_in || d_in + n <= d_out, "axt_augment_frames: d_out overlaps d_in: the warp is a gather and cannot run in place");
     hipStream_t st = (hipStream_t)stream;
     const int nty = axt_cdiv(H, AXT_TILE), ntx = axt_cdiv(W, AXT_TILE);
     if (d_occ) AXT_CHECK_HIP(hipMemsetAsync(d_occ, 0, (size_t)T * nty * ntx, st));

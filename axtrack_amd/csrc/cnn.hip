@@ -2197,7 +2197,7 @@ int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, 
     tl.n = n_tiles;
     for (int k = 0; k < n_tiles; ++k) {
         const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * AXT_TILE < H && tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
                     ty, tx, H, W);
         tl.yx[2 * k] = (short)ty;
         tl.yx[2 * k + 1] = (short)tx;
@@ -2217,7 +2217,7 @@ int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all,
     tl.n = n_tiles;
     for (int k = 0; k < n_tiles; ++k) {
         const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * AXT_TILE < H && tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
                     ty, tx, H, W);
         tl.yx[2 * k] = (short)ty;
         tl.yx[2 * k + 1] = (short)tx;
@@ -2239,7 +2239,7 @@ int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int 
     tl.n = n_tiles;
     for (int k = 0; k < n_tiles; ++k) {
         const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * AXT_TILE < H && tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
                     ty, tx, H, W);
         tl.yx[2 * k] = (short)ty;
         tl.yx[2 * k + 1] = (short)tx;
@@ -2263,7 +2263,7 @@ int axt_cnn_front_frames(axt_detector *det, const float *d_frames, int T_all, in
     tl.n = n_tiles;
     for (int k = 0; k < n_tiles; ++k) {
         const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * AXT_TILE < H && tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
                     ty, tx, H, W);
         tl.yx[2 * k] = (short)ty;
         tl.yx[2 * k + 1] = (short)tx;

@@ -46,6 +46,8 @@ __global__ __launch_bounds__(256) void tile_occupancy_kernel(const float *__rest
     }
 }
 
+constexpr int kOccMaxFrames = 65535 + 4;       // the second launch puts T_all - 4 frames into the grid's y dimension
+
 __global__ void occ_words_to_bytes(const unsigned int *__restrict__ w, uint8_t *__restrict__ out, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -58,8 +60,19 @@ __global__ void occ_words_to_bytes(const unsigned int *__restrict__ w, uint8_t *
 // ------------------------------------------------------------------------------------------------
 constexpr int ST_UNDECIDED = 0, ST_ALIVE = 1, ST_DEAD = 2;
 
+// dx^2 + dy^2 < min_dist^2, exact for any two pairs of int coordinates: the differences are taken in 64 bits (tiles 128
+// columns apart differ by 65536, whose 32-bit square is 0), and a pair with |dx| or |dy| >= min_dist is out without a
+// product. What is left has |dx|, |dy| <= 32766 (min_dist < 32768, checked by the entry point): the sum fits 31 bits.
+__device__ inline bool nms_within(int xj, int yj, int xi, int yi, int min_dist)
+{
+    const long dx = (long)xj - xi, dy = (long)yj - yi;
+    if (dx <= -(long)min_dist || dx >= min_dist || dy <= -(long)min_dist || dy >= min_dist) return false;
+    const int ix = (int)dx, iy = (int)dy;
+    return ix * ix + iy * iy < min_dist * min_dist;
+}
+
 __global__ __launch_bounds__(256) void decode_stitch_nms_kernel(
-    const float *__restrict__ yolo, int n_tiles, TileOrigins tiles, float conf_thr, int thr2, int cap,
+    const float *__restrict__ yolo, int n_tiles, TileOrigins tiles, float conf_thr, int min_dist, int cap,
     float *__restrict__ o_conf, int *__restrict__ o_x, int *__restrict__ o_y, int *__restrict__ o_count)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -113,7 +126,7 @@ __global__ __launch_bounds__(256) void decode_stitch_nms_kernel(
     const int n = n_kept;
 
     // ---- greedy NMS (AxonDetections.py:261-274) resolved in parallel rounds: row i dies iff an
-    // earlier ALIVE row lies within dx^2+dy^2 < thr2; it is alive once every earlier row within
+    // earlier ALIVE row lies within dx^2+dy^2 < min_dist^2 (nms_within); it is alive once every earlier row within
     // that distance is known dead. The fixed point is unique (= the sequential result).
     for (int round = 0; round <= n; ++round) {
         int pending_any = 0;
@@ -122,8 +135,7 @@ __global__ __launch_bounds__(256) void decode_stitch_nms_kernel(
             const int xi = s_x[i], yi = s_y[i];
             int st = ST_ALIVE;
             for (int j = 0; j < i; ++j) {
-                const int dx = s_x[j] - xi, dy = s_y[j] - yi;
-                if (dx * dx + dy * dy < thr2) {
+                if (nms_within(s_x[j], s_y[j], xi, yi, min_dist)) {
                     const int sj = state[j];
                     if (sj == ST_ALIVE) { st = ST_DEAD; break; }
                     if (sj == ST_UNDECIDED) st = ST_UNDECIDED;
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(256) void decode_stitch_nms_kernel(
 // workspace per frame: kept conf/x/y/idx [ncand], sorted conf/x/y [ncand], state [ncand]  (8 x ncand x 4 bytes)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void decode_stitch_nms_big_kernel(
-    const float *__restrict__ yolo, int n_tiles, TileOrigins tiles, float conf_thr, int thr2, int cap,
+    const float *__restrict__ yolo, int n_tiles, TileOrigins tiles, float conf_thr, int min_dist, int cap,
     float *__restrict__ o_conf, int *__restrict__ o_x, int *__restrict__ o_y, int *__restrict__ o_count,
     unsigned char *__restrict__ work)
 {
@@ -252,8 +264,7 @@ __global__ __launch_bounds__(256) void decode_stitch_nms_big_kernel(
             const int xi = s_x[i], yi = s_y[i];
             int st = ST_ALIVE;
             for (int j = 0; j < i; ++j) {
-                const int dx = s_x[j] - xi, dy = s_y[j] - yi;
-                if (dx * dx + dy * dy < thr2) {
+                if (nms_within(s_x[j], s_y[j], xi, yi, min_dist)) {
                     const int sj = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if (sj == ST_ALIVE) { st = ST_DEAD; break; }
                     if (sj == ST_UNDECIDED) st = ST_UNDECIDED;
@@ -296,8 +307,11 @@ extern "C" {
 
 int axt_tile_occupancy(const float *d_frames, int T_all, int H, int W, uint8_t *d_occ, void *stream)
 {
-    AXT_REQUIRE(d_frames && d_occ, "null argument");
-    AXT_REQUIRE(T_all > 0 && H > 0 && W > 0, "bad shape %dx%dx%d", T_all, H, W);
+    AXT_REQUIRE(d_frames && d_occ, "axt_tile_occupancy: null argument");
+    AXT_REQUIRE(T_all > 0 && H > 0 && W > 0, "axt_tile_occupancy: bad shape %dx%dx%d", T_all, H, W);
+    AXT_REQUIRE((long)H * W <= 0x7fffffffL, "axt_tile_occupancy: a frame of %d x %d pixels exceeds 2^31 - 1", H, W);
+    AXT_REQUIRE(T_all <= kOccMaxFrames, "axt_tile_occupancy: T_all %d exceeds %d (one launch spans T_all - 4 frames)", T_all,
+                kOccMaxFrames);
     hipStream_t st = (hipStream_t)stream;
     const int nty = axt_cdiv(H, AXT_TILE), ntx = axt_cdiv(W, AXT_TILE);
     unsigned int *words = nullptr;
@@ -323,11 +337,17 @@ int axt_decode_stitch_nms(const float *d_yolo, int n_frames, int n_tiles, const 
                           int min_dist, int cap, float *d_conf, int32_t *d_x, int32_t *d_y, int32_t *d_count,
                           void *stream)
 {
-    AXT_REQUIRE(d_yolo && h_tile_yx && d_conf && d_x && d_y && d_count, "null argument");
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range (1..256)", n_tiles);
-    AXT_REQUIRE(cap >= n_tiles * AXT_CELLS, "cap %d < n_tiles*144 = %d", cap, n_tiles * AXT_CELLS);
-    AXT_REQUIRE(min_dist >= 0 && min_dist < 32768, "min_dist out of range");
-    if (n_frames <= 0) return AXT_OK;
+    static const char fn[] = "axt_decode_stitch_nms";
+    AXT_REQUIRE(d_yolo && h_tile_yx && d_conf && d_x && d_y && d_count, "%s: null argument", fn);
+    AXT_REQUIRE(n_frames >= 0, "%s: n_frames %d is negative", fn, n_frames);
+    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "%s: n_tiles %d out of range (1..256)", fn, n_tiles);
+    AXT_REQUIRE(cap >= n_tiles * AXT_CELLS, "%s: cap %d < n_tiles*144 = %d", fn, cap, n_tiles * AXT_CELLS);
+    AXT_REQUIRE((long)n_frames * cap <= 0x7fffffffL, "%s: n_frames %d x cap %d exceeds 2^31 - 1 slots", fn, n_frames, cap);
+    AXT_REQUIRE(min_dist >= 0 && min_dist < 32768, "%s: min_dist %d out of range (0..32767)", fn, min_dist);
+    AXT_REQUIRE(conf_thr == conf_thr, "%s: conf_thr is not a number", fn);
+    for (int k = 0; k < 2 * n_tiles; ++k)          // (TileOrigins keeps them as short)
+        AXT_REQUIRE(h_tile_yx[k] >= 0 && h_tile_yx[k] <= 32767, "%s: tile %d has index %d outside 0..32767", fn, k / 2, h_tile_yx[k]);
+    if (n_frames == 0) return AXT_OK;
     TileOrigins tiles;
     tiles.n = n_tiles;
     for (int k = 0; k < n_tiles; ++k) {
@@ -340,7 +360,7 @@ int axt_decode_stitch_nms(const float *d_yolo, int n_frames, int n_tiles, const 
         unsigned char *work = nullptr;
         AXT_CHECK_HIP(hipMallocAsync((void **)&work, per_frame * (size_t)n_frames, st));
         hipLaunchKernelGGL(decode_stitch_nms_big_kernel, dim3(n_frames), dim3(256), 0, st, d_yolo, n_tiles, tiles, conf_thr,
-                           min_dist * min_dist, cap, d_conf, d_x, d_y, d_count, work);
+                           min_dist, cap, d_conf, d_x, d_y, d_count, work);
         AXT_LAUNCH_CHECK();
         AXT_CHECK_HIP(hipFreeAsync(work, st));
         return AXT_OK;
@@ -349,7 +369,7 @@ int axt_decode_stitch_nms(const float *d_yolo, int n_frames, int n_tiles, const 
     static AxtOncePerDevice once;                 // (per device: see axt_common.h)
     if (int rc = axt_max_dynamic_lds(decode_stitch_nms_kernel, 28 * AXT_CELLS * 7 * 4, once)) return rc;
     hipLaunchKernelGGL(decode_stitch_nms_kernel, dim3(n_frames), dim3(256), lds, (hipStream_t)stream, d_yolo, n_tiles,
-                       tiles, conf_thr, min_dist * min_dist, cap, d_conf, d_x, d_y, d_count);
+                       tiles, conf_thr, min_dist, cap, d_conf, d_x, d_y, d_count);
     AXT_LAUNCH_CHECK();
     return AXT_OK;
 }

@@ -631,10 +631,26 @@ extern "C" int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const
                                    const int32_t *h_dmax, const int64_t *d_cost_units, int64_t thr_units, int t_begin,
                                    int t_end, int32_t *d_pred, int32_t *d_work, void *stream, const int64_t *d_ctab)
 {
-    AXT_REQUIRE(d_x && d_y && d_count && (d_ctab || (h_dmax && d_cost_units)) && d_work && d_pred, "null argument");
-    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && cap <= 2048, "axt_hungarian_pairs: cap %d out of range [1,2048]", cap);
+    AXT_REQUIRE(d_x && d_y && d_count && (d_ctab || (h_dmax && d_cost_units)) && d_work && d_pred, "axt_hungarian_pairs: null argument");
+    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && cap <= 2048, "axt_hungarian_pairs: cap %d out of range [1,2048] or n_frames %d below 1", cap,
+                n_frames);
+    AXT_REQUIRE((long)n_frames * cap <= 0x3fffffffL, "axt_hungarian_pairs: n_frames %d x cap %d exceeds 2^30 - 1 slots", n_frames, cap);
     AXT_REQUIRE(max_gap == 1 || max_gap == 2, "axt_hungarian_pairs: max_gap must be 1 or 2");
     AXT_REQUIRE(t_begin >= 0 && t_begin <= t_end && t_end <= n_frames, "axt_hungarian_pairs: bad frame range [%d,%d)", t_begin, t_end);
+    // (a dummy cost is thr_units << 16 | hash: it has to fit an i64)
+    AXT_REQUIRE(thr_units >= 0 && thr_units <= ((int64_t)1 << 46), "axt_hungarian_pairs: thr_units %lld out of range [0, 2^46]",
+                (long long)thr_units);
+    if (!d_ctab) {
+        AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL, "axt_hungarian_pairs: bad grid size %d x %d", H, W);
+        AXT_REQUIRE(!grid || (grid->H == H && grid->W == W), "axt_hungarian_pairs: the grid is not %d x %d", H, W);
+        AXT_REQUIRE(max_dist >= 1 && max_dist < 32768, "axt_hungarian_pairs: max_dist %d out of range (1..32767)", max_dist);
+        // the kernels stage units[0 .. max_dist] of a gap in LDS; only the closed form keeps its lengths below that by itself
+        for (int g = 0; g < max_gap; ++g) {
+            AXT_REQUIRE(h_dmax[g] >= 0 && h_dmax[g] < 32768, "axt_hungarian_pairs: h_dmax[%d] = %d out of range (0..32767)", g, h_dmax[g]);
+            AXT_REQUIRE(!grid || h_dmax[g] <= max_dist, "axt_hungarian_pairs: h_dmax[%d] = %d exceeds max_dist %d: the units table has "
+                        "max_dist + 1 entries per gap", g, h_dmax[g], max_dist);
+        }
+    }
     int dmax[2] = {0, 0};                          // the admission limits per gap (h_dmax may be NULL, or hold one entry)
     if (d_ctab) {
         // Link costs given: the kernels use neither path lengths nor limits nor units (they stage units[0 .. limit] in LDS,
@@ -645,8 +661,14 @@ extern "C" int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const
         conn8 = 0;
         d_cost_units = d_ctab;
     } else {
-        for (int g = 0; g < max_gap; ++g) dmax[g] = h_dmax[g];
+        // The kernels stage units[0 .. dmax] in the (max_dist + 2) * 8 bytes of LDS reserved below and lay the arrays after it
+        // out from dmax. No length exceeds max_dist (the closed form by construction, a grid's by the check above), so a
+        // larger limit admits nothing more: clamp it, or the staging reads past the units table and writes past the LDS.
+        for (int g = 0; g < max_gap; ++g) dmax[g] = h_dmax[g] < max_dist ? h_dmax[g] : max_dist;
     }
+    const size_t lds_base = (size_t)cap * (3 * 8 + 8 * 4 + 2) + 8 + (size_t)(max_dist + 2) * 8 + 8 +
+                            (size_t)cap * 8 + (cap <= 576 ? (size_t)cap * 48 : 0);       // + dummy costs, + the initialisation's partial minima
+    AXT_REQUIRE(lds_base <= 160 * 1024, "axt_hungarian_pairs: cap %d and max_dist %d need %zu bytes of LDS", cap, max_dist, lds_base);
     hipStream_t st = (hipStream_t)stream;
     const long slots = (long)n_frames * cap;
     int *pred1 = d_pred, *pred2 = d_pred + slots;
@@ -655,9 +677,6 @@ extern "C" int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const
     AXT_LAUNCH_CHECK();
     int rc = axt_frame_offsets(d_count, n_frames, cap, frame_off, st);
     if (rc) return rc;
-    const size_t lds_base = (size_t)cap * (3 * 8 + 8 * 4 + 2) + 8 + (size_t)(max_dist + 2) * 8 + 8 +
-                            (size_t)cap * 8 + (cap <= 576 ? (size_t)cap * 48 : 0);       // + dummy costs, + the initialisation's partial minima
-    AXT_REQUIRE(lds_base <= 160 * 1024, "axt_hungarian_pairs: cap %d needs %zu bytes of LDS", cap, lds_base);
     // pairs with at most cdim x cdim detections keep their cost matrix in LDS (72 KiB) instead of recomputing it
     int cdim = cap < 96 ? cap : 96;
     if (lds_base + (size_t)cdim * cdim * 8 > 160 * 1024) cdim = 0;
@@ -713,7 +732,9 @@ extern "C" int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const
 extern "C" int axt_chain_tracks(const int32_t *d_count, int n_frames, int cap, const int32_t *d_pred, int32_t *d_work,
                                 int32_t *d_track, int32_t *d_n_tracks, void *stream)
 {
-    AXT_REQUIRE(d_count && d_pred && d_work && d_track && d_n_tracks && n_frames >= 1 && cap >= 1, "bad argument");
+    AXT_REQUIRE(d_count && d_pred && d_work && d_track && d_n_tracks, "axt_chain_tracks: null argument");
+    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && (long)n_frames * cap <= 0x3fffffffL,
+                "axt_chain_tracks: n_frames %d or cap %d below 1, or more than 2^30 - 1 slots", n_frames, cap);
     hipStream_t st = (hipStream_t)stream;
     const long slots = (long)n_frames * cap;
     const int *pred1 = d_pred, *pred2 = d_pred + slots;

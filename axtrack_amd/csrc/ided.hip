@@ -74,8 +74,11 @@ extern "C" int axt_ided_table(const int32_t *d_track, const float *d_conf, const
                               const int32_t *d_count, int n_frames, int cap, int n_ids, const int32_t *d_id_row, int n_rows,
                               int label_quirk, int32_t *d_work, double *d_table, void *stream)
 {
-    AXT_REQUIRE(d_track && d_conf && d_x && d_y && d_count && d_work && n_frames >= 1 && cap >= 1, "axt_ided_table: bad argument");
+    AXT_REQUIRE(d_track && d_conf && d_x && d_y && d_count && d_work, "axt_ided_table: null argument");
+    AXT_REQUIRE(n_frames >= 1 && cap >= 1, "axt_ided_table: n_frames %d or cap %d below 1", n_frames, cap);
     AXT_REQUIRE(n_ids >= 0 && n_rows >= 0 && (d_id_row || n_rows == n_ids), "axt_ided_table: n_rows %d != n_ids %d without a row map", n_rows, n_ids);
+    AXT_REQUIRE((long)n_frames * cap <= 0x7fffffffL && (long)n_rows * n_frames <= 0x7fffffffL,
+                "axt_ided_table: %d frames x cap %d or %d rows x %d frames exceed 2^31 - 1", n_frames, cap, n_rows, n_frames);
     if (n_rows == 0) return AXT_OK;
     AXT_REQUIRE(d_table, "axt_ided_table: null table");
     hipStream_t st = (hipStream_t)stream;

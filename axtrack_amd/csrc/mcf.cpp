@@ -1224,7 +1224,7 @@ static int mcf_solve_impl(int n_det, const int64_t *h_obs, const int64_t *h_entr
                           int64_t *h_pot_u = nullptr, int64_t *h_pot_v = nullptr, int64_t *pot_t = nullptr)
 {
     if (n_det < 0 || !h_row_ptr || !n_tracks || !total_cost || (n_det > 0 && (!h_obs || !h_entry || !h_exit || !h_next || !h_track))) {
-        axt_set_error("axt_mcf_solve: null or negative argument");
+        axt_set_error("axt_mcf_solve: null argument, or n_det %d negative", n_det);
         return AXT_EINVAL;
     }
     if (min_flow < 0 || max_flow < min_flow) {
@@ -1352,7 +1352,9 @@ static int mcf_solve_impl(int n_det, const int64_t *h_obs, const int64_t *h_entr
     }
     *n_tracks = id;
     *total_cost = total;
-    if (h_pot_u && !done) {
+    if (h_pot_u && n_det == 0) {
+        *pot_t = 0;                               // an empty network: no search ran, the solver holds no potentials
+    } else if (h_pot_u && !done) {
         for (int k = 0; k < n_det; ++k) { h_pot_u[k] = s.pi[s.U(k)] - s.pi[s.S]; h_pot_v[k] = s.pi[s.V(k)] - s.pi[s.S]; }
         *pot_t = s.pi[s.T] - s.pi[s.S];
     }

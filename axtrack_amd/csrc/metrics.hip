@@ -99,7 +99,9 @@ extern "C" int axt_detection_confusion(const float *d_conf, const int32_t *d_x, 
                                        void *stream)
 {
     AXT_REQUIRE(d_conf && d_x && d_y && d_count && d_gx && d_gy && d_gcount && d_thrs && d_confusion, "axt_detection_confusion: null argument");
-    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && cap <= 2048 && gcap >= 1 && n_thr >= 1, "axt_detection_confusion: bad shape");
+    AXT_REQUIRE(n_frames >= 1 && cap >= 1 && cap <= 2048 && gcap >= 1 && n_thr >= 1 && n_thr <= 65535,
+                "axt_detection_confusion: bad shape (%d frames, cap %d not in 1..2048, gcap %d, %d thresholds not in 1..65535)", n_frames, cap,
+                gcap, n_thr);
     AXT_REQUIRE(min_dist >= 0 && min_dist <= 1024, "axt_detection_confusion: min_dist %d out of range", min_dist);
     AXT_REQUIRE(k_mask < n_thr, "axt_detection_confusion: mask threshold index %d >= %d", k_mask, n_thr);
     hipLaunchKernelGGL(confusion_kernel, dim3(n_frames, n_thr), dim3(64), sizeof(unsigned) * ((cap + 31) / 32 + 1),

@@ -194,21 +194,31 @@ static int stats_blocks_per_frame(int T, long frame_px)
     return bpf < 1 ? 1 : (int)bpf;
 }
 
+// the arguments the three entry points share: T frames of H x W pixels (a frame's pixels are counted in 31 bits, as
+// everywhere in the package, so that T * H * W fits a long), offset and clip_lower finite
+static int prep_args_check(const char *fn, int T, int H, int W, float offset, float clip_lower)
+{
+    AXT_REQUIRE(T > 0 && H > 0 && W > 0 && (long)H * W <= 0x7fffffffL, "%s: bad shape %d x %d x %d", fn, T, H, W);
+    AXT_REQUIRE(std::isfinite(offset) && std::isfinite(clip_lower), "%s: offset %g or clip_lower %g is not finite", fn, (double)offset,
+                (double)clip_lower);
+    return AXT_OK;
+}
+
 }  // namespace
 
 extern "C" int axt_preprocess_stats_u16(const uint16_t *d_raw, const uint8_t *d_mask, int T, int H, int W, float offset,
                                         float clip_lower, int log_correct, axt_frame_stats *d_stats, void *d_scratch,
                                         size_t *scratch_bytes, void *stream)
 {
-    AXT_REQUIRE(scratch_bytes, "null argument");
-    AXT_REQUIRE(T > 0 && H > 0 && W > 0, "bad argument");
+    AXT_REQUIRE(scratch_bytes, "axt_preprocess_stats_u16: null argument");
+    if (int rc = prep_args_check("axt_preprocess_stats_u16", T, H, W, offset, clip_lower)) return rc;
     const long frame = (long)H * W;
     const int bpf = stats_blocks_per_frame(T, frame);
     const size_t have = *scratch_bytes, need = (size_t)T * bpf * sizeof(axt_frame_stats);
     *scratch_bytes = need;
     if (!d_scratch) return AXT_OK;                    // size query
-    AXT_REQUIRE(d_raw && d_stats, "null argument");
-    AXT_REQUIRE(have >= need, "scratch of %zu bytes, %zu needed", have, need);
+    AXT_REQUIRE(d_raw && d_stats, "axt_preprocess_stats_u16: null argument");
+    AXT_REQUIRE(have >= need, "axt_preprocess_stats_u16: scratch of %zu bytes, %zu needed", have, need);
     axt_frame_stats *partials = static_cast<axt_frame_stats *>(d_scratch);
     hipLaunchKernelGGL(preprocess_stats_kernel, dim3((unsigned)(T * bpf)), dim3(256), 0, (hipStream_t)stream, d_raw, d_mask,
                        frame, bpf, offset, clip_lower, log_correct, partials);
@@ -223,8 +233,8 @@ extern "C" int axt_preprocess_u16_framewise(const uint16_t *d_raw, const uint8_t
                                             float clip_lower, int log_correct, const float *d_scale, float *d_out,
                                             void *stream)
 {
-    AXT_REQUIRE(d_raw && d_out && d_scale, "null argument");
-    AXT_REQUIRE(T > 0 && H > 0 && W > 0, "bad argument");
+    AXT_REQUIRE(d_raw && d_out && d_scale, "axt_preprocess_u16_framewise: null argument");
+    if (int rc = prep_args_check("axt_preprocess_u16_framewise", T, H, W, offset, clip_lower)) return rc;
     const long n = (long)T * H * W, frame = (long)H * W;
     long blocks = (n / 8 + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;
@@ -238,8 +248,9 @@ extern "C" int axt_preprocess_u16_framewise(const uint16_t *d_raw, const uint8_t
 extern "C" int axt_preprocess_u16(const uint16_t *d_raw, const uint8_t *d_mask, int T, int H, int W, float offset,
                                   float clip_lower, int log_correct, float scale, float *d_out, void *stream)
 {
-    AXT_REQUIRE(d_raw && d_out, "null argument");
-    AXT_REQUIRE(T > 0 && H > 0 && W > 0 && scale > 0.f, "bad argument");
+    AXT_REQUIRE(d_raw && d_out, "axt_preprocess_u16: null argument");
+    if (int rc = prep_args_check("axt_preprocess_u16", T, H, W, offset, clip_lower)) return rc;
+    AXT_REQUIRE(scale > 0.f, "axt_preprocess_u16: scale %g is not above 0", (double)scale);
     const long n = (long)T * H * W, frame = (long)H * W;
     long blocks = (n / 8 + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;

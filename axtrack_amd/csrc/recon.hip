@@ -458,10 +458,13 @@ struct StageCounts {
 extern "C" int axt_track_links(const int32_t *d_track, const int32_t *d_count, int n_frames, int cap, int max_gap,
                                int32_t *d_links, int32_t *d_work, int64_t *n_links, void *stream)
 {
-    AXT_REQUIRE(n_frames >= 0 && cap >= 1 && max_gap >= 1 && n_links, "bad argument");
+    AXT_REQUIRE(n_links, "axt_track_links: null argument");
+    AXT_REQUIRE(n_frames >= 0 && cap >= 1 && (long)n_frames * cap <= 0x3fffffffL,
+                "axt_track_links: n_frames %d negative, cap %d below 1, or more than 2^30 - 1 slots", n_frames, cap);
+    AXT_REQUIRE(max_gap >= 1 && max_gap <= 255, "axt_track_links: max_gap %d out of range (1..255)", max_gap);
+    AXT_REQUIRE(n_frames == 0 || (d_track && d_count && d_links && d_work), "axt_track_links: null argument");
     *n_links = 0;
     if (n_frames == 0) return AXT_OK;
-    AXT_REQUIRE(d_track && d_count && d_links && d_work, "null argument");
     hipStream_t st = (hipStream_t)stream;
     const long slots = (long)n_frames * cap;
     int *head = d_work, *gap = d_work + slots, *frame_cnt = d_work + 2 * slots, *frame_off = frame_cnt + n_frames;
@@ -485,9 +488,12 @@ extern "C" int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const in
                               int n_links, const int32_t *d_head_group, int group, int H, int W, int max_dist, int conn8,
                               int32_t *d_len, int32_t *d_stage, void *stream)
 {
-    AXT_REQUIRE(n_links >= 0 && cap >= 1 && H > 0 && W > 0 && max_dist > 1 && max_dist < 32768, "bad argument");
+    AXT_REQUIRE(n_links >= 0 && cap >= 1, "axt_link_paths: n_links %d negative or cap %d below 1", n_links, cap);
+    AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL, "axt_link_paths: bad grid size %d x %d", H, W);
+    AXT_REQUIRE(max_dist > 1 && max_dist < 32768, "axt_link_paths: max_dist %d out of range (2..32767)", max_dist);
+    AXT_REQUIRE(!grid || (grid->H == H && grid->W == W), "axt_link_paths: the grid is not %d x %d", H, W);
     if (n_links == 0) return AXT_OK;
-    AXT_REQUIRE(d_x && d_y && d_links && d_len && d_stage, "null argument");
+    AXT_REQUIRE(d_x && d_y && d_links && d_len && d_stage, "axt_link_paths: null argument");
     hipStream_t st = (hipStream_t)stream;
     const int nb = (n_links + 255) / 256;
     if (!grid) {
@@ -572,7 +578,12 @@ extern "C" int axt_link_cells(const int32_t *d_links, int n_links, const int32_t
                               int max_dist, int max_gap, int64_t *d_cell_ptr, int32_t *d_cells, int32_t *d_interp,
                               int64_t *n_cells, void *stream)
 {
-    AXT_REQUIRE(n_links >= 0 && max_dist > 1 && max_gap >= 1 && d_cell_ptr && n_cells, "bad argument");
+    AXT_REQUIRE(d_cell_ptr && n_cells, "axt_link_cells: null argument");
+    AXT_REQUIRE(n_links >= 0, "axt_link_cells: n_links %d is negative", n_links);
+    AXT_REQUIRE(max_dist > 1 && max_dist < 32768, "axt_link_cells: max_dist %d out of range (2..32767)", max_dist);
+    AXT_REQUIRE(max_gap >= 1 && max_gap <= 255, "axt_link_cells: max_gap %d out of range (1..255)", max_gap);
+    AXT_REQUIRE(n_links == 0 || d_len, "axt_link_cells: null argument");
+    AXT_REQUIRE(!d_cells || n_links == 0 || (d_links && d_stage && (max_gap == 1 || d_interp)), "axt_link_cells: null argument");
     hipStream_t st = (hipStream_t)stream;
     if (!d_cells) {
         hipLaunchKernelGGL((axt_scan_kernel<long long, ClampedCount>), dim3(1), dim3(1024), 0, st, d_len, (long)n_links,

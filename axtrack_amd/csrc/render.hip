@@ -272,11 +272,15 @@ extern "C" int axt_render_frames(const float *d_frames, const uint8_t *d_mask, i
 {
     AXT_REQUIRE(d_frames && d_ts && d_trail_ptr && d_trail_col && d_prim_ptr && d_tables && d_out,
                 "axt_render_frames: null pointer");
-    AXT_REQUIRE(H > 0 && W > 0 && Ho > 0 && Wo > 0 && ymin >= 0 && xmin >= 0 && ymin + Ho <= H && xmin + Wo <= W,
-                "axt_render_frames: slice [%d, %d) x [%d, %d) outside the %d x %d frame", ymin, ymin + Ho, xmin, xmin + Wo,
-                H, W);
+    AXT_REQUIRE(H > 0 && W > 0 && Ho > 0 && Wo > 0 && ymin >= 0 && xmin >= 0 && Ho <= H && Wo <= W && ymin <= H - Ho && xmin <= W - Wo,
+                "axt_render_frames: slice of %d x %d from (%d, %d) outside the %d x %d frame", Ho, Wo, ymin, xmin, H, W);
+    AXT_REQUIRE((long)H * W <= 0x7fffffffL, "axt_render_frames: a frame of %d x %d pixels exceeds 2^31 - 1", H, W);
     AXT_REQUIRE(grid >= 0 && mask_stride >= 0, "axt_render_frames: grid and mask_stride must be >= 0");
-    if (n_out <= 0) return AXT_OK;
+    AXT_REQUIRE(n_out >= 0, "axt_render_frames: n_out %d is negative", n_out);
+    // prim_ptr is indexed by output frame x tile in int, and one launch takes every (run of frames, tile) as a workgroup
+    AXT_REQUIRE((long)n_out * axt_cdiv(Wo, RT) * axt_cdiv(Ho, RT) < 0x7fffffffL,
+                "axt_render_frames: %d output frames x %d tiles exceed 2^31 - 2", n_out, axt_cdiv(Wo, RT) * axt_cdiv(Ho, RT));
+    if (n_out == 0) return AXT_OK;
     RenderArgs a;
     a.frames = d_frames; a.mask = d_mask; a.mask_stride = mask_stride; a.ts = d_ts;
     a.n_out = n_out; a.H = H; a.W = W; a.ymin = ymin; a.xmin = xmin; a.Ho = Ho; a.Wo = Wo;

@@ -342,7 +342,8 @@ extern "C" int axt_segment_edges(const uint16_t *d_img, int H, int W, double sig
     // scipy.ndimage._filters._gaussian_kernel1d: exp(-x^2 / 2 sigma^2), normalised, in f64; then rounded to f32
     GaussTaps taps;
     double w[2 * MAX_RADIUS + 1], sum = 0.0;
-    for (int k = 0; k <= 2 * R; ++k) { const double x = k - R; w[k] = exp(-0.5 / (sigma * sigma) * x * x); sum += w[k]; }
+    // (the centre tap is 1 by definition: for a sigma whose square underflows, -0.5 / 0 * 0 would be NaN)
+    for (int k = 0; k <= 2 * R; ++k) { const double x = k - R; w[k] = k == R ? 1.0 : exp(-0.5 / (sigma * sigma) * x * x); sum += w[k]; }
     for (int k = 0; k <= 2 * MAX_RADIUS; ++k) taps.w[k] = k <= 2 * R ? (float)(w[k] / sum) : 0.0f;
     const size_t lds = sizeof(float) * ((size_t)(ETY + 2 * R) * (ETX + 2 * R) + (size_t)(ETY + 2 * R) * ETX) +
                        sizeof(unsigned short) * (size_t)(ETY + 2 * R + 2) * (ETX + 2 * R + 2);      // <= 53.9 KB

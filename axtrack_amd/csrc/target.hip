@@ -279,7 +279,8 @@ extern "C" int axt_target_sample(const int32_t *d_off, const int32_t *d_moves, i
                                  int32_t *d_det_off, int32_t *d_det_moves, void *stream)
 {
     AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL && n_fields >= 1 && n_frames >= 0 && cap >= 1,
-                "axt_target_sample: bad argument");
+                "axt_target_sample: bad argument (grid %d x %d, %d fields, %d frames, cap %d)", H, W, n_fields, n_frames, cap);
+    AXT_REQUIRE((long)n_frames * cap <= 0x7fffffffL, "axt_target_sample: n_frames %d x cap %d exceeds 2^31 - 1 slots", n_frames, cap);
     if (n_frames == 0) return AXT_OK;
     AXT_REQUIRE(d_off && d_moves && d_x && d_y && d_count && d_det_off && d_det_moves, "axt_target_sample: null argument");
     AXT_REQUIRE(n_fields == 1 || d_field_index, "axt_target_sample: %d fields need a field index per frame", n_fields);
@@ -295,7 +296,9 @@ extern "C" int axt_target_paths(const axt_grid *grid, const int32_t *d_off, cons
                                 const int32_t *d_field_index, int group, int64_t *d_cell_ptr, int32_t *d_cells,
                                 int64_t *n_cells, void *stream)
 {
-    AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL && n_frames >= 0 && cap >= 1, "axt_target_paths: bad argument");
+    AXT_REQUIRE(H > 0 && W > 0 && (long)H * W <= 0x7fffffffL && n_frames >= 0 && cap >= 1,
+                "axt_target_paths: bad argument (grid %d x %d, %d frames, cap %d)", H, W, n_frames, cap);
+    AXT_REQUIRE((long)n_frames * cap <= 0x7fffffffL, "axt_target_paths: n_frames %d x cap %d exceeds 2^31 - 1 slots", n_frames, cap);
     AXT_REQUIRE(d_cell_ptr && n_cells, "axt_target_paths: null argument");
     AXT_REQUIRE(n_frames == 0 || d_det_moves, "axt_target_paths: null argument");
     hipStream_t st = (hipStream_t)stream;

@@ -859,7 +859,7 @@ int axt_tile_stacks(const float *d_frames, int T_all, int H, int W, int t0, int 
     tl.n = n_tiles;
     for (int k = 0; k < n_tiles; ++k) {
         const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty * kStackT < H && tx * kStackT < W, "%s: tile %d (%d,%d) outside %dx%d", fn, k, ty,
+        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * kStackT < H && (long)tx * kStackT < W, "%s: tile %d (%d,%d) outside %dx%d", fn, k, ty,
                     tx, H, W);
         tl.yx[2 * k] = (short)ty;
         tl.yx[2 * k + 1] = (short)tx;

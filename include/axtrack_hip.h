@@ -14,6 +14,14 @@
  *     caller-provided buffers; calls are asynchronous on `stream` unless stated otherwise.
  *   - Detections of a frame are three parallel arrays (conf f32, x i32, y i32) of capacity
  *     `cap` per frame, sorted by descending confidence, plus a per-frame count.
+ *   - Arguments outside the bounds stated per function: AXT_EINVAL before any device call, with the function's name or
+ *     the offending value in axt_last_error(); output buffers and host outputs (*n_arcs, *n_cells, ...) stay as they
+ *     were. Shared bounds: a frame or grid of H x W cells has H, W >= 1 and H * W <= 2^31 - 1 (cells are numbered
+ *     y*W + x in i32); a floating-point argument must be finite unless its function says otherwise, and a NaN is
+ *     always refused. Flag arguments (conn8, bg, big_endian, label_quirk, log_correct, flip_y, flip_x, rotate, and `on` of
+ *     axt_conv_trainer_set_batch_stats) are read as zero / non-zero: any int is accepted. group (axt_link_paths,
+ *     axt_target_paths) is any int: a value that no frame carries selects nothing. tests/contract_cases.py holds every
+ *     bound as a table; the two are kept in step by the tests.
  */
 #ifndef AXTRACK_HIP_H
 #define AXTRACK_HIP_H
@@ -56,7 +64,7 @@ typedef struct axt_detector axt_detector;
  *   then fcs.1.weight[1024,40960], fcs.1.bias, fcs.3.weight[1024,1024], fcs.3.bias,
  *        fcs.5.weight[432,1024], fcs.5.bias
  * BatchNorm (eps 1e-5) is folded into the convolution in f64 and rounded once to f32.
- * max_batch = largest number of tile-forwards one call will be asked for (sizes the workspace).
+ * max_batch = largest number of tile-forwards one call will be asked for (sizes the workspace), 1 <= max_batch <= 65535.
  * Synchronous (returns after the upload has completed). */
 int axt_detector_create(const float *const *h_tensors, int n_tensors, int max_batch,
                         axt_detector **out);
@@ -86,7 +94,7 @@ size_t axt_detector_device_bytes(const axt_detector *det);
 
 /* detect_axons (model.py:119-125; call site AxonDetections.py:118):
  * d_x f32 [B,5,512,512] NCHW -> d_yolo f32 [B,12,12,3] (dim1 = x cell, dim2 = y cell,
- * last = conf, x_in_cell, y_in_cell). B <= max_batch. */
+ * last = conf, x_in_cell, y_in_cell). 0 <= B <= max_batch. */
 int axt_cnn_forward(axt_detector *det, const float *d_x, int B, float *d_yolo, void *stream);
 
 /* The same forward pass fed straight from the timelapse, fusing
@@ -94,7 +102,8 @@ int axt_cnn_forward(axt_detector *det, const float *d_x, int B, float *d_yolo, v
  * d_frames f32 [T_all,H,W] is channel 0 of the context-padded sequence; detection frame t of
  * tile k reads frames t..t+4 at tile origin (tile_yx[2k]*512, tile_yx[2k+1]*512), zero beyond
  * H/W (ZeroPad2d at Timelapse.py:529-533). Output d_yolo f32 [n_frames, n_tiles, 12,12,3] for
- * detection frames t0 .. t0+n_frames-1. n_frames*n_tiles may exceed max_batch (chunked). */
+ * detection frames t0 .. t0+n_frames-1. n_frames*n_tiles may exceed max_batch (chunked). t0 >= 0, n_frames >= 0 and
+ * t0 + n_frames + 4 <= T_all; 1 <= n_tiles <= 256, every tile's origin inside the frame (row * 512 < H, col * 512 < W). */
 int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W,
                            int t0, int n_frames, const int32_t *h_tile_yx, int n_tiles,
                            float *d_yolo, void *stream);
@@ -121,7 +130,7 @@ int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int 
  * features in the detector's batch buffer from item `item0` on; after the last chunk axt_cnn_back runs the remaining conv
  * blocks and the three linear layers ONCE for items 0 .. n_items-1 (the first linear layer streams its 168 MB of weights per
  * call, whatever the batch) and writes d_yolo [n_items,12,12,3]. item0 + items <= max_batch. Same results, bit for bit, as
- * axt_cnn_forward_frames over the same items. Asynchronous. */
+ * axt_cnn_forward_frames over the same items. item0 >= 0, 0 <= n_items <= max_batch. Asynchronous. */
 int axt_cnn_front_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                          const int32_t *h_tile_yx, int n_tiles, int item0, void *stream);
 int axt_cnn_back(axt_detector *det, int n_items, float *d_yolo, void *stream);
@@ -135,10 +144,13 @@ double axt_cnn_flops_per_tile(void);
  * pass slows it by ~8 %, bracketing the dominant kernel alone by < 1 %); on = 0, none. Kernel ids: 0..7 the eight conv
  * blocks, 8/10/12 the linear-layer GEMMs, 9/11/13 their split-K reductions.
  * axt_detector_read_profile synchronises on the recorded events and returns, per kernel id, the
- * summed milliseconds, the number of launches and the number of tile-forwards since the last read. */
+ * summed milliseconds, the number of launches and the number of tile-forwards since the last read (ms, launches, items:
+ * host arrays of n >= AXT_N_CNN_KERNELS entries). on is not range-checked: a negative value acts as 1, a value above 15
+ * brackets no kernel. */
 #define AXT_N_CNN_KERNELS 14
 int axt_detector_set_profiling(axt_detector *det, int on);
 int axt_detector_read_profile(axt_detector *det, double *ms, int64_t *launches, int64_t *items, int n);
+/* A kernel id outside 0..13 gives 0: there is no error to report. */
 double axt_cnn_kernel_flops_per_tile(int kernel);
 
 /* ------------------------------------------------------------------------------------------
@@ -146,7 +158,8 @@ double axt_cnn_kernel_flops_per_tile(int kernel);
  * Timelapse._read_tiff, _clip_image_values, _log_adjust_image, _standardize
  * (Timelapse.py:205-326) as one fused pass: x = u16/65535 -> mask -> max(x-offset,0) ->
  * (x<clip_lower ? 0 : x) -> log2(1+x) -> x/scale. d_raw u16 [T,H,W]; d_mask u8 [H,W] or NULL;
- * offset / clip_lower in [0,1] units (0 = skip); d_out f32 [T,H,W].
+ * offset / clip_lower in [0,1] units (0 = skip), finite; log_correct: zero / non-zero; scale > 0 (+inf allowed: every
+ * pixel becomes 0); d_out f32 [T,H,W]. T, H, W >= 1.
  * ------------------------------------------------------------------------------------------ */
 int axt_preprocess_u16(const uint16_t *d_raw, const uint8_t *d_mask, int T, int H, int W, float offset,
                        float clip_lower, int log_correct, float scale, float *d_out, void *stream);
@@ -156,7 +169,9 @@ int axt_preprocess_u16(const uint16_t *d_raw, const uint8_t *d_mask, int T, int 
  * n = how many values are != 0, sum and sumsq of the values (each f32 widened to f64 first), max of the values (0 for an
  * empty frame). Deterministic: per-block partials go to d_scratch and a second launch adds them in a fixed order; no
  * atomics, two calls give identical bits. *scratch_bytes: in, the size of d_scratch; out, the size needed. With
- * d_scratch == NULL the call only answers that size (d_raw, d_stats may be NULL then). d_stats [T] on the device. */
+ * d_scratch == NULL the call only answers that size (d_raw, d_stats may be NULL then). d_stats [T] on the device.
+ * *scratch_bytes is written whenever T, H, W, offset and clip_lower are valid, also by a call that is then refused
+ * because the scratch is too small: that is how the caller learns the size. */
 typedef struct {
     int64_t n;
     double sum, sumsq;
@@ -175,6 +190,7 @@ int axt_preprocess_u16_framewise(const uint16_t *d_raw, const uint8_t *d_mask, i
 /* ------------------------------------------------------------------------------------------
  * Tiling: which 512x512 tiles the reference keeps (Timelapse.py:551-558): a tile is kept if
  * any pixel of it is > 0 at any t. d_occ u8 [ceil(H/512)*ceil(W/512)] row-major, 1 = keep.
+ * 1 <= T_all <= 65539 (the frames after the fourth are one launch's second grid dimension).
  * ------------------------------------------------------------------------------------------ */
 int axt_tile_occupancy(const float *d_frames, int T_all, int H, int W, uint8_t *d_occ, void *stream);
 
@@ -188,6 +204,10 @@ int axt_tile_occupancy(const float *d_frames, int T_all, int H, int W, uint8_t *
  * in descending confidence (ties: tile order, then cell order), d_count i32 [n_frames].
  * n_tiles <= 256; frames of up to 28 kept tiles keep their candidates in LDS, larger ones in a workspace in HBM
  * (allocated on the stream for the call): same order, same result.
+ * Bounds: 1 <= n_tiles <= 256; tile indices 0 .. 32767 (the kernels keep them as short), otherwise free: any rows and
+ * columns in any order; cap >= n_tiles * 144 and n_frames * cap <= 2^31 - 1; 0 <= min_dist <= 32767; conf_thr any number,
+ * +-inf included, NaN: AXT_EINVAL. n_frames == 0: AXT_OK, nothing is touched; negative: AXT_EINVAL. The NMS distance is exact
+ * for any two stitched coordinates (differences in 64 bits).
  * ------------------------------------------------------------------------------------------ */
 int axt_decode_stitch_nms(const float *d_yolo, int n_frames, int n_tiles, const int32_t *h_tile_yx,
                           float conf_thr, int min_dist, int cap,
@@ -198,7 +218,8 @@ int axt_decode_stitch_nms(const float *d_yolo, int n_frames, int n_tiles, const 
  * ------------------------------------------------------------------------------------------ */
 /* observation_model (mincostflow_models.py:6-27) after the confidence capping of
  * AxonDetections.py:655-659. method 0 = 'scale_to_max' (conf / max over all frames),
- * 1 = 'ceil' (min(conf,1)). d_cost f64 [n_frames,cap] (entries >= count are untouched). */
+ * 1 = 'ceil' (min(conf,1)). d_cost f64 [n_frames,cap] (entries >= count are untouched). cap >= 1, max_conf_cost finite.
+ * n_frames == 0: AXT_OK, nothing is touched; negative: AXT_EINVAL. */
 int axt_obs_costs(const float *d_conf, const int32_t *d_count, int n_frames, int cap,
                   int method, double max_conf_cost, double *d_cost, void *stream);
 
@@ -215,8 +236,9 @@ void axt_grid_destroy(axt_grid *grid);
  * (rows) to detection j of the later frame on weights {1 on mask, 65536 off}; max_dist where
  * the euclidean distance is >= max_dist, an end point is outside the grid, or the path has
  * more than max_dist cells. grid = NULL for an all-ones mask (closed form); with a grid its
- * connectivity must equal conn8 (exact single-source search per detection of the earlier frame).
- * D i32 [na, nb] row-major. */
+ * connectivity must equal conn8 (exact single-source search per detection of the earlier frame) and its size H x W.
+ * D i32 [na, nb] row-major. na, nb >= 0 (either 0: AXT_OK, nothing is touched) and na * nb <= 2^31 - 1;
+ * 1 <= max_dist <= 32767. */
 int axt_path_cost(const int32_t *d_xa, const int32_t *d_ya, int na,
                   const int32_t *d_xb, const int32_t *d_yb, int nb,
                   const axt_grid *grid, int H, int W, int max_dist, int conn8,
@@ -226,7 +248,7 @@ int axt_path_cost(const int32_t *d_xa, const int32_t *d_ya, int na,
  * _compute_detections_astar_paths, AxonDetections.py:570-577, for the cache file and for drawing): D as above, and
  * d_cells i32 [na, nb, max_dist] receives, for every pair with D < max_dist, the D cells of one minimum-cost path
  * as y*W + x, source first; other entries are left untouched. Needs a grid (all-ones masks have closed-form
- * staircases); which of several equally cheap paths pyastar2d would return is not pinned. */
+ * staircases); which of several equally cheap paths pyastar2d would return is not pinned. Bounds as axt_path_cost. */
 int axt_path_cells(const int32_t *d_xa, const int32_t *d_ya, int na,
                    const int32_t *d_xb, const int32_t *d_yb, int nb,
                    const axt_grid *grid, int H, int W, int max_dist, int conn8,
@@ -266,7 +288,13 @@ int axt_path_cells(const int32_t *d_xa, const int32_t *d_ya, int na,
  *   d_hist, d_hist_sum (axt_box_histograms below) with vis_weight in (0,1], miss_rate, edge_cost_thr -- d_hist NULL: costs
  *     from d_cost_units, the three numbers are not read. Otherwise the appearance term: the cost is computed per pair,
  *     d_cost_units is ignored and d_cost may be NULL. With d_len_table this is the combination the reference's parameter
- *     search runs (assign_ids(astar_paths_cache='from') with MCF_VIS_SIM_WEIGHT > 0, AxonDetections.py:882,911-912). */
+ *     search runs (assign_ids(astar_paths_cache='from') with MCF_VIS_SIM_WEIGHT > 0, AxonDetections.py:882,911-912).
+ *     miss_rate finite and >= 0; edge_cost_thr any number, +-inf included, NaN: AXT_EINVAL.
+ * Bounds: n_frames >= 1, cap >= 1, 1 <= max_gap <= 8, n_frames * cap * max_gap <= 2^31 - 1 (computed in size_t);
+ * 1 <= max_dist <= 32767; H, W as everywhere (not read with d_len_table), a grid must be H x W; 0 <= h_dmax[g] <= 32767.
+ * Where the path lengths come from a table (d_len_table, or a grid) and d_cost_units prices them, additionally
+ * h_dmax[g] <= max_dist: a length can reach h_dmax[g] and indexes the units table, which has max_dist + 1 entries per gap.
+ * The closed form never exceeds max_dist and accepts any h_dmax[g] in range. A refused call leaves *n_arcs as it was. */
 int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, const int32_t *d_src_count,
                    int n_frames, int cap, const axt_grid *grid, int H, int W, int max_dist, int conn8,
                    int max_gap, const int32_t *h_dmax,
@@ -284,6 +312,8 @@ int axt_build_arcs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_coun
  * of detection frame f, which is what the tracker is shown (AxonDetections.py:682-685) -- min-max
  * normalised. The crop starts at (max(y - box/2, 0), max(x - box/2, 0)) and is clipped at the far edges.
  * d_hist f32 [n_frames, cap, 180], d_hist_sum f64 [n_frames, cap] (bin sums, used by the distance).
+ * Bounds: T_all >= 1, t_offset >= 0 and t_offset + n_frames <= T_all; 1 <= n_frames <= 65535 (the launch's second grid
+ * dimension), cap >= 1, 1 <= box <= 32768.
  *
  * axt_build_arcs with d_hist = these histograms computes the cost of transition_model (:100-118) per pair:
  *   cost = -log((1-w) * (1 - D/max_dist) * miss_rate^(gap-1) + w * (1 - d_B(hist_a, hist_b)) + 1e-6)
@@ -308,7 +338,8 @@ int axt_box_histograms(const float *d_frames, int T_all, int H, int W, int t_off
  *          h_track i32 [n_det]: trajectory id (numbered by first detection) or -1;
  *          *n_tracks, *total_cost.
  * Returns AXT_INFEASIBLE if fewer than min_flow trajectories can be routed (the reference's
- * falsy compute_trajectories(), AxonDetections.py:691-696).
+ * falsy compute_trajectories(), AxonDetections.py:691-696). n_det >= 0, 0 <= min_flow <= max_flow; every arc must point
+ * forward (k < h_col[e] < n_det), else AXT_EINVAL.
  * ------------------------------------------------------------------------------------------ */
 int axt_mcf_solve(int n_det, const int64_t *h_obs, const int64_t *h_entry, const int64_t *h_exit,
                   const int64_t *h_row_ptr, const int32_t *h_col, const int64_t *h_cost,
@@ -365,6 +396,12 @@ void axt_mcf_shard_free(axt_mcf_shard *shard);
  * [2, n_frames*cap], predecessor index in frame t-1 / t-2 or -1; entries of other frames stay -1). A frame-sharded rank
  * passes its own range, and the ranks combine d_pred with one element-wise MAX all-reduce. max_gap is 1 or 2, cap at most
  * 2048; d_cost_units i64 [max_gap, max_dist+1]; d_work i32 [2*n_frames*cap + n_frames + 1] scratch.
+ * Bounds: n_frames >= 1, n_frames * cap <= 2^30 - 1, 0 <= t_begin <= t_end <= n_frames, 0 <= thr_units <= 2^46 (a dummy
+ * cost is thr_units << 16 | hash in i64). Without d_ctab: H, W as everywhere, a grid must be H x W,
+ * 1 <= max_dist <= 32767, 0 <= h_dmax[g] <= 32767, and with a grid h_dmax[g] <= max_dist (the kernels stage the
+ * max_dist + 1 units of a gap in LDS and a searched length can reach h_dmax[g]; the closed form never exceeds max_dist and
+ * accepts any h_dmax[g] in range). The LDS bounds cap and max_dist together: 66 cap + 48 cap (cap <= 576) + 8 max_dist + 32
+ * <= 163840 bytes.
  * Optional inputs, each a nullable pointer:
  *   grid -- NULL: all-ones mask, closed-form path lengths. Otherwise the path lengths of the pairs come from the
  *     masked-grid searches of the arc builder (_compute_detections_astar_paths on weights {1 on mask, 65536 off},
@@ -378,6 +415,7 @@ void axt_mcf_shard_free(axt_mcf_shard *shard);
  *
  * axt_chain_tracks numbers the chains of d_pred (after the all-reduce in sharded runs): d_track i32 [n_frames, cap] =
  * trajectory id of every detection slot (-1 beyond count), d_n_tracks i32 [1]; d_work i32 [2*n_frames*cap] scratch.
+ * n_frames >= 1, cap >= 1, n_frames * cap <= 2^30 - 1.
  * ------------------------------------------------------------------------------------------ */
 int axt_hungarian_pairs(const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
                         const axt_grid *grid, int H, int W, int max_dist, int conn8, int max_gap,
@@ -395,6 +433,8 @@ int axt_chain_tracks(const int32_t *d_count, int n_frames, int cap, const int32_
  * concat drops the others, :831, and labels the rest by position).
  * d_track i32 [n_frames, cap] (-1 = no identity), d_id_row: NULL (row = id, n_rows == n_ids) or
  * i32 [n_ids] id -> row (-1 = drop); d_work i32 [n_frames] scratch. Asynchronous.
+ * n_frames >= 1, cap >= 1, n_ids >= 0, n_rows >= 0 (n_rows == 0: AXT_OK, nothing is touched);
+ * n_frames * cap <= 2^31 - 1 and n_rows * n_frames <= 2^31 - 1.
  * ------------------------------------------------------------------------------------------ */
 int axt_ided_table(const int32_t *d_track, const float *d_conf, const int32_t *d_x, const int32_t *d_y,
                    const int32_t *d_count, int n_frames, int cap, int n_ids, const int32_t *d_id_row, int n_rows,
@@ -407,7 +447,9 @@ int axt_ided_table(const int32_t *d_track, const float *d_conf, const int32_t *d
 /* The links of the tracks: for every detection slot (f, i) of d_track i32 [n_frames, cap] (-1 = none) with id k, the
  * first detection of k in frames f+1 .. f+max_gap (max_gap = MCF_MAX_NUM_MISSES + 1). d_links i32 [n_frames*cap, 3]
  * receives (tail slot f*cap+i, head slot, gap) of each link in ascending tail order (deterministic);
- * d_work i32 [2*n_frames*cap + 2*n_frames + 1]; *n_links = number of links. Synchronises the stream. */
+ * d_work i32 [2*n_frames*cap + 2*n_frames + 1]; *n_links = number of links. Synchronises the stream.
+ * n_frames >= 0 (n_frames == 0: AXT_OK and *n_links = 0), cap >= 1, n_frames * cap <= 2^30 - 1, 1 <= max_gap <= 255. A
+ * refused call leaves *n_links as it was. */
 int axt_track_links(const int32_t *d_track, const int32_t *d_count, int n_frames, int cap, int max_gap,
                     int32_t *d_links, int32_t *d_work, int64_t *n_links, void *stream);
 
@@ -418,7 +460,8 @@ int axt_track_links(const int32_t *d_track, const int32_t *d_count, int n_frames
  * search for what they cannot decide). Only the links whose HEAD frame f has d_head_group[f] == group (all links for
  * d_head_group == NULL): one call per distinct mask of a time-varying mask. d_len i32 [n_links] (zeroed before the first
  * call) receives the number of cells, max_dist = no path; d_stage i32 [n_links, max_dist] the cells y*W + x, source
- * first. Reads back one count (links for the exact search) when grid != NULL. */
+ * first. Reads back one count (links for the exact search) when grid != NULL. n_links >= 0 (0: AXT_OK, nothing is
+ * touched), cap >= 1, 2 <= max_dist <= 32767, a grid must be H x W. */
 int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const int32_t *d_y, int cap, const int32_t *d_links,
                    int n_links, const int32_t *d_head_group, int group, int H, int W, int max_dist, int conn8,
                    int32_t *d_len, int32_t *d_stage, void *stream);
@@ -426,7 +469,8 @@ int axt_link_paths(const axt_grid *grid, const int32_t *d_x, const int32_t *d_y,
 /* The paths of axt_link_paths as CSR. Phase 1 (d_cells == NULL): d_cell_ptr i64 [n_links+1] = prefix sum of the lengths
  * (0 for no path), *n_cells = total (synchronises). Phase 2: d_cells i32 [n_cells] filled from d_stage, and
  * d_interp i32 [n_links, max_gap-1]: for a link of gap g >= 2 with a path of L cells, entry k-1 (k = 1 .. g-1) = the
- * cell at index (2k(L-1) + g) / (2g) of the path (the interpolated anchor of frame tail+k), -1 otherwise. */
+ * cell at index (2k(L-1) + g) / (2g) of the path (the interpolated anchor of frame tail+k), -1 otherwise.
+ * n_links >= 0, 2 <= max_dist <= 32767, 1 <= max_gap <= 255. A refused call leaves *n_cells as it was. */
 int axt_link_cells(const int32_t *d_links, int n_links, const int32_t *d_len, const int32_t *d_stage, int max_dist,
                    int max_gap, int64_t *d_cell_ptr, int32_t *d_cells, int32_t *d_interp, int64_t *n_cells, void *stream);
 
@@ -452,7 +496,8 @@ int axt_target_field(const axt_grid *grid, int H, int W, int conn8, const int32_
 /* The field at every detection slot: d_det_off / d_det_moves i32 [n_frames, cap] = (off, moves) at (d_y, d_x) of the
  * slot, -1 for slots >= d_count[f] and for detections outside the grid (the decode does not clamp). d_off / d_moves i32
  * [n_fields, H, W]; d_field_index i32 [n_frames] = the field of frame f (one per distinct mask of a time-varying mask;
- * NULL with n_fields == 1; an index outside [0, n_fields) gives -1). Asynchronous. */
+ * NULL with n_fields == 1; an index outside [0, n_fields) gives -1). Asynchronous. n_fields >= 1, cap >= 1,
+ * n_frames >= 0 (n_frames == 0: AXT_OK, nothing is touched), n_frames * cap <= 2^31 - 1. */
 int axt_target_sample(const int32_t *d_off, const int32_t *d_moves, int n_fields, const int32_t *d_field_index, int H,
                       int W, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count, int n_frames, int cap,
                       int32_t *d_det_off, int32_t *d_det_moves, void *stream);
@@ -463,7 +508,8 @@ int axt_target_sample(const int32_t *d_off, const int32_t *d_moves, int n_fields
  * Phase 1 (d_cells == NULL): d_cell_ptr i64 [n_frames*cap + 1] = prefix sum of d_det_moves + 1 (0 where it is -1),
  * *n_cells = total (synchronises). Phase 2: d_cells i32 [*n_cells] receives y*W + x, detection first, for the slots
  * whose frame f has d_field_index[f] == group (all slots for d_field_index == NULL) from the ONE field d_off / d_moves
- * i32 [H, W] and its grid (NULL = all ones): one call per distinct mask. One thread per detection. Asynchronous. */
+ * i32 [H, W] and its grid (NULL = all ones): one call per distinct mask. One thread per detection. Asynchronous.
+ * n_frames >= 0, cap >= 1, n_frames * cap <= 2^31 - 1. A refused call leaves *n_cells as it was. */
 int axt_target_paths(const axt_grid *grid, const int32_t *d_off, const int32_t *d_moves, int H, int W, int conn8,
                      const int32_t *d_x, const int32_t *d_y, int n_frames, int cap, const int32_t *d_det_moves,
                      const int32_t *d_field_index, int group, int64_t *d_cell_ptr, int32_t *d_cells, int64_t *n_cells,
@@ -520,7 +566,8 @@ int axt_segment_flood(const uint8_t *d_img, int H, int W, int seed_y, int seed_x
  * TP, FP, FN. Labels are matched in order; a label whose closest candidate is already claimed is a
  * false negative; an empty side is replaced by one phantom row at the origin with conf 0 (:434-437).
  * k_mask >= 0: additionally d_fp_mask u8 [n_frames, cap] / d_fn_mask u8 [n_frames, gcap] for that
- * threshold index (either may be NULL). Asynchronous.
+ * threshold index (either may be NULL); any k_mask < 0 means no masks, k_mask >= n_thr: AXT_EINVAL. Asynchronous.
+ * n_frames >= 1, 1 <= cap <= 2048, gcap >= 1, 1 <= n_thr <= 65535 (the launch's second grid dimension), 0 <= min_dist <= 1024.
  * ------------------------------------------------------------------------------------------ */
 int axt_detection_confusion(const float *d_conf, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
                             int n_frames, int cap, const int32_t *d_gx, const int32_t *d_gy, const int32_t *d_gcount,
@@ -534,13 +581,15 @@ int axt_detection_confusion(const float *d_conf, const int32_t *d_x, const int32
  * detections; labels d_gid (dense identities in [0, no)), d_gx, d_gy i32 [n_frames, gcap], d_gcount i32 [n_frames].
  * Identities are unique within a frame on both sides; identities out of range take no part. The counts are clamped:
  * a frame uses max(min(d_count[f], cap), 0) detection slots and max(min(d_gcount[f], gcap), 0) label slots. A pair is admissible
- * when dx^2 + dy^2 <= max_dist^2. Limits: cap, gcap <= 1024, max_dist <= 255, no, nh <= 2^24 (AXT_EINVAL beyond).
+ * when dx^2 + dy^2 <= max_dist^2. Limits: cap, gcap <= 1024, max_dist <= 255, no, nh <= 2^24 (AXT_EINVAL beyond);
+ * 1 <= n_assoc <= 65535, n_frames >= 1, all of cap, gcap, no, nh >= 1, max_dist >= 0.
  * Outputs: d_counts i64 [n_assoc, 10] = n_match, n_switch, n_miss, n_fp, sum of matched d2, n_obj, n_pred,
  * n_unique_objects, n_fragmentations, idtp; d_tallies i32 [n_assoc, no, 2] = frames present, frames not missed.
  * Event log (each pointer may be NULL): d_ev_kind u8 [n_assoc, n_frames, gcap] per label slot (0 none, 1 MATCH,
  * 2 SWITCH, 3 MISS), d_ev_partner i32, same shape (the partner's detection slot, -1 = none), d_ev_fp u8
  * [n_assoc, n_frames, cap] per detection slot. *scratch_bytes: in, the size of d_scratch; out, the size needed;
- * with d_scratch == NULL the call only answers that size (the other pointers may be NULL then). Integer work,
+ * with d_scratch == NULL the call only answers that size (the other pointers may be NULL then); it is written whenever the
+ * sizes are valid, also by a call that is then refused because the scratch is too small. Integer work,
  * two calls give identical bits. Asynchronous.
  * ------------------------------------------------------------------------------------------ */
 int axt_mot_scores(const int32_t *d_track, int n_assoc, const int32_t *d_x, const int32_t *d_y, const int32_t *d_count,
@@ -564,7 +613,9 @@ int axt_mot_scores(const int32_t *d_track, int n_assoc, const int32_t *d_x, cons
  * outline a x a, 1 solid ground-truth outline, 2 glyph a = char - 32 at scale b, 3 rectangle a x b, 4 rectangle a x b of the target layer that lies between the
  * grid and the trails: key 1 = a target path, (217, 217, 217), key 2 = target cells, white, over the paths) binned per
  * (output frame, tile): d_prim_ptr i32 [n_out*n_tiles+1]; key = layer << 24 | (n + 1), the largest key wins, layer 3
- * is grey (107). d_tables u8: palette [20, 3], then the glyph rows [95, 7]. Asynchronous. */
+ * is grey (107). d_tables u8: palette [20, 3], then the glyph rows [95, 7]. Asynchronous.
+ * Bounds: Ho, Wo >= 1, ymin, xmin >= 0, ymin + Ho <= H and xmin + Wo <= W (checked without overflow); grid >= 0,
+ * mask_stride >= 0; n_out * tiles < 2^31 - 1. n_out == 0: AXT_OK, nothing is touched; negative: AXT_EINVAL. */
 int axt_render_tile_size(void);
 int axt_render_frames(const float *d_frames, const uint8_t *d_mask, int64_t mask_stride, const int32_t *d_ts, int n_out,
                       int H, int W, int ymin, int xmin, int Ho, int Wo, int grid, int bg, const int32_t *d_trail_ptr,
@@ -581,6 +632,7 @@ int axt_render_frames(const float *d_frames, const uint8_t *d_mask, int64_t mask
  * label index), every other cell zero. A label belongs to tile (ty, tx) iff ty*512 <= y < (ty+1)*512 and likewise x;
  * labels of tiles that are not listed are dropped. Cell arithmetic in f32 as the reference's (bit-equal); of two labels
  * in a cell the one with the higher index wins all four channels (one thread per cell scans the labels: no race).
+ * F >= 0 (F == 0 writes nothing), cap >= 1, 1 <= n_tiles <= 256, tile indices 0 .. 32766, F * n_tiles * 144 < 2^39.
  *
  * axt_head_trainer: device-resident master weights ([out,in] row-major f32, state_dict layout), Adam moments m, v (f32,
  * zero), the step count and the activations of the last forward batch. NOUT = 432, max_batch <= 64.
@@ -596,6 +648,8 @@ int axt_render_frames(const float *d_frames, const uint8_t *d_mask, int64_t mask
  *   weight_decay w in ascending b without storing it and updates m, v, w in place as torch.optim.Adam does
  *   (t = the handle's step count after its increment). Biases likewise. No atomics: byte-identical from run to run.
  * _read_weights / _read_moments (layer 0..2; any pointer may be NULL): device -> host, synchronous.
+ * K0, H1, H2 >= 1; 1 <= B <= max_batch in every call that takes a batch. Adam: 0 <= beta1, beta2 < 1, eps >= 0,
+ * weight_decay >= 0, else AXT_EINVAL; lr and the three lambdas are taken as they are (any value, not checked).
  * ------------------------------------------------------------------------------------------ */
 int axt_yolo_targets(const int32_t *d_lx, const int32_t *d_ly, const int32_t *d_lcount, int F, int cap,
                      const int32_t *h_tile_yx, int n_tiles, float *d_target, void *stream);
@@ -695,7 +749,9 @@ int axt_conv_trainer_step(axt_conv_trainer *tr, const float *d_in, const int32_t
  *   dy, dx (any sign and size): subtracted; a source outside the frame gives 0.
  * d_occ (may be NULL) u8 [T, ceil(H/512) * ceil(W/512)]: zeroed by the call, then 1 where the OUTPUT frame has a pixel
  * > 0 in that tile (partial edge tiles count). No atomics: byte-identical from run to run. Asynchronous.
- * axt_augment_frame_chunk: the frames one workgroup loops over with the source indices it computed once. */
+ * axt_augment_frame_chunk: the frames one workgroup loops over with the source indices it computed once.
+ * 1 <= T <= 393210 and 1 <= H <= 262140 (one launch: 65535 grid rows of 4 image rows, 65535 chunks of 6 frames), W >= 1;
+ * m00 .. m11 finite when rotate != 0 (not read otherwise). */
 int axt_augment_frame_chunk(void);
 int axt_augment_frames(const float *d_in, int T, int H, int W, int dy, int dx, int flip_y, int flip_x, int rotate,
                        float m00, float m01, float m10, float m11, float *d_out, uint8_t *d_occ, void *stream);
@@ -703,7 +759,8 @@ int axt_augment_frames(const float *d_in, int T, int H, int W, int dy, int dx, i
 /* Integer arc cost used by the flow network (the costs libmot hands its solver at AxonDetections.py:663-690, from
  * observation_model / transition_model, mincostflow_models.py:6-27,67-119): round(cost * 1e6) << 16 | hash16(kind, a, b).
  * kind 0 entry, 1 exit, 2 observation, 3 transition. The low 16 bits make the optimum unique
- * (DESIGN.md "Unpinned third-party semantics"). */
+ * (DESIGN.md "Unpinned third-party semantics"). Pure arithmetic without an error return: any cost, kind, a and b give a value
+ * (a NaN or a cost beyond +-9.2e12 gives an unspecified one). */
 int64_t axt_arc_cost_int(double cost, int kind, int64_t a, int64_t b);
 
 #ifdef __cplusplus

@@ -26,7 +26,8 @@
  *   [B, 5, 512, 512]: channel c of item (f, k) is frames[t0 + f + c], rows from tile_yx[2k]*512, columns from
  *   tile_yx[2k+1]*512, +0.0 beyond H or W. One thread per float4 where W is a multiple of 4 and both pointers are 16-byte
  *   aligned, else per float. Asynchronous on `stream`, no copy, nothing allocated. d_frames, T_all, H, W, t0, n_frames,
- *   h_tile_yx, n_tiles as axt_cnn_features_frames takes them (n_frames >= 1), 1 <= B <= 1024, else AXT_EINVAL. The item
+ *   h_tile_yx, n_tiles as axt_cnn_features_frames takes them (1 <= n_frames <= 2^22, 1 <= H, W <= 32768, every tile's
+ *   origin inside the frame: the products with 512 are formed in 64 bits), 1 <= B <= 1024, else AXT_EINVAL. The item
  *   numbers are on the device, so the call cannot refuse one: an item outside [0, n_frames*n_tiles) gives a stack of +0.0
  *   and reads nothing.
  *

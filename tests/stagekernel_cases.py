@@ -234,6 +234,50 @@ def decode_cases():
     return [_decode_case(1), _decode_case(LDS_TILES), _decode_case(LDS_TILES + 1), _decode_zero_case()]
 
 
+# Tiles so far apart that the square of their distance does not fit 32 bits: 128 tiles = 65536 px, whose square is 2^32 (wraps
+# to 0); 91 tiles = 46592 px, whose square 2170814464 wraps to a negative number. Either way a 32-bit dx * dx + dy * dy lies
+# below 23^2 and the less confident twin dies. (Not part of decode_cases(): tests/test_contract_gpu.py runs them.)
+DISTANT_TILES = (128, 91)
+
+
+def distant_tiles_case(apart, along, n_tiles):
+    """Two kept tiles `apart` tile columns (along = 'cols') or rows ('rows') from each other, the other n_tiles - 2 tiles
+    empty; in both frames the two tiles hold the same cell with the same in-cell offsets at confidences 0.9 / 0.8 (twins:
+    both survive), and tile 0 a pair 21 x 9 px apart that must still lose its weaker member."""
+    far = (0, apart) if along == 'cols' else (apart, 0)
+    keep = [(0, 0), far] + [(1 + k // 16, 1 + k % 16) for k in range(n_tiles - 2)]
+    g = _Grid(2, keep)
+    for f in range(2):
+        cell = (5 + f) * S + 7
+        g.raw(f, 0, cell, 0.9, 0.25, 0.75, None)
+        g.raw(f, 1, cell, 0.8, 0.25, 0.75, None)
+        g.put(f, 0, 2 * S + 2, 0.95, 100, 100 + f)                      # the genuinely close pair: d^2 = 522 < 529
+        g.put(f, 0, 2 * S + 3, 0.60, 121, 109 + f)
+    return Case('decode', f'twins_{apart}_{along}_tiles{n_tiles}',
+                [f'twins {apart} tile {along} apart', 'close pair inside a tile', f'n_tiles == {n_tiles}'],
+                yolo=g.yolo, keep=keep, conf_thr=F32_FLOOR, min_dist=23, cap=n_tiles * CELLS, want=g.want)
+
+
+def distant_tiles_cases():
+    return [distant_tiles_case(apart, along, n) for apart in DISTANT_TILES for along in ('cols', 'rows') for n in (2, LDS_TILES + 1)]
+
+
+def decode_256_tiles_case():
+    """n_tiles == 256 with cap == 256 * 144 exactly: tile indices spread up to (15, 15), the last tile at the largest accepted
+    index (32767, 32767), about 300 cells above the threshold per frame (the rank is quadratic in those only)."""
+    rng = np.random.default_rng(256)
+    keep = [(r, c) for r in range(16) for c in range(16)][:255] + [(32767, 32767)]
+    yolo = np.zeros((2, 256, S, S, 3), np.float32)
+    for f in range(2):
+        for _ in range(300):
+            k, i, j = int(rng.integers(0, 256)), int(rng.integers(0, S)), int(rng.integers(0, S))
+            yolo[f, k, i, j] = (rng.uniform(0.56, 0.99), rng.uniform(0, 1), rng.uniform(0, 1))
+        yolo[f, 255, 11, 11] = (0.93, 0.5, 0.5)
+        yolo[f, 255, 11, 10] = (0.71, 0.5, 1.1)                          # 17 px above it: dies
+    return Case('decode', 'tiles256', ['n_tiles == 256', 'cap == n_tiles * 144', 'tile index 32767'], yolo=yolo, keep=keep,
+                conf_thr=F32_FLOOR, min_dist=23, cap=256 * CELLS, want={})
+
+
 def decode_reference(case):
     """Per frame (conf f32, x i64, y i64) from the oracle's decode_filter -> stitch -> nms."""
     return [orc.nms(*orc.stitch(orc.decode_filter(y, TILE, S, case.conf_thr), case.keep, TILE), case.min_dist) for y in case.yolo]

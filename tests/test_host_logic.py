@@ -34,35 +34,17 @@ def test_library_exports_every_declared_symbol():
 
 def test_association_entry_points_check_arguments_without_a_gpu():
     """axt_build_arcs and axt_hungarian_pairs refuse bad arguments before they touch the device (invalid calls only:
-    a valid one would reach a launch)."""
+    a valid one would reach a launch). The calls stand in tests/contract_cases.py (LEGACY) with the rest of the argument
+    contract; tests/test_contract_cpu.py makes them again in a process that cannot see a device."""
+    import contract_cases as cc
     lib = _lib.load()
-    EINVAL = -22
-    buf = np.zeros(64, np.int64)
-    p = buf.ctypes.data                                               # (never dereferenced: the checks come first)
-    n = ctypes.c_int64(0)
-
-    def arcs(d_x=p, max_gap=2, hist=None, hsum=None, weight=0.0, col=None, length=None, gap=None, units=None, cost=None):
-        return lib.axt_build_arcs(d_x, p, p, None, 4, 8, None, 64, 64, 500, 0, max_gap, p, hist, hsum, weight, 0.5, 4.6, p, p,
-                                  col, length, gap, units, cost, ctypes.byref(n), None, None)
-
-    assert arcs(d_x=None) == EINVAL
-    assert b'null argument' in lib.axt_last_error()
-    assert arcs(max_gap=9) == EINVAL
-    assert arcs(hist=p, hsum=None, weight=0.5) == EINVAL                                  # histograms without their sums
-    assert arcs(hist=p, hsum=p, weight=0.0) == EINVAL
-    assert arcs(hist=p, hsum=p, weight=1.5) == EINVAL
-    assert b'1.5' in lib.axt_last_error()
-    assert arcs(col=p, length=p, gap=p, cost=p, units=None) == EINVAL                     # phase 2: costs wanted, no units
-    assert b'go together' in lib.axt_last_error()
-
-    def pairs(cap=8, max_gap=2, a=0, b=4, units=p, ctab=None):
-        return lib.axt_hungarian_pairs(p, p, p, 4, cap, None, 64, 64, 500, 0, max_gap, p, units, 4600000, a, b, p, p, None, ctab)
-
-    assert pairs(cap=2049) == EINVAL
-    assert b'2049' in lib.axt_last_error()
-    assert pairs(max_gap=3) == EINVAL
-    assert pairs(a=3, b=2) == EINVAL
-    assert pairs(units=None, ctab=None) == EINVAL                                         # neither a cost table nor units
+    sentinel = cc.sentinel_buffer()
+    assert len(cc.LEGACY) == 10
+    for call, fragment in cc.LEGACY:
+        rc, message, touched = cc.run_refusal(lib, call, sentinel)
+        assert rc == -22, f'{call.id}: returned {rc}: {message}'
+        assert fragment is None or fragment in message.encode(), f'{call.id}: {message!r} lacks {fragment!r}'
+        assert not touched, f'{call.id}: a refused call wrote to a buffer'
 
 
 def test_product_has_no_oracle_import():

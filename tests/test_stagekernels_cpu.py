@@ -278,6 +278,49 @@ def test_ranking_ties_by_cell_only_changes_a_named_case(name):
     assert sorted(zip(bad[1].tolist(), bad[2].tolist())) != sorted(zip(ref[1].tolist(), ref[2].tolist())), case.route
 
 
+def _nms_in_32_bits(conf, x, y, min_dist):
+    """orc.nms with dx * dx + dy * dy formed in int32 (wrapping), as a kernel that does not widen forms it."""
+    order = np.argsort(-conf.astype(np.float64), kind='stable')
+    x, y = x[order].astype(np.int32), y[order].astype(np.int32)
+    alive = []
+    with np.errstate(over='ignore'):
+        for i in range(len(x)):
+            dx, dy = x[alive] - x[i], y[alive] - y[i]
+            if not ((dx * dx + dy * dy) < np.int32(min_dist * min_dist)).any():
+                alive.append(i)
+    return len(alive)
+
+
+@pytest.mark.parametrize('case', sc.distant_tiles_cases(), ids=repr)
+def test_distant_twins_separate_a_32_bit_nms_from_an_exact_one(case):
+    """The twins' 32-bit squared distance is below 23^2 while the exact one is not: the reference keeps both, a kernel that
+    forms the sum in int loses one per frame. The close pair inside tile 0 loses its weaker member either way."""
+    ref = sc.decode_reference(case)
+    assert len(case.yolo) == 2 and case.min_dist == 23
+    for f in range(2):
+        c, x, y, k, cell = sc.decode_candidates(case, f)
+        assert len(c) == 4
+        a, b = np.nonzero(c == np.float32(0.9))[0][0], np.nonzero(c == np.float32(0.8))[0][0]
+        assert k[a] == 0 and k[b] == 1 and cell[a] == cell[b]
+        dx, dy = int(x[b]) - int(x[a]), int(y[b]) - int(y[a])
+        exact = dx * dx + dy * dy
+        wrapped = ((exact + 2 ** 31) % 2 ** 32) - 2 ** 31                  # what int arithmetic keeps of it
+        assert sorted((abs(dx), abs(dy))) == [0, int(case.name.split('_')[1]) * sc.TILE], case.route
+        assert wrapped < 23 * 23 <= exact, f'{case.route}: 32-bit sum {wrapped}, exact {exact}'
+        assert len(ref[f][0]) == 3 and {0.9, 0.8, 0.95} == {round(float(v), 2) for v in ref[f][0]}, case.route
+        assert _nms_in_32_bits(c, x, y, case.min_dist) == 2, case.route
+
+
+def test_the_256_tile_case_is_what_it_says():
+    case = sc.decode_256_tiles_case()
+    assert len(case.keep) == len(set(case.keep)) == 256 and case.cap == 256 * sc.CELLS and max(max(t) for t in case.keep) == 32767
+    assert (15, 14) in case.keep
+    for f in range(2):
+        n = len(sc.decode_candidates(case, f)[0])
+        assert 250 <= n <= 310, n
+        assert len(sc.decode_reference(case)[f][0]) < n                      # something is suppressed
+
+
 # ------------------------------------------------------------------------------------------------- the other references
 def test_identity_reference_rows_are_the_kernels_rows():
     for c in family('ided'):
