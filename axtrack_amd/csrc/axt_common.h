@@ -74,6 +74,28 @@ static inline int axt_max_dynamic_lds(K kernel, int bytes, AxtOncePerDevice &onc
 // the kept tiles of a frame (tile row, tile column), passed to the kernels by value
 struct TileList { int n; short yx[2 * 256]; };
 
+// the last tile row (column) that begins inside a frame of `extent` pixels; -1: no tile does
+static inline int axt_last_tile(int extent, int tile) { return extent >= 1 ? (extent - 1) / tile : -1; }
+
+// The TileList of an entry point `fn` from its host array h_tile_yx [n_tiles][2]. AXT_EINVAL for n_tiles outside 1..256
+// and for a row index outside 0..max_ty or a column index outside 0..max_tx; both limits are capped at 32767, what the
+// short holds. The index itself is compared, never a product of it, so no index can wrap its way past the check.
+static inline int axt_tile_list(const char *fn, const int32_t *h_tile_yx, int n_tiles, int max_ty, int max_tx, TileList *tl)
+{
+    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "%s: n_tiles %d out of range [1,256]", fn, n_tiles);
+    if (max_ty > 32767) max_ty = 32767;
+    if (max_tx > 32767) max_tx = 32767;
+    tl->n = n_tiles;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
+        AXT_REQUIRE(ty >= 0 && ty <= max_ty && tx >= 0 && tx <= max_tx, "%s: tile %d (%d,%d) outside rows 0..%d, columns 0..%d", fn, k,
+                    ty, tx, max_ty, max_tx);
+        tl->yx[2 * k] = (short)ty;
+        tl->yx[2 * k + 1] = (short)tx;
+    }
+    return AXT_OK;
+}
+
 // cnn_front.hip: conv blocks 0 + 1 in one launch: frames -> block 1's output [B,40,128,128]
 int axt_launch_conv_fused01(const float *in, const float *w0, const float *b0, const float *w1, const float *b1, float *out,
                             int B, hipStream_t st, int Hf, int Wf, int t0, int tstep, int item0, int n_tiles, const TileList &tl);

@@ -36,7 +36,7 @@ namespace {
 // network description (deployed ARCHITECTURE, deployed_model/params.txt:34)
 // ------------------------------------------------------------------------------------------------
 struct ConvSpec { int cin, cout, stride, pool, hin; };
-static const ConvSpec kConv[8] = {
+static constexpr ConvSpec kConv[8] = {
     {5, 20, 2, 0, 512}, {20, 40, 2, 0, 256}, {40, 80, 1, 1, 128}, {80, 80, 1, 0, 64},
     {80, 80, 1, 1, 64}, {80, 80, 1, 0, 32},  {80, 80, 1, 1, 32},  {80, 160, 1, 0, 16}};
 constexpr int kFeat = 160 * 16 * 16;   // 40960
@@ -1440,7 +1440,20 @@ static const ConvPlan kPlan[8] = {{5, 2, 1}, {4, 3, 1}, {8, 5, 1}, {8, 5, 1}, {8
 #endif
 constexpr int kChunkA = AXT_CHUNK_A;      // conv blocks 0-2
 constexpr int kChunkB = AXT_CHUNK_B;      // conv blocks 3-4
-constexpr int kFc1Split = 32, kFc2Split = 4, kFc3Split = 4;
+
+// d_act[i] holds conv block i's output, after its pool where the block pools: its floats per item, and the items it has
+// room for (blocks 0-1 run kChunkA items a launch, blocks 2-3 collect kChunkB of them, from block 4 on the whole group)
+constexpr int act_side(int i) { return kConv[i].hin / kConv[i].stride / (kConv[i].pool ? 2 : 1); }
+constexpr size_t act_floats(int i) { return (size_t)kConv[i].cout * act_side(i) * act_side(i); }
+inline int act_slots(int max_batch, int i) { return std::min(max_batch, i < 2 ? kChunkA : i < 4 ? kChunkB : max_batch); }
+static_assert(act_floats(0) == 20u * 256 * 256 && act_floats(1) == 40u * 128 * 128 && act_floats(2) == 80u * 64 * 64 &&
+              act_floats(3) == 80u * 64 * 64 && act_floats(4) == 80u * 32 * 32 && act_floats(5) == 80u * 32 * 32 &&
+              act_floats(6) == 80u * 16 * 16 && act_floats(7) == 160u * 16 * 16 && act_floats(7) == kFeat,
+              "the activation buffers derived from kConv are the network's");
+
+// the three linear layers: out = act(in [fin] x W [fin][fpad] + b), the GEMM split `split` ways along fin
+struct LinearSpec { int fin, fout, fpad, split, sigmoid; };
+static const LinearSpec kLinear[3] = {{kFeat, kFc, kFc, 32, 1}, {kFc, kFc, kFc, 4, 1}, {kFc, kOut, kOutPad, 4, 0}};
 
 }  // namespace
 
@@ -1737,22 +1750,31 @@ int launch_reduce(const float *slab, int S, int M, int N, int Nout, const float 
     return AXT_OK;
 }
 
-// conv blocks 0..2 for up to kChunkA items: frames -> d_act[2] slot `slot0`
-int run_front_a(axt_detector *d, const float *frames, int Hf, int Wf, int t0, int tstep, int item0, int n_tiles,
-                const TileList &tl, int nb, int slot0, hipStream_t st)
+// where a pass reads its items from: item i is tile i % n_tiles of the 5 frames from t0 + (i / n_tiles) * tstep on
+struct FrameSource {
+    const float *frames;
+    int H, W, t0, tstep, n_tiles;
+    TileList tl;
+};
+
+int run_conv_block(axt_detector *d, int li, const float *in, float *out, int nb, hipStream_t st);       // below, the stride-1 blocks
+
+// conv blocks 0..2 for up to kChunkA items, item0 the first: frames -> d_act[2] slot `slot0`
+int run_front_a(axt_detector *d, const FrameSource &src, int item0, int nb, int slot0, hipStream_t st)
 {
+    const int Hf = src.H, Wf = src.W, t0 = src.t0, tstep = src.tstep, n_tiles = src.n_tiles;
     int rc;
     if (d->fuse01 && Wf % 4 == 0) {
         // blocks 0 and 1 in one kernel (its 16-byte input pieces need aligned rows: other widths take the separate kernels)
         ProfSpan ps(d, st, 0, nb);
         d->act0_written = false;
-        if ((rc = axt_launch_conv_fused01(frames, d->d_wconv[0], d->d_bconv[0], d->d_wconv[1], d->d_bconv[1], d->d_act[1], nb, st,
-                                      Hf, Wf, t0, tstep, item0, n_tiles, tl))) return rc;
+        if ((rc = axt_launch_conv_fused01(src.frames, d->d_wconv[0], d->d_bconv[0], d->d_wconv[1], d->d_bconv[1], d->d_act[1], nb, st,
+                                      Hf, Wf, t0, tstep, item0, n_tiles, src.tl))) return rc;
     } else {
     {
         ProfSpan ps(d, st, 0, nb);
         d->act0_written = true;
-        const float *src = frames;
+        const float *in = src.frames;
         int pitch = Wf, t_first = 0;
         if (Wf % 4 != 0) {
             // rows that are not 16-byte aligned: copy the frames this launch reads into a buffer whose pitch is
@@ -1772,12 +1794,12 @@ int run_front_a(axt_detector *d, const float *frames, int Hf, int Wf, int t0, in
             }
             const long n4 = (long)nf * Hf * (pitch / 4);
             hipLaunchKernelGGL(repitch_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                               frames + (size_t)t_first * Hf * Wf, Wf, pitch, n4, d->d_pad);
+                               src.frames + (size_t)t_first * Hf * Wf, Wf, pitch, n4, d->d_pad);
             AXT_LAUNCH_CHECK();
-            src = d->d_pad;
+            in = d->d_pad;
         }
-        rc = launch_conv_s2<5, 20, 5, true, 3>(src, d->d_wconv[0], d->d_bconv[0], d->d_act[0], 512, nb, st, Hf, pitch,
-                                            t0 - t_first, tstep, item0, n_tiles, &tl);
+        rc = launch_conv_s2<5, 20, 5, true, 3>(in, d->d_wconv[0], d->d_bconv[0], d->d_act[0], 512, nb, st, Hf, pitch,
+                                            t0 - t_first, tstep, item0, n_tiles, &src.tl);
         if (rc) return rc;
     }
     {
@@ -1785,139 +1807,135 @@ int run_front_a(axt_detector *d, const float *frames, int Hf, int Wf, int t0, in
         if ((rc = launch_conv_s2<20, 40, 4, false, 2>(d->d_act[0], d->d_wconv[1], d->d_bconv[1], d->d_act[1], 256, nb, st))) return rc;
     }
     }
-    {
-        ProfSpan ps(d, st, 2, nb);
-        float *dst = d->d_act[2] + (size_t)slot0 * 80 * 64 * 64;
-        rc = d->arith == 2 ? launch_conv_wino<40, true>(d->d_act[1], d->d_wwino[2], d->d_bconv[2], dst, 128, nb, st)
-             : d->arith ? launch_conv_b3<40, true>(d->d_act[1], d->d_wb3[2], d->d_bconv[2], dst, 128, nb, st)
-                      : launch_conv<40, 80, true, 8, 5>(d->d_act[1], d->d_wconv[2], d->d_bconv[2], dst, 128, 1, nb, st);
-        if (rc) return rc;
+    return run_conv_block(d, 2, d->d_act[1], d->d_act[2] + (size_t)slot0 * act_floats(2), nb, st);
+}
+
+// The launch of stride-1 block li in the arithmetic the detector is set to. The map side and the channel groups are kConv's
+// and kPlan's; the template arguments are what those two say about block li. Winograd takes its output channels in groups
+// of 80; the bf16x3 kernel has 80 of them, so block 7 runs the direct kernel in that arithmetic.
+template <int CIN, int COUT, bool POOL>
+int launch_conv_arith(axt_detector *d, int li, const float *in, float *out, int nb, hipStream_t st)
+{
+    const int hin = kConv[li].hin;
+    const float *bias = d->d_bconv[li];
+    if (d->arith == 2) return launch_conv_wino<CIN, POOL, COUT / 80>(in, d->d_wwino[li], bias, out, hin, nb, st);
+    if constexpr (COUT == 80)
+        if (d->arith) return launch_conv_b3<CIN, POOL>(in, d->d_wb3[li], bias, out, hin, nb, st);
+    return launch_conv<CIN, COUT, POOL, 8, 5>(in, d->d_wconv[li], bias, out, hin, kPlan[li].ngroups, nb, st);
+}
+
+// One stride-1 conv block, li in 2..7, for nb items: in -> out, under kernel id li
+int run_conv_block(axt_detector *d, int li, const float *in, float *out, int nb, hipStream_t st)
+{
+    AXT_REQUIRE(li >= 2 && li <= 7, "conv block %d is not a stride-1 block", li);
+    ProfSpan ps(d, st, li, nb);
+    switch (li) {
+    case 2: return launch_conv_arith<40, 80, true>(d, li, in, out, nb, st);
+    case 3: case 5: return launch_conv_arith<80, 80, false>(d, li, in, out, nb, st);
+    case 4: case 6: return launch_conv_arith<80, 80, true>(d, li, in, out, nb, st);
+    default: return launch_conv_arith<80, 160, false>(d, li, in, out, nb, st);         // block 7
     }
+}
+
+// conv blocks first..last (within 2..7) for nb items, each reading the output of the block before it. Block li writes
+// d_act[li]; last_out != nullptr: the last of them writes there instead.
+int run_conv_blocks(axt_detector *d, int first, int last, float *last_out, int nb, hipStream_t st)
+{
+    for (int li = first; li <= last; ++li)
+        if (int rc = run_conv_block(d, li, d->d_act[li - 1], li == last && last_out ? last_out : d->d_act[li], nb, st)) return rc;
     return AXT_OK;
 }
 
-// conv blocks 3..4 for up to kChunkB items: d_act[2] -> act4_out
-int run_front_b(axt_detector *d, int nb, float *act4_out, hipStream_t st)
+// The chunk walk: conv blocks 0..4 for items first_item .. first_item + n_items - 1 of a pass (n_items <= max_batch),
+// kChunkB items at a time through blocks 3-4 and, inside those, kChunkA items at a time through blocks 0-2. Item
+// first_item + j leaves block 4 in act4_out + j items. act2_out != nullptr: blocks 3-4 do not run, and block 2's
+// output, which is chunk-sized, is copied out after every chunk, item first_item + j to act2_out + j items.
+int run_front(axt_detector *d, const FrameSource &src, int first_item, int n_items, float *act4_out, float *act2_out,
+              hipStream_t st)
 {
-    int rc;
-    {
-        ProfSpan ps(d, st, 3, nb);
-        rc = d->arith == 2 ? launch_conv_wino<80, false>(d->d_act[2], d->d_wwino[3], d->d_bconv[3], d->d_act[3], 64, nb, st)
-             : d->arith ? launch_conv_b3<80, false>(d->d_act[2], d->d_wb3[3], d->d_bconv[3], d->d_act[3], 64, nb, st)
-                      : launch_conv<80, 80, false, 8, 5>(d->d_act[2], d->d_wconv[3], d->d_bconv[3], d->d_act[3], 64, 1, nb, st);
-        if (rc) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 4, nb);
-        rc = d->arith == 2 ? launch_conv_wino<80, true>(d->d_act[3], d->d_wwino[4], d->d_bconv[4], act4_out, 64, nb, st)
-             : d->arith ? launch_conv_b3<80, true>(d->d_act[3], d->d_wb3[4], d->d_bconv[4], act4_out, 64, nb, st)
-                      : launch_conv<80, 80, true, 8, 5>(d->d_act[3], d->d_wconv[4], d->d_bconv[4], act4_out, 64, 1, nb, st);
-        if (rc) return rc;
-    }
-    return AXT_OK;
-}
-
-// conv layers 5..7 for nb items whose block-4 output is in d_act[4]: d_act[7] [item,160,16,16] is what the first linear
-// layer reads (the flatten of model.py:50-53 is this buffer as it stands)
-// last: the last conv block to run (7, or 6 for axt_cnn_block_features_frames(block = 6))
-int run_back_conv(axt_detector *d, int nb, hipStream_t st, int last = 7)
-{
-    int rc;
-    {
-        ProfSpan ps(d, st, 5, nb);
-        rc = d->arith == 2 ? launch_conv_wino<80, false>(d->d_act[4], d->d_wwino[5], d->d_bconv[5], d->d_act[5], 32, nb, st)
-             : d->arith ? launch_conv_b3<80, false>(d->d_act[4], d->d_wb3[5], d->d_bconv[5], d->d_act[5], 32, nb, st)
-                      : launch_conv<80, 80, false, 8, 5>(d->d_act[4], d->d_wconv[5], d->d_bconv[5], d->d_act[5], 32, 1, nb, st);
-        if (rc) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 6, nb);
-        rc = d->arith == 2 ? launch_conv_wino<80, true>(d->d_act[5], d->d_wwino[6], d->d_bconv[6], d->d_act[6], 32, nb, st)
-             : d->arith ? launch_conv_b3<80, true>(d->d_act[5], d->d_wb3[6], d->d_bconv[6], d->d_act[6], 32, nb, st)
-                      : launch_conv<80, 80, true, 8, 5>(d->d_act[5], d->d_wconv[6], d->d_bconv[6], d->d_act[6], 32, 1, nb, st);
-        if (rc) return rc;
-    }
-    if (last < 7) return AXT_OK;
-    {
-        ProfSpan ps(d, st, 7, nb);
-        rc = d->arith == 2 ? launch_conv_wino<80, false, 2>(d->d_act[6], d->d_wwino[7], d->d_bconv[7], d->d_act[7], 16, nb, st)
-                           : launch_conv<80, 160, false, 8, 5>(d->d_act[6], d->d_wconv[7], d->d_bconv[7], d->d_act[7], 16, 2, nb, st);
-        if (rc) return rc;
-    }
-    return AXT_OK;
-}
-
-// layers 5..7 + the three linear layers for nb items whose block-4 output is in d_act[4]
-int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
-{
-    int rc;
-    if ((rc = run_back_conv(d, nb, st))) return rc;
-    {
-        ProfSpan ps(d, st, 8, nb);
-        if ((rc = launch_gemm(d->d_act[7], kFeat, d->d_wfc[0], kFc, d->d_slab, nb, kFeat, kFc1Split, st))) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 9, nb);
-        if ((rc = launch_reduce(d->d_slab, kFc1Split, nb, kFc, kFc, d->d_bfc[0], 1, d->d_fc1, st))) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 10, nb);
-        if ((rc = launch_gemm(d->d_fc1, kFc, d->d_wfc[1], kFc, d->d_slab, nb, kFc, kFc2Split, st))) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 11, nb);
-        if ((rc = launch_reduce(d->d_slab, kFc2Split, nb, kFc, kFc, d->d_bfc[1], 1, d->d_fc2, st))) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 12, nb);
-        if ((rc = launch_gemm(d->d_fc2, kFc, d->d_wfc[2], kOutPad, d->d_slab, nb, kFc, kFc3Split, st))) return rc;
-    }
-    {
-        ProfSpan ps(d, st, 13, nb);
-        if ((rc = launch_reduce(d->d_slab, kFc3Split, nb, kOutPad, kOut, d->d_bfc[2], 0, d_yolo, st))) return rc;
-    }
-    return AXT_OK;
-}
-
-// d_feat != nullptr: stop after conv block 10 and copy its output, the input of the first linear layer, to
-// d_feat [n_items, 40960] (axt_cnn_features_frames); d_yolo is not written then. feat_block = 6: stop one block earlier and
-// copy d_act[6], [n_items, 20480]; feat_block = 4: run none of conv blocks 5..7 and copy d_act[4], [n_items, 81920]
-// (axt_cnn_block_features_frames); feat_block = 2: run conv blocks 0..2 only and copy d_act[2], [n_items, 327680], which is
-// chunk-sized, out after every chunk
-int forward_items(axt_detector *d, const float *frames, int Hf, int Wf, int t0, int tstep, int n_items, int n_tiles,
-                  const TileList &tl, float *d_yolo, hipStream_t st, float *d_feat = nullptr, int feat_block = 7)
-{
-    for (int base = 0; base < n_items; base += d->max_batch) {
-        const int nb = (n_items - base < d->max_batch) ? n_items - base : d->max_batch;
-        for (int cb = 0; cb < nb; cb += kChunkB) {
-            const int nbb = (nb - cb < kChunkB) ? nb - cb : kChunkB;
-            for (int c = 0; c < nbb; c += kChunkA) {
-                const int nc = (nbb - c < kChunkA) ? nbb - c : kChunkA;
-                const int rc = run_front_a(d, frames, Hf, Wf, t0, tstep, base + cb + c, n_tiles, tl, nc, c, st);
-                if (rc) return rc;
-            }
-            if (d_feat && feat_block == 2) {
-                const size_t per_item = (size_t)80 * 64 * 64;
-                AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)(base + cb) * per_item, d->d_act[2], (size_t)nbb * per_item * sizeof(float),
-                                             hipMemcpyDeviceToDevice, st));
-                continue;
-            }
-            const int rc = run_front_b(d, nbb, d->d_act[4] + (size_t)cb * 80 * 32 * 32, st);
-            if (rc) return rc;
-        }
-        if (d_feat && feat_block == 2) continue;
-        if (d_feat) {
-            const int rc = feat_block >= 6 ? run_back_conv(d, nb, st, feat_block) : AXT_OK;
-            if (rc) return rc;
-            const size_t per_item = feat_block == 7 ? (size_t)kFeat : feat_block == 6 ? (size_t)80 * 16 * 16 : (size_t)80 * 32 * 32;
-            AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)base * per_item, d->d_act[feat_block], (size_t)nb * per_item * sizeof(float),
+    for (int cb = 0; cb < n_items; cb += kChunkB) {
+        const int nbb = std::min(n_items - cb, kChunkB);
+        for (int c = 0; c < nbb; c += kChunkA)
+            if (int rc = run_front_a(d, src, first_item + cb + c, std::min(nbb - c, kChunkA), c, st)) return rc;
+        if (act2_out) {
+            AXT_CHECK_HIP(hipMemcpyAsync(act2_out + (size_t)cb * act_floats(2), d->d_act[2], (size_t)nbb * act_floats(2) * sizeof(float),
                                          hipMemcpyDeviceToDevice, st));
             continue;
         }
-        const int rc = run_back(d, nb, d_yolo + (size_t)base * kOut, st);
-        if (rc) return rc;
+        if (int rc = run_conv_blocks(d, 3, 4, act4_out + (size_t)cb * act_floats(4), nbb, st)) return rc;
     }
     return AXT_OK;
+}
+
+// conv blocks 5..7 + the three linear layers for nb items whose block-4 output is in d_act[4]. d_act[7] [item,160,16,16]
+// is what the first linear layer reads: the flatten of model.py:50-53 is this buffer as it stands. Kernel ids 8 + 2l and
+// 9 + 2l are linear layer l's GEMM and its reduction.
+int run_back(axt_detector *d, int nb, float *d_yolo, hipStream_t st)
+{
+    if (int rc = run_conv_blocks(d, 5, 7, nullptr, nb, st)) return rc;
+    const float *in = d->d_act[7];
+    float *const out[3] = {d->d_fc1, d->d_fc2, d_yolo};
+    for (int l = 0; l < 3; ++l) {
+        const LinearSpec &ls = kLinear[l];
+        {
+            ProfSpan ps(d, st, 8 + 2 * l, nb);
+            if (int rc = launch_gemm(in, ls.fin, d->d_wfc[l], ls.fpad, d->d_slab, nb, ls.fin, ls.split, st)) return rc;
+        }
+        ProfSpan ps(d, st, 9 + 2 * l, nb);
+        if (int rc = launch_reduce(d->d_slab, ls.split, nb, ls.fpad, ls.fout, d->d_bfc[l], ls.sigmoid, out[l], st)) return rc;
+        in = out[l];
+    }
+    return AXT_OK;
+}
+
+// A whole pass in groups of max_batch items. d_feat == nullptr: YOLO grids to d_yolo. Otherwise the pass stops after conv
+// block feat_block (2, 4, 6 or 7) and copies that block's output to d_feat [n_items, act_floats(feat_block)]; d_yolo is
+// not written then (axt_cnn_features_frames, axt_cnn_block_features_frames).
+int forward_items(axt_detector *d, const FrameSource &src, int n_items, float *d_yolo, hipStream_t st, float *d_feat = nullptr,
+                  int feat_block = 7)
+{
+    for (int base = 0; base < n_items; base += d->max_batch) {
+        const int nb = std::min(n_items - base, d->max_batch);
+        const bool tap2 = d_feat && feat_block == 2;
+        if (int rc = run_front(d, src, base, nb, d->d_act[4], tap2 ? d_feat + (size_t)base * act_floats(2) : nullptr, st)) return rc;
+        if (tap2) continue;
+        if (!d_feat) {
+            if (int rc = run_back(d, nb, d_yolo + (size_t)base * kOut, st)) return rc;
+            continue;
+        }
+        if (int rc = run_conv_blocks(d, 5, feat_block, nullptr, nb, st)) return rc;
+        const size_t per_item = act_floats(feat_block);
+        AXT_CHECK_HIP(hipMemcpyAsync(d_feat + (size_t)base * per_item, d->d_act[feat_block], (size_t)nb * per_item * sizeof(float),
+                                     hipMemcpyDeviceToDevice, st));
+    }
+    return AXT_OK;
+}
+
+// What the frames entry points share: their argument checks, and the source their pass reads.
+int frames_source(const char *fn, const axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
+                  const int32_t *h_tile_yx, int n_tiles, FrameSource *src)
+{
+    AXT_REQUIRE(det && d_frames && h_tile_yx, "null argument");
+    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "%s: frames [%d,%d) + context exceed T_all=%d", fn, t0,
+                t0 + n_frames, T_all);
+    src->frames = d_frames;
+    src->H = H;
+    src->W = W;
+    src->t0 = t0;
+    src->tstep = 1;
+    src->n_tiles = n_tiles;
+    return axt_tile_list(fn, h_tile_yx, n_tiles, axt_last_tile(H, AXT_TILE), axt_last_tile(W, AXT_TILE), &src->tl);
+}
+
+int block_features_frames(const char *fn, axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
+                          const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream)
+{
+    AXT_REQUIRE(block == 2 || block == 4 || block == 6 || block == 7, "%s: block %d is none of 2, 4, 6, 7", fn, block);
+    AXT_REQUIRE(d_feat, "null argument");
+    FrameSource src;
+    if (int rc = frames_source(fn, det, d_frames, T_all, H, W, t0, n_frames, h_tile_yx, n_tiles, &src)) return rc;
+    if (n_frames == 0) return AXT_OK;
+    return forward_items(det, src, n_frames * n_tiles, nullptr, (hipStream_t)stream, d_feat, block);
 }
 
 }  // namespace
@@ -1931,7 +1949,7 @@ double axt_cnn_flops_per_tile(void)
         const double ho = c.hin / c.stride;
         f += 2.0 * ho * ho * c.cout * c.cin * 9;
     }
-    f += 2.0 * kFeat * kFc + 2.0 * kFc * kFc + 2.0 * kFc * kOut;
+    for (const LinearSpec &l : kLinear) f += 2.0 * l.fin * l.fout;
     return f;
 }
 
@@ -1958,28 +1976,27 @@ int axt_detector_create(const float *const *h_tensors, int n_tensors, int max_ba
         }
     }
     // linear layers: reference stores [out,in]; the GEMM wants [in][out_padded]
-    const int fin[3] = {kFeat, kFc, kFc}, fout[3] = {kFc, kFc, kOut}, fpad[3] = {kFc, kFc, kOutPad};
+    size_t slab = 0;                                    // the GEMMs' partial sums: the largest of the three layers'
     for (int l = 0; l < 3 && !rc; ++l) {
+        const LinearSpec &ls = kLinear[l];
         const float *w = h_tensors[48 + 2 * l], *b = h_tensors[48 + 2 * l + 1];
-        std::vector<float> wt((size_t)fin[l] * fpad[l], 0.f);
-        for (int o = 0; o < fout[l]; ++o)
-            for (int i = 0; i < fin[l]; ++i) wt[(size_t)i * fpad[l] + o] = w[(size_t)o * fin[l] + i];
+        std::vector<float> wt((size_t)ls.fin * ls.fpad, 0.f);
+        for (int o = 0; o < ls.fout; ++o)
+            for (int i = 0; i < ls.fin; ++i) wt[(size_t)i * ls.fpad + o] = w[(size_t)o * ls.fin + i];
         if ((rc = dev_alloc(d, &d->d_wfc[l], wt.size()))) break;
-        if ((rc = dev_alloc(d, &d->d_bfc[l], (size_t)fout[l]))) break;
+        if ((rc = dev_alloc(d, &d->d_bfc[l], (size_t)ls.fout))) break;
         if (hipMemcpy(d->d_wfc[l], wt.data(), wt.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d->d_bfc[l], b, (size_t)fout[l] * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            hipMemcpy(d->d_bfc[l], b, (size_t)ls.fout * 4, hipMemcpyHostToDevice) != hipSuccess) {
             axt_set_error("weight upload failed (linear %d)", l);
             rc = AXT_EHIP;
         }
+        slab = std::max(slab, (size_t)ls.split * ls.fpad);
     }
     // activations
-    const size_t per_item[8] = {20u * 256 * 256, 40u * 128 * 128, 80u * 64 * 64, 80u * 64 * 64,
-                                80u * 32 * 32,   80u * 32 * 32,   80u * 16 * 16, 160u * 16 * 16};
-    for (int i = 0; i < 8 && !rc; ++i)
-        rc = dev_alloc(d, &d->d_act[i], per_item[i] * (size_t)std::min(max_batch, i < 2 ? kChunkA : i < 4 ? kChunkB : max_batch));
-    if (!rc) rc = dev_alloc(d, &d->d_slab, (size_t)kFc1Split * max_batch * kFc);
-    if (!rc) rc = dev_alloc(d, &d->d_fc1, (size_t)max_batch * kFc);
-    if (!rc) rc = dev_alloc(d, &d->d_fc2, (size_t)max_batch * kFc);
+    for (int i = 0; i < 8 && !rc; ++i) rc = dev_alloc(d, &d->d_act[i], act_floats(i) * act_slots(max_batch, i));
+    if (!rc) rc = dev_alloc(d, &d->d_slab, slab * max_batch);
+    if (!rc) rc = dev_alloc(d, &d->d_fc1, (size_t)max_batch * kLinear[0].fout);
+    if (!rc) rc = dev_alloc(d, &d->d_fc2, (size_t)max_batch * kLinear[1].fout);
     if (!rc && hipDeviceSynchronize() != hipSuccess) {
         axt_set_error("device synchronize failed after upload");
         rc = AXT_EHIP;
@@ -2054,8 +2071,8 @@ int axt_detector_conv_spec(int li, int *cin, int *cout, int *stride)
 int axt_detector_linear_spec(int layer, int *fin, int *fout)
 {
     AXT_REQUIRE(layer >= 0 && layer < 3 && fin && fout, "linear layer %d not in 0..2", layer);
-    *fin = layer == 0 ? kFeat : kFc;
-    *fout = layer == 2 ? kOut : kFc;
+    *fin = kLinear[layer].fin;
+    *fout = kLinear[layer].fout;
     return AXT_OK;
 }
 
@@ -2091,9 +2108,9 @@ int axt_detector_load_linear(axt_detector *d, int layer, const float *d_weight, 
     AXT_REQUIRE(d && d_weight && d_bias, "%s: null argument", fn);
     AXT_REQUIRE(layer >= 0 && layer < 3, "%s: linear layer %d not in 0..2", fn, layer);
     hipStream_t st = (hipStream_t)stream;
-    const int fin = layer == 0 ? kFeat : kFc, fout = layer == 2 ? kOut : kFc, fpad = layer == 2 ? kOutPad : kFc;
-    if (int rc = axt_repack_linear(d_weight, fin, fout, fpad, d->d_wfc[layer], st)) return rc;
-    AXT_CHECK_HIP(hipMemcpyAsync(d->d_bfc[layer], d_bias, (size_t)fout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    const LinearSpec &ls = kLinear[layer];
+    if (int rc = axt_repack_linear(d_weight, ls.fin, ls.fout, ls.fpad, d->d_wfc[layer], st)) return rc;
+    AXT_CHECK_HIP(hipMemcpyAsync(d->d_bfc[layer], d_bias, (size_t)ls.fout * sizeof(float), hipMemcpyDeviceToDevice, st));
     return AXT_OK;
 }
 
@@ -2167,9 +2184,8 @@ double axt_cnn_kernel_flops_per_tile(int kernel)
         const double ho = c.hin / c.stride;
         return 2.0 * ho * ho * c.cout * c.cin * 9;
     }
-    const double f[6] = {2.0 * kFeat * kFc, (double)kFc1Split * kFc, 2.0 * kFc * kFc, (double)kFc2Split * kFc,
-                         2.0 * kFc * kOut, (double)kFc3Split * kOut};
-    return f[kernel - 8];
+    const LinearSpec &l = kLinear[(kernel - 8) / 2];        // its GEMM, then the reduction of the GEMM's partial sums
+    return (kernel - 8) % 2 == 0 ? 2.0 * l.fin * l.fout : (double)l.split * l.fout;
 }
 
 int axt_cnn_forward(axt_detector *det, const float *d_x, int B, float *d_yolo, void *stream)
@@ -2179,107 +2195,45 @@ int axt_cnn_forward(axt_detector *det, const float *d_x, int B, float *d_yolo, v
     if (B == 0) return AXT_OK;
     // X[B,5,512,512] is a timelapse of 5*B frames of 512x512 in which item b reads frames 5b..5b+4:
     // the frames path with a frame step of 5 and a single tile at the origin.
-    TileList tl;
-    tl.n = 1;
-    tl.yx[0] = 0;
-    tl.yx[1] = 0;
-    return forward_items(det, d_x, AXT_TILE, AXT_TILE, 0, AXT_IN_CH, B, 1, tl, d_yolo, (hipStream_t)stream);
+    FrameSource src = {d_x, AXT_TILE, AXT_TILE, 0, AXT_IN_CH, 1, {1, {0, 0}}};
+    return forward_items(det, src, B, d_yolo, (hipStream_t)stream);
 }
 
 int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                            const int32_t *h_tile_yx, int n_tiles, float *d_yolo, void *stream)
 {
-    AXT_REQUIRE(det && d_frames && d_yolo && h_tile_yx, "null argument");
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
-    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",
-                t0, t0 + n_frames, T_all);
-    TileList tl;
-    tl.n = n_tiles;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
-                    ty, tx, H, W);
-        tl.yx[2 * k] = (short)ty;
-        tl.yx[2 * k + 1] = (short)tx;
-    }
+    static const char fn[] = "axt_cnn_forward_frames";
+    AXT_REQUIRE(d_yolo, "null argument");
+    FrameSource src;
+    if (int rc = frames_source(fn, det, d_frames, T_all, H, W, t0, n_frames, h_tile_yx, n_tiles, &src)) return rc;
     if (n_frames == 0) return AXT_OK;
-    return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, d_yolo, (hipStream_t)stream);
+    return forward_items(det, src, n_frames * n_tiles, d_yolo, (hipStream_t)stream);
 }
 
 int axt_cnn_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                             const int32_t *h_tile_yx, int n_tiles, float *d_feat, void *stream)
 {
-    AXT_REQUIRE(det && d_frames && d_feat && h_tile_yx, "null argument");
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
-    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",
-                t0, t0 + n_frames, T_all);
-    TileList tl;
-    tl.n = n_tiles;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
-                    ty, tx, H, W);
-        tl.yx[2 * k] = (short)ty;
-        tl.yx[2 * k + 1] = (short)tx;
-    }
-    if (n_frames == 0) return AXT_OK;
-    return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, nullptr, (hipStream_t)stream, d_feat);
+    return block_features_frames("axt_cnn_features_frames", det, d_frames, T_all, H, W, t0, n_frames, h_tile_yx, n_tiles, 7, d_feat,
+                                 stream);
 }
 
 int axt_cnn_block_features_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                                   const int32_t *h_tile_yx, int n_tiles, int block, float *d_feat, void *stream)
 {
-    AXT_REQUIRE(block == 2 || block == 4 || block == 6 || block == 7, "axt_cnn_block_features_frames: block %d is none of 2, 4, 6, 7",
-                block);
-    AXT_REQUIRE(det && d_frames && d_feat && h_tile_yx, "null argument");
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
-    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",
-                t0, t0 + n_frames, T_all);
-    TileList tl;
-    tl.n = n_tiles;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
-                    ty, tx, H, W);
-        tl.yx[2 * k] = (short)ty;
-        tl.yx[2 * k + 1] = (short)tx;
-    }
-    if (n_frames == 0) return AXT_OK;
-    return forward_items(det, d_frames, H, W, t0, 1, n_frames * n_tiles, n_tiles, tl, nullptr, (hipStream_t)stream, d_feat,
-                         block);
+    return block_features_frames("axt_cnn_block_features_frames", det, d_frames, T_all, H, W, t0, n_frames, h_tile_yx, n_tiles,
+                                 block, d_feat, stream);
 }
 
 int axt_cnn_front_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W, int t0, int n_frames,
                          const int32_t *h_tile_yx, int n_tiles, int item0, void *stream)
 {
-    AXT_REQUIRE(det && d_frames && h_tile_yx, "null argument");
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "n_tiles %d out of range [1,256]", n_tiles);
-    AXT_REQUIRE(t0 >= 0 && n_frames >= 0 && t0 + n_frames + 4 <= T_all, "frames [%d,%d) + context exceed T_all=%d",
-                t0, t0 + n_frames, T_all);
+    static const char fn[] = "axt_cnn_front_frames";
+    FrameSource src;
+    if (int rc = frames_source(fn, det, d_frames, T_all, H, W, t0, n_frames, h_tile_yx, n_tiles, &src)) return rc;
     const int n_items = n_frames * n_tiles;
-    AXT_REQUIRE(item0 >= 0 && item0 + n_items <= det->max_batch, "items [%d,%d) exceed the detector's max_batch %d", item0,
+    AXT_REQUIRE(item0 >= 0 && item0 + n_items <= det->max_batch, "%s: items [%d,%d) exceed the detector's max_batch %d", fn, item0,
                 item0 + n_items, det->max_batch);
-    TileList tl;
-    tl.n = n_tiles;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * AXT_TILE < H && (long)tx * AXT_TILE < W, "tile %d (%d,%d) outside %dx%d", k,
-                    ty, tx, H, W);
-        tl.yx[2 * k] = (short)ty;
-        tl.yx[2 * k + 1] = (short)tx;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    for (int cb = 0; cb < n_items; cb += kChunkB) {
-        const int nbb = (n_items - cb < kChunkB) ? n_items - cb : kChunkB;
-        for (int c = 0; c < nbb; c += kChunkA) {
-            const int nc = (nbb - c < kChunkA) ? nbb - c : kChunkA;
-            const int rc = run_front_a(det, d_frames, H, W, t0, 1, cb + c, n_tiles, tl, nc, c, st);
-            if (rc) return rc;
-        }
-        const int rc = run_front_b(det, nbb, det->d_act[4] + (size_t)(item0 + cb) * 80 * 32 * 32, st);
-        if (rc) return rc;
-    }
-    return AXT_OK;
+    return run_front(det, src, 0, n_items, det->d_act[4] + (size_t)item0 * act_floats(4), nullptr, (hipStream_t)stream);
 }
 
 int axt_cnn_back(axt_detector *det, int n_items, float *d_yolo, void *stream)
@@ -2297,8 +2251,8 @@ int axt_cnn_back(axt_detector *det, int n_items, float *d_yolo, void *stream)
 // the sigmoid. h_out receives n items from slot slot0 as dense [n, C, H, W] ([n, 1024] for 8 and 9). Every buffer is stored
 // as dense f32 NCHW / [items][1024] already (conv_epilogue, reduce_bias_act), so this is one copy and no conversion.
 // Synchronises the device first; nothing here is on the forward path.
-// Which item sits in which slot after a pass (forward_items, axt_cnn_front_frames, axt_cnn_back), items numbered as the
-// pass numbers them:
+// The sizes are act_floats() and act_slots(), which create allocates by. Which item sits in which slot after a pass
+// (forward_items over run_front and run_back; axt_cnn_front_frames, axt_cnn_back), items numbered as the pass numbers them:
 //   buffers 4-9 hold the last group of max_batch items in order: item base + j in slot j (axt_cnn_front_frames: the
 //     call's item k in slot item0 + k of buffer 4; buffers 5-9 are written by axt_cnn_back for items 0..n_items-1);
 //   buffers 2-3 hold the last chunk_b group of that max_batch group: its item j in slot j;
@@ -2310,15 +2264,14 @@ extern "C" int axt_debug_cnn_activation(const axt_detector *det, int which, int 
 {
     AXT_REQUIRE(det && h_out, "null argument");
     AXT_REQUIRE(which >= 0 && which <= 9, "axt_debug_cnn_activation: buffer %d not in 0..9", which);
-    static const size_t per_item[10] = {20u * 256 * 256, 40u * 128 * 128, 80u * 64 * 64, 80u * 64 * 64, 80u * 32 * 32,
-                                        80u * 32 * 32,   80u * 16 * 16,   160u * 16 * 16, (size_t)kFc,  (size_t)kFc};
-    const int cap = std::min(det->max_batch, which < 2 ? kChunkA : which < 4 ? kChunkB : det->max_batch);
+    const size_t per_item = which < 8 ? act_floats(which) : (size_t)kLinear[which - 8].fout;
+    const int cap = act_slots(det->max_batch, which);
     AXT_REQUIRE(slot0 >= 0 && n >= 0 && slot0 <= cap && n <= cap - slot0, "axt_debug_cnn_activation: slots [%d,%d) exceed the %d of buffer %d",
                 slot0, slot0 + n, cap, which);
     AXT_REQUIRE(which != 0 || det->act0_written, "axt_debug_cnn_activation: the last pass ran the fused front kernel, which does not write block 0's output");
     const float *src = which < 8 ? det->d_act[which] : which == 8 ? det->d_fc1 : det->d_fc2;
     AXT_CHECK_HIP(hipDeviceSynchronize());
-    if (n > 0) AXT_CHECK_HIP(hipMemcpy(h_out, src + (size_t)slot0 * per_item[which], (size_t)n * per_item[which] * sizeof(float), hipMemcpyDeviceToHost));
+    if (n > 0) AXT_CHECK_HIP(hipMemcpy(h_out, src + (size_t)slot0 * per_item, (size_t)n * per_item * sizeof(float), hipMemcpyDeviceToHost));
     return AXT_OK;
 }
 

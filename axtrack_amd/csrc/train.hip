@@ -417,15 +417,8 @@ int axt_yolo_targets(const int32_t *d_lx, const int32_t *d_ly, const int32_t *d_
 {
     AXT_REQUIRE(d_lx && d_ly && d_lcount && h_tile_yx && d_target, "axt_yolo_targets: null argument");
     AXT_REQUIRE(F >= 0 && cap >= 1, "axt_yolo_targets: F=%d cap=%d", F, cap);
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "axt_yolo_targets: n_tiles %d out of range [1,256]", n_tiles);
     TileList tl;
-    tl.n = n_tiles;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && ty < 32767 && tx < 32767, "axt_yolo_targets: tile %d (%d,%d) out of range (0..32766)", k, ty, tx);
-        tl.yx[2 * k] = (short)ty;
-        tl.yx[2 * k + 1] = (short)tx;
-    }
+    if (int rc = axt_tile_list("axt_yolo_targets", h_tile_yx, n_tiles, 32766, 32766, &tl)) return rc;
     const long total = (long)F * n_tiles * AXT_CELLS;
     if (total == 0) return AXT_OK;
     AXT_REQUIRE(total < (1l << 31) * 256, "axt_yolo_targets: %d frames x %d tiles: too many cells (2^39 at most)", F, n_tiles);

@@ -851,19 +851,11 @@ int axt_tile_stacks(const float *d_frames, int T_all, int H, int W, int t0, int 
     AXT_REQUIRE(d_frames && h_tile_yx && d_index && d_out, "%s: null argument", fn);
     AXT_REQUIRE(H >= 1 && W >= 1 && H <= kMaxPoolHW && W <= kMaxPoolHW, "%s: frames of %d x %d not in [1,%d]", fn, H, W,
                 kMaxPoolHW);
-    AXT_REQUIRE(n_tiles >= 1 && n_tiles <= 256, "%s: n_tiles %d out of range [1,256]", fn, n_tiles);
     AXT_REQUIRE(t0 >= 0 && n_frames >= 1 && n_frames <= (1 << 22) && (int64_t)t0 + n_frames + (kStackC - 1) <= T_all,
                 "%s: frames [%d,%d) + context exceed T_all=%d", fn, t0, t0 + n_frames, T_all);
     AXT_REQUIRE(B >= 1 && B <= 1024, "%s: batch %d not in [1,1024]", fn, B);
     TileList tl;
-    tl.n = n_tiles;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int ty = h_tile_yx[2 * k], tx = h_tile_yx[2 * k + 1];
-        AXT_REQUIRE(ty >= 0 && tx >= 0 && (long)ty * kStackT < H && (long)tx * kStackT < W, "%s: tile %d (%d,%d) outside %dx%d", fn, k, ty,
-                    tx, H, W);
-        tl.yx[2 * k] = (short)ty;
-        tl.yx[2 * k + 1] = (short)tx;
-    }
+    if (int rc = axt_tile_list(fn, h_tile_yx, n_tiles, axt_last_tile(H, kStackT), axt_last_tile(W, kStackT), &tl)) return rc;
     const bool vec = W % 4 == 0 && (uintptr_t)d_frames % 16 == 0 && (uintptr_t)d_out % 16 == 0;
     const size_t n = (size_t)B * kStackC * kStackT * kStackT / (vec ? 4 : 1);
     const dim3 grid((unsigned)((n + 255) / 256));

@@ -59,6 +59,19 @@ def state_dict_tensor_order():
     return keys
 
 
+def _frames_args(frames, tile_yx, t0=0, n_frames=None, device=None):
+    """What every entry point that reads a timelapse hands the library: frames checked (a contiguous f32 [T_all, H, W] on
+    the GPU; on `device` where one is given) -> (T_all, H, W, n_frames, tile_yx), n_frames defaulting to every detection
+    frame from t0 on and tile_yx as contiguous i32 [n_tiles, 2]."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() == 3 and frames.is_contiguous()
+            and frames.dtype == torch.float32 and device in (None, frames.device)):
+        raise ValueError('frames must be a contiguous f32 tensor [T_all, H, W] on the GPU')
+    T_all, H, W = frames.shape
+    if n_frames is None:
+        n_frames = T_all - 4 - t0
+    return T_all, H, W, n_frames, np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+
+
 class Detector:
     """Device-resident YOLO_AXTrack (model.py:20-125) in eval mode; `detect_axons` keeps the
     reference's name and tensor contract (model.py:119-125)."""
@@ -233,12 +246,8 @@ class Detector:
     def detect_frames(self, frames, tile_yx, t0=0, n_frames=None):
         """frames f32 [T_all,H,W] on the GPU -> YOLO grids [n_frames, n_tiles, 12,12,3] for detection
         frames t0..t0+n_frames-1 (get_frametiles_stack + detect_axons, AxonDetections.py:115-118)."""
-        T_all, H, W = frames.shape
-        if n_frames is None:
-            n_frames = T_all - 4 - t0
-        tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+        T_all, H, W, n_frames, tile_yx = _frames_args(frames, tile_yx, t0, n_frames, self.device)
         out = torch.empty((n_frames, len(tile_yx), S, S, 3), dtype=torch.float32, device=self.device)
-        assert frames.is_contiguous() and frames.dtype == torch.float32 and frames.device == self.device
         with torch.cuda.device(self.device):
             _lib.check(self._lib.axt_cnn_forward_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,
                                                         tile_yx.ctypes.data, len(tile_yx), out.data_ptr(), _stream()),
@@ -268,10 +277,7 @@ class Detector:
         return self._block_table(frames, tile_yx, t0, n_frames, out, block, TRUNK_FEATURES[block])
 
     def _block_table(self, frames, tile_yx, t0, n_frames, out, block, width):
-        T_all, H, W = frames.shape
-        if n_frames is None:
-            n_frames = T_all - 4 - t0
-        tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
+        T_all, H, W, n_frames, tile_yx = _frames_args(frames, tile_yx, t0, n_frames, self.device)
         n_items = n_frames * len(tile_yx)
         if out is None:
             out = torch.empty((n_items, width), dtype=torch.float32, device=self.device)
@@ -280,7 +286,6 @@ class Detector:
                     and out.shape[1] == width and out.shape[0] >= n_items):
                 raise ValueError(f'out must be a contiguous f32 table [>= {n_items}, {width}] on {self.device}')
             out = out[:n_items]
-        assert frames.is_contiguous() and frames.dtype == torch.float32 and frames.device == self.device
         with torch.cuda.device(self.device):
             if block == 7:
                 _lib.check(self._lib.axt_cnn_features_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames,
@@ -296,9 +301,7 @@ class Detector:
     def front_frames(self, frames, tile_yx, t0, n_frames, item0):
         """Conv blocks 0-5 of detection frames t0 .. t0+n_frames-1 into the detector's batch buffer from item `item0`
         (axt_cnn_front_frames): input that arrives in chunks. back() finishes the pass for all items at once."""
-        T_all, H, W = frames.shape
-        tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
-        assert frames.is_contiguous() and frames.dtype == torch.float32 and frames.device == self.device
+        T_all, H, W, n_frames, tile_yx = _frames_args(frames, tile_yx, t0, n_frames, self.device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.axt_cnn_front_frames(self._h, frames.data_ptr(), T_all, H, W, t0, n_frames, tile_yx.ctypes.data,
                                                       len(tile_yx), int(item0), _stream()), 'axt_cnn_front_frames')
@@ -317,14 +320,9 @@ def tile_stacks(frames, tile_yx, index, out=None):
     tensor on the GPU, or host integers, which are checked) -> f32 [B, 5, 512, 512]: channel c of item (f, k) is frame f + c,
     from the tile's origin, +0.0 beyond H or W. out: a contiguous f32 tensor of at least B stacks to write into."""
     _require_gpu()
-    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dim() == 3 and frames.is_contiguous()
-            and frames.dtype == torch.float32):
-        raise ValueError('frames must be a contiguous f32 tensor [T_all, H, W] on the GPU')
-    T_all, H, W = frames.shape
-    n_frames = T_all - 4
+    T_all, H, W, n_frames, tile_yx = _frames_args(frames, tile_yx)
     if n_frames < 1:
         raise ValueError(f'{T_all} frames hold no stack of 5')
-    tile_yx = np.ascontiguousarray(tile_yx, np.int32).reshape(-1, 2)
     if isinstance(index, torch.Tensor):
         index = index.to(frames.device, torch.int32).contiguous().reshape(-1)
     else:

@@ -103,7 +103,8 @@ int axt_cnn_forward(axt_detector *det, const float *d_x, int B, float *d_yolo, v
  * tile k reads frames t..t+4 at tile origin (tile_yx[2k]*512, tile_yx[2k+1]*512), zero beyond
  * H/W (ZeroPad2d at Timelapse.py:529-533). Output d_yolo f32 [n_frames, n_tiles, 12,12,3] for
  * detection frames t0 .. t0+n_frames-1. n_frames*n_tiles may exceed max_batch (chunked). t0 >= 0, n_frames >= 0 and
- * t0 + n_frames + 4 <= T_all; 1 <= n_tiles <= 256, every tile's origin inside the frame (row * 512 < H, col * 512 < W). */
+ * t0 + n_frames + 4 <= T_all; 1 <= n_tiles <= 256, every tile's origin inside the frame (row * 512 < H, col * 512 < W).
+ * A tile index above 32767 is AXT_EINVAL whatever H and W are, here and in every entry point that takes h_tile_yx. */
 int axt_cnn_forward_frames(axt_detector *det, const float *d_frames, int T_all, int H, int W,
                            int t0, int n_frames, const int32_t *h_tile_yx, int n_tiles,
                            float *d_yolo, void *stream);

@@ -665,3 +665,104 @@ int main()
     stated = [line for name in sorted(os.listdir(csrc)) if name.endswith(('.hip', '.h', '.cpp'))
               for line in open(os.path.join(csrc, name)) if '{-1, 1, 0, 0, -1, -1, 1, 1}' in line]
     assert len(stated) == 1, stated
+
+
+def test_the_tile_list_is_checked_on_the_index_itself(tmp_path):
+    """Every entry point that takes h_tile_yx builds its TileList with axt_tile_list (csrc/axt_common.h): n_tiles in 1..256,
+    every index in 0..limit with the limit capped at 32767, what the list's short holds; the frame callers' limit is
+    axt_last_tile(extent, 512). A host program runs the helper over the cases; what it must answer is restated here. The
+    index is compared, never its product with 512, so 4194304 (whose product wraps an int) and 39062 (a row of a frame of
+    20 000 000 rows, which would wrap in the short) are refused. Built a second time with the address and undefined-behaviour
+    sanitizers, the program must answer the same."""
+    import subprocess
+    import contract_cases as cc
+    INT_MAX = 2 ** 31 - 1
+    cases = []                                                # (name, 'E' extents | 'L' limits, a, b, n_tiles, tiles)
+
+    def case(name, kind, a, b, tiles, n_tiles=None):
+        cases.append((name, kind, a, b, len(tiles) if n_tiles is None else n_tiles, tiles))
+    case('n_tiles 0', 'E', 512, 512, [(0, 0)], n_tiles=0)
+    case('n_tiles 1', 'E', 512, 512, [(0, 0)])
+    case('n_tiles 256', 'E', 1024, 1024, [(k % 2, k // 2 % 2) for k in range(256)])
+    case('n_tiles 257', 'E', 1024, 1024, [(0, 0)] * 257)
+    case('row -1', 'E', 1024, 1024, [(-1, 0)])
+    case('column -1', 'E', 1024, 1024, [(0, -1)])
+    case('a bad tile behind good ones', 'E', 1024, 1024, [(0, 0), (1, 1), (2, 0)])
+    for ext in (512, 513, 1024):
+        last = (ext - 1) // 512
+        case(f'last row inside H = {ext}', 'E', ext, 4, [(last, 0)])
+        case(f'first row beyond H = {ext}', 'E', ext, 4, [(last + 1, 0)])
+        case(f'last column inside W = {ext}', 'E', 4, ext, [(0, last)])
+        case(f'first column beyond W = {ext}', 'E', 4, ext, [(0, last + 1)])
+    case('an empty frame holds no tile', 'E', 0, 0, [(0, 0)])
+    case('4194304 in a frame', 'E', 512, 512, [(4194304, 0)])
+    case('4194304 under the largest limit', 'L', INT_MAX, INT_MAX, [(0, 4194304)])
+    case('32767 under a limit above it', 'L', 40000, INT_MAX, [(32767, 32767)])
+    case('row 32768 under a limit above it', 'L', 40000, INT_MAX, [(32768, 0)])
+    case('column 32768 under a limit above it', 'L', 40000, INT_MAX, [(0, 32768)])
+    case('row 39062 of 20 000 000 rows', 'E', 20000000, 4, [(39062, 0)])
+    case('row 32767 of 20 000 000 rows', 'E', 20000000, 4, [(32767, 0)])
+    case('axt_yolo_targets: 32766', 'L', 32766, 32766, [(32766, 32766)])
+    case('axt_yolo_targets: row 32767', 'L', 32766, 32766, [(32767, 0)])
+    case('axt_yolo_targets: column 32767', 'L', 32766, 32766, [(0, 32767)])
+
+    def expected(kind, a, b, n_tiles, tiles):
+        max_ty, max_tx = ((a - 1) // 512 if a >= 1 else -1, (b - 1) // 512 if b >= 1 else -1) if kind == 'E' else (a, b)
+        ok = 1 <= n_tiles <= 256 and all(0 <= ty <= min(max_ty, 32767) and 0 <= tx <= min(max_tx, 32767) for ty, tx in tiles[:n_tiles])
+        return (cc.OK, n_tiles, [v for t in tiles[:n_tiles] for v in t]) if ok else (cc.EINVAL, None, None)
+
+    src = tmp_path / 'tiles.cpp'
+    src.write_text(r'''
+#include <stdarg.h>
+#include "axt_common.h"
+static char g_msg[512];
+void axt_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
+    va_end(ap);
+}
+int main()
+{
+    char kind;
+    int a, b, n_tiles, given;
+    while (scanf(" %c %d %d %d %d", &kind, &a, &b, &n_tiles, &given) == 5) {
+        int32_t *yx = new int32_t[2 * given];                 // exactly the pairs given: a read beyond them is the sanitizer's
+        for (int k = 0; k < 2 * given; ++k)
+            if (scanf("%d", &yx[k]) != 1) return 2;
+        TileList tl;
+        memset(&tl, 0x7f, sizeof tl);
+        g_msg[0] = 0;
+        const int max_ty = kind == 'E' ? axt_last_tile(a, 512) : a, max_tx = kind == 'E' ? axt_last_tile(b, 512) : b;
+        const int rc = axt_tile_list("axt_some_entry", yx, n_tiles, max_ty, max_tx, &tl);
+        printf("%d", rc);
+        if (rc == AXT_OK) {
+            printf(" %d", tl.n);
+            for (int k = 0; k < 2 * tl.n; ++k) printf(" %d", (int)tl.yx[k]);
+        }
+        printf("|%s\n", g_msg);
+        delete[] yx;
+    }
+    return 0;
+}
+''')
+    text = ''.join(f'{kind} {a} {b} {n} {len(tiles)} ' + ' '.join(f'{ty} {tx}' for ty, tx in tiles) + '\n' for _, kind, a, b, n, tiles in cases)
+    csrc = os.path.join(ROOT, 'axtrack_amd', 'csrc')
+    for flags in ([], ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g']):
+        exe = tmp_path / ('tiles_san' if flags else 'tiles')
+        subprocess.check_call(['/opt/rocm/bin/hipcc', '-x', 'c++', '-std=c++17', '-D__HIP_PLATFORM_AMD__', '-I/opt/rocm/include', f'-I{csrc}', *flags,
+                               str(src), '-o', str(exe), '-L/opt/rocm/lib', '-lamdhip64', '-Wl,-rpath,/opt/rocm/lib'])
+        run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+        assert run.returncode == 0, f'{flags}: status {run.returncode}: {run.stderr[-2000:]}'
+        lines = run.stdout.splitlines()
+        assert len(lines) == len(cases)
+        for (name, kind, a, b, n, tiles), line in zip(cases, lines):
+            got, msg = line.split('|', 1)
+            got = [int(v) for v in got.split()]
+            rc, n_want, yx_want = expected(kind, a, b, n, tiles)
+            assert got[0] == rc, f'{name} {flags}: returned {got[0]}, expected {rc} ({msg})'
+            if rc == cc.OK:
+                assert got[1] == n_want and got[2:] == yx_want, f'{name} {flags}: the list differs'
+            else:
+                assert 'axt_some_entry' in msg, f'{name} {flags}: the message does not name the function: {msg!r}'
