@@ -144,6 +144,12 @@ SIGNATURES = {
                                   c_void_p]),
 }
 
+# exported and bound like the above, but declared under csrc/ (axt_tiff_inflate.h) and not yet part of the public ABI of
+# include/, whose contract table lists every prototype there
+INTERNAL_SIGNATURES = {
+    'axt_tiff_inflate_u16': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -159,7 +165,7 @@ def load():
             raise AxtError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            f'or `make -C axtrack_amd/csrc`. axtrack_amd has no CPU fallback.')
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **INTERNAL_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

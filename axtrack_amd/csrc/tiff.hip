@@ -22,33 +22,9 @@
 // Bad data ends a segment with a status code; nothing traps, prints or retries.
 #include "axt_common.h"
 #include "tiff_decode.h"
+#include "tiff_rows.h"
 
 namespace {
-
-constexpr int kTiffWave = 64;
-constexpr int kTiffMaxBlocks = 2048;
-
-__device__ __forceinline__ void tiff_finish_rows(const uint8_t *from, uint16_t *out, int rows, int W, int predictor, int big_endian,
-                                                 int lane)
-{
-    for (int r = 0; r < rows; ++r) {
-        const size_t row = (size_t)r * W;
-        uint16_t carry = 0;
-        for (int x0 = 0; x0 < W; x0 += kTiffWave) {                        // (wave-uniform trip count: the shuffles are safe)
-            const int x = x0 + lane;
-            unsigned v = x < W ? axt_tiff_sample(from + (row + x) * 2, big_endian) : 0u;
-            if (predictor == 2) {
-                for (int d = 1; d < kTiffWave; d <<= 1) {
-                    const unsigned up = __shfl_up(v, d, kTiffWave);
-                    if (lane >= d) v += up;
-                }
-                v += carry;
-                carry = (uint16_t)__shfl(v, kTiffWave - 1, kTiffWave);
-            }
-            if (x < W) out[row + x] = (uint16_t)v;
-        }
-    }
-}
 
 __global__ __launch_bounds__(kTiffWave) void tiff_decode_k(const uint8_t *__restrict__ d_src, int64_t src_len,
                                                          const axt_tiff_segment *__restrict__ segs, int n_segs, int W,

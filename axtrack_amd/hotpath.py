@@ -987,12 +987,15 @@ class McfShard:
 
 
 # ------------------------------------------------------------------ TIFF strips (csrc/tiff.hip, include/axtrack_hip_tiff.h)
-TIFF_STATUS_TEXT = {1: 'the input ends before the rows are complete', 2: 'an invalid LZW code',
-                    3: 'the data decodes to more than the rows of the strip', 4: 'the segment descriptor is out of range'}
+TIFF_STATUS_TEXT = {1: 'the input ends before the rows are complete', 2: 'an invalid LZW code or Deflate stream',
+                    3: 'the data decodes to more than the rows of the strip', 4: 'the segment descriptor is out of range',
+                    5: 'checksum: the Adler-32 of the Deflate stream is not that of the inflated bytes'}
+TIFF_INFLATE = (8, 32946)                            # Compression values of Deflate strips: csrc/tiff_inflate.hip
 
 
 def tiff_decode_launch(d_src, segs, W, compression, predictor, big_endian, out, status):
-    """axt_tiff_decode_u16 on the current stream, nothing waited for. d_src: uint8 device tensor; segs: TIFF_SEGMENT_DTYPE
+    """axt_tiff_decode_u16 -- for Deflate strips (compression 8, 32946) axt_tiff_inflate_u16 -- on the current stream,
+    nothing waited for. d_src: uint8 device tensor; segs: TIFF_SEGMENT_DTYPE
     records (host; uploaded here from pinned memory) or a device uint8 tensor that already holds them; out: contiguous
     2-byte device tensor, the records' dst_offset counted in its elements; status: int32 device tensor [n_segs]. Returns
     the device copy of the records, which the caller keeps until the stream has passed the launch."""
@@ -1011,9 +1014,14 @@ def tiff_decode_launch(d_src, segs, W, compression, predictor, big_endian, out, 
     assert d_src.device == out.device
     lib = _lib.load()
     with torch.cuda.device(out.device):
-        _lib.check(lib.axt_tiff_decode_u16(d_src.data_ptr(), d_src.numel(), d_segs.data_ptr(), n, int(W), int(compression),
-                                           int(predictor), int(bool(big_endian)), out.data_ptr(), out.numel(),
-                                           status.data_ptr(), _stream()), 'axt_tiff_decode_u16')
+        if int(compression) in TIFF_INFLATE:
+            _lib.check(lib.axt_tiff_inflate_u16(d_src.data_ptr(), d_src.numel(), d_segs.data_ptr(), n, int(W), int(predictor),
+                                                int(bool(big_endian)), out.data_ptr(), out.numel(), status.data_ptr(), _stream()),
+                       'axt_tiff_inflate_u16')
+        else:
+            _lib.check(lib.axt_tiff_decode_u16(d_src.data_ptr(), d_src.numel(), d_segs.data_ptr(), n, int(W), int(compression),
+                                               int(predictor), int(bool(big_endian)), out.data_ptr(), out.numel(),
+                                               status.data_ptr(), _stream()), 'axt_tiff_decode_u16')
     return d_segs
 
 

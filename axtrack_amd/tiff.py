@@ -1,5 +1,7 @@
 """TIFF timelapses without a third-party reader: the container is parsed here on the host with struct /
-numpy over a memory map, the strips are decoded on the GPU (csrc/tiff.hip through hotpath.tiff_decode_u16).
+numpy over a memory map, the strips are decoded on the GPU (csrc/tiff.hip, and csrc/tiff_inflate.hip for Deflate, through
+hotpath.tiff_decode_u16). The one place where the host still decodes pixel data is a pack of fewer than
+INFLATE_ON_DEVICE_FROM Deflate strips, where one core running zlib is measurably faster (inflate_on_device).
 
     info = tiff_info(path)            shape, byte order, compression, predictor and the segment table; reads tags only
     raw  = read_tiff(path)            the stack on the device as int16-viewed uint16 [T,H,W] (what _raw_on_device hands on)
@@ -16,6 +18,7 @@ COMPRESSION_NONE, COMPRESSION_LZW, COMPRESSION_DEFLATE, COMPRESSION_ADOBE_DEFLAT
 DEFLATE = (COMPRESSION_ADOBE_DEFLATE, COMPRESSION_DEFLATE)
 SUPPORTED_COMPRESSION = (COMPRESSION_NONE, COMPRESSION_LZW, COMPRESSION_PACKBITS) + DEFLATE
 CHUNK_FRAMES = 64                                    # read_tiff packs, copies and decodes at most this many frames at a time
+INFLATE_ON_DEVICE_FROM = 64                          # strips in a pack from which Deflate is inflated on the device (inflate_on_device)
 
 # tag numbers (TIFF 6.0)
 NEW_SUBFILE_TYPE, IMAGE_WIDTH, IMAGE_LENGTH, BITS_PER_SAMPLE, COMPRESSION, PHOTOMETRIC = 254, 256, 257, 258, 259, 262
@@ -268,20 +271,37 @@ def _frame_list(frames, T):
     return frames[0], frames[-1] + 1
 
 
+def inflate_on_device(n_segments):
+    """Whether a pack of n_segments Deflate strips is inflated on the device (csrc/tiff_inflate.hip) or by zlib on the host.
+    One wave inflates one strip, so a launch of very few large strips takes as long as one wave needs for its whole
+    strip, and one host core is faster there. Where the routes cross is a measurement, profiles/tiff_inflate_timing.json
+    ('small_packs': both routes on packs of 1 to 256 strips): the device's time is that of one wave's strip
+    whatever the count, the host's grows with it, and from 64 strips on the device wins both for strips of whole 512 x 512
+    pages (from 32 on) and for strips of 32 rows (the host still wins at 32)."""
+    return n_segments >= INFLATE_ON_DEVICE_FROM
+
+
 class SegmentPacker:
     """The strips of runs of frames, packed for the device. pack(a, b) -> (bytes as a numpy uint8 view of a pinned torch
     buffer, that buffer, descriptor records for hotpath.tiff_decode_u16 with dst offsets relative to frame a, the
-    segments' indices in the table, compression to decode with). Strips that follow one another in the file are copied
-    as one run. Deflate strips are inflated here, strip by strip, and travel as uncompressed ones."""
+    number of bytes packed). Strips that follow one another in the file are copied as one run, compressed as they are:
+    device_compression, what the records are to be decoded with, is the file's own.
 
-    def __init__(self, info):
-        self.info = info
+    inflate: where Deflate strips are inflated. 'device': they travel compressed like every other strip and
+    device_compression is 8 / 32946. 'host': zlib.decompress here, strip by strip; the inflated bytes travel and
+    device_compression is 1. None: inflate_on_device(number of strips) decides for every pack call, so device_compression
+    is to be read after pack."""
+
+    def __init__(self, info, inflate=None):
+        if inflate not in (None, 'device', 'host'):
+            raise ValueError(f"inflate is 'device', 'host' or None, not {inflate!r}")
+        self.info, self.inflate = info, inflate
         self.buf = np.memmap(info.path, dtype=np.uint8, mode='r')
         self.first = np.searchsorted(info.frame, np.arange(info.shape[0] + 1))       # (the table is in frame order)
         # little-endian, uncompressed, no predictor: where the packed strips also come out in frame order, one plain copy is
         # the whole job (the callers check the order)
         self.plain = info.compression == COMPRESSION_NONE and info.predictor == 1 and info.byteorder == '<'
-        self.device_compression = COMPRESSION_NONE if info.compression in DEFLATE else info.compression
+        self.device_compression = COMPRESSION_NONE if info.compression in DEFLATE and inflate == 'host' else info.compression
 
     def segments(self, a, b):
         return int(self.first[a]), int(self.first[b])
@@ -295,7 +315,11 @@ class SegmentPacker:
         segs = np.zeros(s1 - s0, TIFF_SEGMENT_DTYPE)
         segs['dst_offset'] = ((i.frame[s0:s1].astype(np.int64) - a) * H + i.row0[s0:s1]) * W
         segs['rows'] = i.rows[s0:s1]
+        on_host = False
         if i.compression in DEFLATE:
+            on_host = self.inflate == 'host' or (self.inflate is None and not inflate_on_device(s1 - s0))
+            self.device_compression = COMPRESSION_NONE if on_host else i.compression
+        if on_host:
             parts = []
             for k in range(s0, s1):
                 o, n = int(i.src_offset[k]), int(i.src_bytes[k])
@@ -330,7 +354,8 @@ def read_tiff(path, frames=None, device='cuda:0'):
     estimate_stnd_scaler take as they take an array), or with device='cpu' a numpy uint16 array by the same route plus one
     copy back. frames: a range or slice of consecutive pages. The strips' bytes go to the device as they are in the file,
     at most CHUNK_FRAMES frames at a time through a pinned buffer, and are expanded there; the statuses of all segments
-    are read once at the end, and a strip that does not decode raises TiffError naming its frame and row."""
+    are read once at the end, and a strip that does not decode -- a Deflate strip that does not inflate or fails its
+    Adler-32 included -- raises TiffError naming its frame and row."""
     import torch
     from . import hotpath as hp
     info = tiff_info(path)
