@@ -144,10 +144,13 @@ SIGNATURES = {
                                   c_void_p]),
 }
 
-# exported and bound like the above, but declared under csrc/ (axt_tiff_inflate.h) and not yet part of the public ABI of
-# include/, whose contract table lists every prototype there
+# exported and bound like the above, but declared under csrc/ (axt_tiff_inflate.h, axt_tiff_deflate.h) and not yet part of
+# the public ABI of include/, whose contract table lists every prototype there
 INTERNAL_SIGNATURES = {
     'axt_tiff_inflate_u16': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    'axt_tiff_deflate_bound': (c_int64, [c_int64]),
+    'axt_tiff_deflate_u16': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'axt_tiff_compact_streams': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

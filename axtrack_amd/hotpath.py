@@ -1049,6 +1049,89 @@ def tiff_decode_u16(d_src, segs, W, compression, predictor, big_endian, out, fra
     return out
 
 
+# ------------------------------------------------------------------ TIFF strips, deflated (csrc/tiff_deflate.hip, csrc/axt_tiff_deflate.h)
+TIFF_DEFLATE_STATUS_TEXT = {3: 'the stream does not fit its slot', 4: 'the segment descriptor is out of range'}
+
+
+def tiff_deflate_bound(raw_bytes):
+    """The longest stream axt_tiff_deflate_u16 writes for raw_bytes bytes: all stored (axt_tiff_deflate_bound)."""
+    return int(_lib.load().axt_tiff_deflate_bound(int(raw_bytes)))
+
+
+def _device_records(segs, device):
+    from .tiff import TIFF_SEGMENT_DTYPE
+    segs = np.ascontiguousarray(segs, TIFF_SEGMENT_DTYPE)
+    pinned = torch.empty(max(segs.nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    pinned.numpy()[:segs.nbytes] = segs.view(np.uint8)
+    d_segs = pinned.to(device, non_blocking=True)
+    d_segs._axt_pinned = pinned                                           # (alive as long as the device copy)
+    return d_segs
+
+
+def tiff_deflate_launch(samples, segs, W, predictor, slots, nbytes, status):
+    """axt_tiff_deflate_u16 on the current stream, nothing waited for. samples: contiguous 2-byte device tensor; segs:
+    TIFF_SEGMENT_DTYPE records (host; uploaded here from pinned memory) or a device uint8 tensor that holds them, with the
+    roles of csrc/axt_tiff_deflate.h: dst_offset / rows name the strip's samples, src_offset / src_bytes its slot in
+    `slots` (uint8 device tensor); nbytes: int64 [n_segs], status: int32 [n_segs], on the device. Returns the device copy of
+    the records, which the caller keeps until the stream has passed the launch."""
+    from .tiff import TIFF_SEGMENT_DTYPE
+    assert samples.is_contiguous() and samples.element_size() == 2 and slots.dtype == torch.uint8 and slots.is_contiguous()
+    if isinstance(segs, torch.Tensor):
+        d_segs, n = segs, segs.numel() // TIFF_SEGMENT_DTYPE.itemsize
+    else:
+        n = len(segs)
+        d_segs = _device_records(segs, samples.device)
+    assert nbytes.dtype == torch.int64 and status.dtype == torch.int32 and nbytes.numel() >= n and status.numel() >= n
+    assert nbytes.is_contiguous() and status.is_contiguous() and slots.device == samples.device == nbytes.device == status.device
+    with torch.cuda.device(samples.device):
+        _lib.check(_lib.load().axt_tiff_deflate_u16(samples.data_ptr(), samples.numel(), d_segs.data_ptr(), n, int(W), int(predictor),
+                                                    slots.data_ptr(), slots.numel(), nbytes.data_ptr(), status.data_ptr(), _stream()),
+                   'axt_tiff_deflate_u16')
+    return d_segs
+
+
+def tiff_compact_launch(slots, d_segs, nbytes, n, packed, offsets):
+    """axt_tiff_compact_streams on the current stream: the n streams back to back in `packed` (uint8 device tensor),
+    offsets: int64 [n + 1] on the device, the exclusive scan of the lengths and their sum."""
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and offsets.dtype == torch.int64 and offsets.numel() >= n + 1
+    with torch.cuda.device(slots.device):
+        _lib.check(_lib.load().axt_tiff_compact_streams(slots.data_ptr(), d_segs.data_ptr(), nbytes.data_ptr(), int(n), packed.data_ptr(),
+                                                        packed.numel(), offsets.data_ptr(), _stream()), 'axt_tiff_compact_streams')
+
+
+def tiff_deflate_strips(samples, segs, W, predictor, frame=None, row0=None):
+    """Deflate strips of a device tensor and bring the streams to the host: the launch into slots of the all-stored bound,
+    the compaction, then two copies -- the table of offsets and statuses, and the packed bytes through a pinned buffer, so
+    that only compressed bytes cross. segs: records with dst_offset / rows set; the slots are laid out here. Returns
+    (uint8 numpy view of the pinned buffer, int64 offsets [n + 1]). Raises tiff.TiffError naming the first failing strip."""
+    from .tiff import TIFF_SEGMENT_DTYPE, TiffError
+    segs = np.array(segs, TIFF_SEGMENT_DTYPE)
+    n, dev = len(segs), samples.device
+    caps = np.array([tiff_deflate_bound(2 * int(r) * int(W)) for r in np.unique(segs['rows'])], np.int64)
+    segs['src_bytes'] = caps[np.searchsorted(np.unique(segs['rows']), segs['rows'])]
+    segs['src_offset'] = np.concatenate([[0], np.cumsum(segs['src_bytes'])[:-1]]) if n else 0
+    total_cap = int(segs['src_bytes'].sum())
+    slots = torch.empty(max(total_cap, 1), dtype=torch.uint8, device=dev)
+    packed = torch.empty(max(total_cap, 1), dtype=torch.uint8, device=dev)
+    table = torch.zeros(2 * n + 2, dtype=torch.int64, device=dev)        # lengths [n], offsets [n + 1], pad
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    d_segs = tiff_deflate_launch(samples, segs, W, predictor, slots, table[:n], status)
+    tiff_compact_launch(slots, d_segs, table[:n], n, packed, table[n:2 * n + 1])
+    st = status[:n].cpu().numpy()                                         # (waits for the stream)
+    bad = np.flatnonzero(st)
+    if len(bad):
+        k = int(bad[0])
+        where = f'segment {k}' if frame is None else f'the strip of frame {int(frame[k])}, row {int(row0[k])} (segment {k})'
+        raise TiffError(f'{where} does not deflate: {TIFF_DEFLATE_STATUS_TEXT.get(int(st[k]), "status " + str(int(st[k])))} '
+                        f'(status {int(st[k])}; {len(bad)} of {n} segments fail)')
+    offsets = table[n:2 * n + 1].cpu().numpy()
+    total = int(offsets[-1])
+    host = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
+    host[:total].copy_(packed[:total])
+    del d_segs
+    return host.numpy()[:total], offsets
+
+
 # ------------------------------------------------------------------ JPEG scan segments (csrc/jpeg.hip, include/axtrack_hip_jpeg.h)
 def jpeg_scan_bound(H, W):
     """Worst-case bytes of one frame's scan segment (axt_jpeg_scan_bound)."""

@@ -21,6 +21,7 @@ import torch
 from . import params as _params
 from .detections import AxonDetections
 from .hotpath import Detector
+from . import hotpath as _hp
 from . import tiff as _tiff
 from .timelapse import (Timelapse, preprocess, pad_mask, estimate_stnd_scaler, frame_scales, load_labels_csv,
                         contiguous_runs)
@@ -137,6 +138,74 @@ def _read_stack(source, what, device='cuda:0'):
         return _tiff.read_stack(source, device=device)
     except _tiff.TiffUnsupported as e:
         raise _tiff.TiffUnsupported(f'{what} {source}: {e}') from e
+
+
+def process_timelapse(src, dest_basename, timeslice=None, offset=0, mask=None, second_mask=None, to_shape=None, H_slice=None,
+                      W_slice=None, device='cuda:0', **write_options):
+    """data_prep_nbs/01_process_training_timelapses.ipynb's process_timelapses for one recording, on the device: the step
+    between segment_mask and prepare_training_data, which "may also be used to preprocess inference data".
+    -> (stack as int16-viewed uint16 [T,H,W] on the device, mask as a bool numpy array or None).
+
+    src: a .tif name (read_tiff), a .npy name or an array; timeslice: (start, stop) frames. offset: subtracted,
+    saturating -- values below it become 0. second_mask, then mask (.npy names or arrays, True = keep): pixels outside
+    become 0. to_shape (H, W): zero padding of (to - size) // 2 on BOTH sides of an axis, exactly as the notebook pads,
+    so an odd difference ends one short of to_shape; a to_shape smaller than the frames raises. H_slice / W_slice: (start,
+    stop) behind the padding; the mask is padded and sliced alike. {dest_basename}.tif is written by write_tiff
+    (write_options: rows_per_strip, predictor, bigtiff, deflate, description, level; the notebook's bigtiff=True is not
+    forced), the adjusted mask by np.save as {dest_basename}.npy."""
+    _hp._require_gpu()
+    dev = torch.device(device)
+    if _tiff.is_tiff_name(src):
+        T = _tiff.tiff_info(src).shape[0]
+        frames = None if timeslice is None else range(*slice(*timeslice).indices(T))
+        stack = _tiff.read_tiff(src, frames=frames, device=dev)
+    else:
+        a = np.load(src) if isinstance(src, str) else src
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a)
+            if a.dtype not in (np.uint16, np.int16):
+                raise TypeError(f'the timelapse is {a.dtype}, not uint16')
+            a = torch.from_numpy(np.ascontiguousarray(a).view(np.int16))
+        stack = a.to(dev)
+        if timeslice is not None:
+            stack = stack[timeslice[0]:timeslice[1]]
+    if stack.dim() != 3:
+        raise ValueError(f'the timelapse must be [T,H,W], got {tuple(stack.shape)}')
+    s = stack.to(torch.int32) & 0xffff                                    # the raw counts as numbers
+    s = (s - int(offset)).clamp_(min=0)
+
+    def load_mask(m):
+        m = np.load(m) if isinstance(m, str) else np.asarray(m)
+        if m.shape != tuple(s.shape[1:]):
+            raise ValueError(f'a mask of shape {m.shape} on frames of {tuple(s.shape[1:])}')
+        return m.astype(bool)
+    if second_mask is not None:
+        s[:, ~torch.from_numpy(load_mask(second_mask)).to(dev)] = 0
+    if mask is not None:
+        mask = load_mask(mask)
+        s[:, ~torch.from_numpy(mask).to(dev)] = 0
+    if to_shape is not None:
+        ph, pw = (int(to_shape[0]) - s.shape[1]) // 2, (int(to_shape[1]) - s.shape[2]) // 2
+        if ph < 0 or pw < 0:
+            raise ValueError(f'to_shape {tuple(to_shape)} is smaller than the frames of {tuple(s.shape[1:])}: padding only')
+        s = torch.nn.functional.pad(s, (pw, pw, ph, ph))
+        if mask is not None:
+            mask = np.pad(mask, ((ph, ph), (pw, pw)), mode='constant')
+    for axis, sl in ((1, H_slice), (2, W_slice)):
+        if sl is not None:
+            s = s.narrow(axis, *_slice_start_length(sl, s.shape[axis]))
+            if mask is not None:
+                mask = mask[sl[0]:sl[1]] if axis == 1 else mask[:, sl[0]:sl[1]]
+    out = torch.where(s >= 32768, s - 65536, s).to(torch.int16).contiguous()     # (0..65535 as int16-viewed uint16)
+    _tiff.write_tiff(f'{dest_basename}.tif', out, **write_options)
+    if mask is not None:
+        np.save(f'{dest_basename}.npy', mask)
+    return out, mask
+
+
+def _slice_start_length(sl, size):
+    start, stop, _ = slice(sl[0], sl[1]).indices(size)
+    return start, max(stop - start, 0)
 
 
 def prepare_training_data(parameters, skip_test=False, **overrides):

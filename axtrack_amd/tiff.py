@@ -5,6 +5,8 @@ INFLATE_ON_DEVICE_FROM Deflate strips, where one core running zlib is measurably
 
     info = tiff_info(path)            shape, byte order, compression, predictor and the segment table; reads tags only
     raw  = read_tiff(path)            the stack on the device as int16-viewed uint16 [T,H,W] (what _raw_on_device hands on)
+    write_tiff(path, stack)           the stack as a Deflate TIFF, its strips deflated on the GPU (csrc/tiff_deflate.hip); the
+                                      container (TiffWriter, build_ifd) is written here on the host
 
 Supported: classic TIFF and BigTIFF, both byte orders, strips, one 16-bit unsigned grayscale plane per page, compression
 none / PackBits / LZW / Deflate, predictor none / horizontal, and ImageJ's single-IFD hyperstacks. Anything else raises
@@ -19,6 +21,7 @@ DEFLATE = (COMPRESSION_ADOBE_DEFLATE, COMPRESSION_DEFLATE)
 SUPPORTED_COMPRESSION = (COMPRESSION_NONE, COMPRESSION_LZW, COMPRESSION_PACKBITS) + DEFLATE
 CHUNK_FRAMES = 64                                    # read_tiff packs, copies and decodes at most this many frames at a time
 INFLATE_ON_DEVICE_FROM = 64                          # strips in a pack from which Deflate is inflated on the device (inflate_on_device)
+DEFLATE_ON_DEVICE_FROM = 64                          # strips in a chunk from which write_tiff deflates on the device (deflate_on_device)
 
 # tag numbers (TIFF 6.0)
 NEW_SUBFILE_TYPE, IMAGE_WIDTH, IMAGE_LENGTH, BITS_PER_SAMPLE, COMPRESSION, PHOTOMETRIC = 254, 256, 257, 258, 259, 262
@@ -405,3 +408,219 @@ def read_stack(path, device='cuda:0', to_host=True):
 
 def is_tiff_name(name):
     return isinstance(name, str) and name.lower().endswith(('.tif', '.tiff'))
+
+
+# ====================================================================================================== TIFF output
+def deflate_on_device(n_strips):
+    """Whether write_tiff deflates a chunk of n_strips strips on the device (csrc/tiff_deflate.hip) or with zlib in a
+    pool of host threads. One wave deflates one strip, so a launch of few strips takes as long as one wave needs for its
+    strip whatever the count, while the host's time grows with the count; where the routes cross is a measurement
+    (profiles/tiff_deflate_timing.py, 'small_packs'). That measurement has not been run yet: the threshold is the
+    inflater's crossover, taken over as a placeholder (DESIGN.md 6.8h "TIFF output", "Time and routing")."""
+    return n_strips >= DEFLATE_ON_DEVICE_FROM
+
+
+def strip_layout(H, W, rows_per_strip=None):
+    """-> (rows per strip, first row of every strip, rows of every strip). None: as many rows as fit 32 KiB, the Deflate
+    window, at least one and at most H."""
+    if rows_per_strip is None:
+        rows_per_strip = min(H, max(1, 32768 // (2 * W)))
+    rps = int(rows_per_strip)
+    if not 1 <= rps <= H:
+        raise ValueError(f'rows_per_strip {rows_per_strip} is not in 1..{H}')
+    row0 = np.arange(0, H, rps, dtype=np.int64)
+    return rps, row0, np.minimum(rps, H - row0)
+
+
+def stored_bound(raw_bytes):
+    """The all-stored zlib stream of raw_bytes bytes: what axt_tiff_deflate_bound returns."""
+    return raw_bytes + 5 * max(1, -(-raw_bytes // 65535)) + 6
+
+
+def _ifd_size(n_strips, big, desc_len):
+    """Bytes of one IFD of build_ifd with its out-of-line values, at most (twelve entries)."""
+    tables = 2 * n_strips * (8 if big else 4) if n_strips > 1 else 0
+    return (8 + 12 * 20 + 8 if big else 2 + 12 * 12 + 4) + tables + desc_len + (desc_len & 1)
+
+
+def file_bound(T, H, W, rows_per_strip, big, desc_len=0):
+    """The size of the file write_tiff writes if every strip came out stored: what decides between TIFF and BigTIFF."""
+    rps, row0, rows = strip_layout(H, W, rows_per_strip)
+    page = int(sum(stored_bound(2 * int(r) * W) for r in rows)) + 1 + _ifd_size(len(rows), big, 0)
+    return (16 if big else 8) + T * page + desc_len + (desc_len & 1)
+
+
+def choose_bigtiff(T, H, W, rows_per_strip=None, bigtiff=None, desc_len=0):
+    """bigtiff None: classic TIFF where the all-stored bound of the whole file stays below 4 GiB, else BigTIFF. False on
+    a file that may not fit raises."""
+    fits = file_bound(T, H, W, rows_per_strip, False, desc_len) < 1 << 32
+    if bigtiff is None:
+        return not fits
+    if not bigtiff and not fits:
+        raise ValueError(f'{T} pages of {H} x {W} may take {file_bound(T, H, W, rows_per_strip, False, desc_len)} bytes, more than '
+                         f'the 4 GiB of classic TIFF offsets: bigtiff=False cannot be kept')
+    return bool(bigtiff)
+
+
+def tiff_header(big, first_ifd=0):
+    return struct.pack('<2sHHHQ', b'II', 43, 8, 0, first_ifd) if big else struct.pack('<2sHI', b'II', 42, first_ifd)
+
+
+def build_ifd(at, H, W, rows_per_strip, predictor, big, strip_offsets, strip_counts, description=None, next_ifd=0):
+    """One page's IFD as it stands at the even file offset `at`, its out-of-line values (the strip tables, the description)
+    behind it, each at an even offset: little-endian, Compression 8, PhotometricInterpretation 1, SampleFormat 1,
+    Predictor only when it is 2, tags in ascending order. -> (bytes, where in them the offset of the next IFD stands)."""
+    assert at % 2 == 0 and len(strip_offsets) == len(strip_counts) == -(-H // rows_per_strip)
+    otype, ofmt, inline = (16, 'Q', 8) if big else (4, 'I', 4)
+    n = len(strip_offsets)
+    entries = [(IMAGE_WIDTH, 4, [W]), (IMAGE_LENGTH, 4, [H]), (BITS_PER_SAMPLE, 3, [16]), (COMPRESSION, 3, [COMPRESSION_ADOBE_DEFLATE]),
+               (PHOTOMETRIC, 3, [1])]
+    if description is not None:
+        entries.append((IMAGE_DESCRIPTION, 2, bytes(description) + b'\0'))
+    entries += [(STRIP_OFFSETS, otype, list(strip_offsets)), (SAMPLES_PER_PIXEL, 3, [1]), (ROWS_PER_STRIP, 4, [rows_per_strip]),
+                (STRIP_BYTE_COUNTS, otype, list(strip_counts))]
+    if predictor == 2:
+        entries.append((PREDICTOR, 3, [2]))
+    entries.append((SAMPLE_FORMAT, 3, [1]))
+    head = 8 + 20 * len(entries) + 8 if big else 2 + 12 * len(entries) + 4
+    body, extra = struct.pack('<Q' if big else '<H', len(entries)), b''
+    for tag, ftype, values in entries:
+        if ftype == 2:
+            data, count = values, len(values)
+        else:
+            data, count = struct.pack(f'<{len(values)}{FIELD_TYPES[ftype][0]}', *values), len(values)
+        if len(data) > inline:
+            where = at + head + len(extra)
+            extra += data + b'\0' * (len(data) & 1)
+            data = struct.pack('<' + ofmt, where)
+        body += struct.pack('<HH' + ofmt, tag, ftype, count) + data.ljust(inline, b'\0')
+    next_at = len(body)
+    return body + struct.pack('<' + ofmt, next_ifd) + extra, next_at
+
+
+class TiffWriter:
+    """The container of write_tiff: pages of Deflate strips in a file, one IFD behind each page's strips, which follow one
+    another without a gap so that a reader copies them as one run. Host only; the strips come compressed."""
+
+    def __init__(self, path, H, W, rows_per_strip=None, predictor=1, big=False, description=None):
+        if predictor not in (1, 2):
+            raise ValueError(f'predictor {predictor} is not 1 (none) or 2 (horizontal differencing)')
+        self.H, self.W, self.predictor, self.big, self.description = H, W, predictor, bool(big), description
+        self.rps, self.row0, self.rows = strip_layout(H, W, rows_per_strip)
+        self.f = open(path, 'wb')
+        self.f.write(tiff_header(self.big))
+        self.pos = 16 if self.big else 8
+        self.link = 8 if self.big else 4                                  # where the offset of the next IFD is to be written
+        self.pages, self.strip_bytes, self.ifd_bytes = 0, 0, 0
+
+    def add_page(self, strips):
+        if len(strips) != len(self.rows):
+            raise ValueError(f'a page has {len(self.rows)} strips, not {len(strips)}')
+        offsets, counts = [], []
+        for s in strips:
+            offsets.append(self.pos), counts.append(len(s))
+            self.f.write(s)
+            self.pos += len(s)
+        self.strip_bytes += sum(counts)
+        if self.pos & 1:
+            self.f.write(b'\0')
+            self.pos += 1
+            self.ifd_bytes += 1
+        if not self.big and self.pos + _ifd_size(len(strips), False, len(self.description or b'') + 1) >= 1 << 32:
+            raise TiffError(f'page {self.pages} ends beyond the 4 GiB of classic TIFF offsets')
+        ifd, next_at = build_ifd(self.pos, self.H, self.W, self.rps, self.predictor, self.big, offsets, counts,
+                                 self.description if self.pages == 0 else None)
+        self.f.write(ifd)
+        self.f.seek(self.link)
+        self.f.write(struct.pack('<Q' if self.big else '<I', self.pos))
+        self.f.seek(0, 2)
+        self.link = self.pos + next_at
+        self.pos += len(ifd)
+        self.ifd_bytes += len(ifd)
+        self.pages += 1
+
+    def close(self):
+        self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def apply_predictor(a, predictor):
+    """uint16 [..., W] as stored: with predictor 2 every sample minus its left neighbour, modulo 2^16."""
+    a = np.asarray(a, np.uint16)
+    if predictor == 2:
+        d = a.copy()
+        d[..., 1:] -= a[..., :-1]
+        a = d
+    return a
+
+
+def _deflate_on_host(raw, row0, rows, predictor, level):
+    """raw: uint16 [frames, H, W] on the host -> every strip's zlib stream, frame by frame, in a pool of threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .render import _POOL_THREADS
+    stored = np.ascontiguousarray(apply_predictor(raw, predictor), '<u2')
+    jobs = [(t, int(r0), int(r)) for t in range(len(stored)) for r0, r in zip(row0, rows)]
+    with ThreadPoolExecutor(max_workers=_POOL_THREADS) as pool:
+        return list(pool.map(lambda j: zlib.compress(stored[j[0], j[1]:j[1] + j[2]].data, level), jobs))
+
+
+def write_tiff(path, stack, rows_per_strip=None, predictor=1, bigtiff=None, deflate=None, description=None, level=6):
+    """Write a timelapse as a Deflate TIFF (Compression 8), one page per frame, the strips deflated on the GPU
+    (csrc/tiff_deflate.hip): what tifffile's imsave(..., photometric='minisblack', compression='deflate') is used for.
+
+    stack: uint16 -- or the int16-viewed raw counts read_tiff returns -- [T,H,W] or [H,W], a device tensor, a host tensor
+    or a numpy array (uploaded one chunk of CHUNK_FRAMES frames at a time). rows_per_strip None: as many rows as fit the
+    32 KiB Deflate window (16 strips for a 512 x 512 page); any value 1..H. predictor 2: horizontal differencing. bigtiff
+    None: classic TIFF where the file cannot pass 4 GiB, else BigTIFF. deflate 'device' / 'host' / None: where the strips
+    are deflated; None asks deflate_on_device for every chunk; the host route is zlib at `level` in a pool of threads,
+    behind a copy of the raw chunk to the host. description: bytes for page 0's ImageDescription.
+    Returns the TiffWriter (closed): pages, strip_bytes, ifd_bytes."""
+    import torch
+    from . import hotpath as hp
+    if deflate not in (None, 'device', 'host'):
+        raise ValueError(f"deflate is 'device', 'host' or None, not {deflate!r}")
+    on_host_array = not isinstance(stack, torch.Tensor)
+    if on_host_array:
+        stack = np.asarray(stack)
+        if stack.dtype not in (np.uint16, np.int16):
+            raise TypeError(f'stack is {stack.dtype}, not uint16 (or int16-viewed raw counts)')
+        stack = torch.from_numpy(np.ascontiguousarray(stack).view(np.int16))
+    elif stack.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)):
+        raise TypeError(f'stack is {stack.dtype}, not uint16 (or int16-viewed raw counts)')
+    elif stack.dtype != torch.int16:
+        stack = stack.view(torch.int16)
+    if stack.dim() == 2:
+        stack = stack[None]
+    if stack.dim() != 3 or 0 in stack.shape:
+        raise ValueError(f'stack has shape {tuple(stack.shape)}, not [T,H,W] or [H,W]')
+    T, H, W = stack.shape
+    rps, row0, rows = strip_layout(H, W, rows_per_strip)
+    desc = None if description is None else (description.encode() if isinstance(description, str) else bytes(description))
+    big = choose_bigtiff(T, H, W, rps, bigtiff, 0 if desc is None else len(desc) + 1)      # (raises before anything is written)
+    hp._require_gpu()
+    dev = stack.device if stack.is_cuda else torch.device('cuda:0')
+    per_page = len(rows)
+    with TiffWriter(path, H, W, rps, predictor, big, desc) as w, torch.cuda.device(dev):
+        for c0 in range(0, T, CHUNK_FRAMES):
+            c1 = min(c0 + CHUNK_FRAMES, T)
+            n = (c1 - c0) * per_page
+            on_device = deflate == 'device' or (deflate is None and deflate_on_device(n))
+            if on_device:
+                chunk = stack[c0:c1].contiguous().to(dev, non_blocking=True)
+                segs = np.zeros(n, TIFF_SEGMENT_DTYPE)
+                frame = np.repeat(np.arange(c0, c1), per_page)
+                segs['dst_offset'] = ((frame - c0) * H + np.tile(row0, c1 - c0)) * W
+                segs['rows'] = np.tile(rows, c1 - c0)
+                data, offsets = hp.tiff_deflate_strips(chunk, segs, W, predictor, frame, np.tile(row0, c1 - c0))
+                strips = [data[int(offsets[k]):int(offsets[k + 1])] for k in range(n)]
+            else:
+                raw = stack[c0:c1].cpu().numpy().view(np.uint16)
+                strips = _deflate_on_host(raw, row0, rows, predictor, level)
+            for t in range(c1 - c0):
+                w.add_page(strips[t * per_page:(t + 1) * per_page])
+    return w
